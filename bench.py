@@ -14,6 +14,11 @@ layout, README_PARALLEL.md:60-67) -- strong scaling, no data-path collective
 global particle number, so the result does not depend on N.  --weak keeps the
 per-GPU count fixed instead.
 
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what
+takes runs of its own: the CPU baseline (the reference's loop on a sample) and the rocprofv3
+counter passes over the dominant kernel.  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy (float64) so that two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -55,7 +60,13 @@ def parse():
                     "e.g. --particles 12500000 --global-particles 1e8 = the shard one of eight GPUs runs, with that run's decisions")
     ap.add_argument("--slice-passes", type=int, default=0, help="fpx_config.pbl_slice_passes: 0 the engine's schedule, -1 one launch, k passes per launch")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="fpx_set_option knob (repeatable), e.g. --opt pbl_slices=48,96,0")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and the rocprofv3 counter passes (--no-cpu-baseline / --no-pmc leave one out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float64; rank 0): a fixed sample of the particles, by particle number, and in configs 4-5 the concentration grids")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def build_scenario(cfg, nsteps, poles=False, without=()):
@@ -323,6 +334,30 @@ def cpu_baseline(args, sc, frac_pbl):
                       f"first step includes initialize())"}
 
 
+DUMP_BLOCKS, DUMP_BLOCK = 32, 8192      # the particle sample of --dump-outputs: 32 runs of 8192 consecutive particle numbers
+
+
+def dump_outputs(eng, outdir, nper, base, grids=None):
+    """What the timed path leaves after its last step, as float64 DIR/<name>.npy: every per-particle array the engine hands
+    back (fpx_download_particles) for a fixed sample of particles -- DUMP_BLOCKS runs of DUMP_BLOCK consecutive particle
+    numbers at seeded offsets, or all of them when there are fewer -- with their global particle numbers, and the grids the
+    timed region read back.  The download goes by particle number, so the locality re-sort does not change the sample;
+    integer fields are exact in float64.  At most 22 arrays x 270335 particles x 8 B + 5.7 MB of grids: under 64 MB."""
+    os.makedirs(outdir, exist_ok=True)
+    nblk = nper // DUMP_BLOCK
+    if nblk <= DUMP_BLOCKS:
+        ranges = [(0, nper)]
+    else:
+        starts = np.sort(np.random.default_rng(0x5EED).choice(nblk, DUMP_BLOCKS, replace=False)) * DUMP_BLOCK
+        ranges = [(int(s), DUMP_BLOCK) for s in starts]
+    parts = [eng.download(first, count) for first, count in ranges]
+    arrays = {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]}
+    arrays["particle_number"] = np.concatenate([np.arange(base + first, base + first + count) for first, count in ranges])
+    arrays.update(grids or {})
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -408,10 +443,11 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.warmup, total_steps):
         do_step(i)
-    grid_sum = None
+    grid_sum = grids = None
     if args.config in (4, 5):
-        grid, _ = eng.grids(allreduce=world > 1)     # the grid reduction over the ranks + D2H of the sums: part of the job
+        grid, dry = eng.grids(allreduce=world > 1)     # the grid reduction over the ranks + D2H of the sums: part of the job
         grid_sum = float(np.asarray(grid, dtype=np.float64).sum())
+        grids = {"gridunc": grid, "drygridunc": dry}
     # the end of the timed region is an output time: the particle count over the ranks, as the reference's root reduces it
     t_cnt = time.perf_counter()
     eng.sync()
@@ -506,14 +542,16 @@ def main():
     if args.pmc_child:
         eng.close()
         return
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, nper, lo, grids)
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         try:
             out["cpu_baseline"] = cpu_baseline(args, sc, frac_pbl)
         except Exception as e:  # the baseline must not sink the GPU number
             out["cpu_baseline"] = {"value": None, "unit": "particle-steps/s", "cores": 1, "kind": "reference",
                                    "sample": f"failed: {e}"}
     eng.close()
-    if rank == 0 and world == 1 and not args.no_pmc:
+    if rank == 0 and world == 1 and args.full and not args.no_pmc:
         # after the engine has released the GPU: the counter pass runs the same workload in a child process
         grp = n_slices if dom == 1 else 1
         out["roofline"]["valu"] = live_valu(args, dom_name, avg_ms, nsteps_local / max(launches, 1), grp)

@@ -42,8 +42,13 @@ def test_struct_sizes_match_header(built):
 
 
 def test_no_device_is_an_error_not_a_fallback(built):
-    import torch
-    if torch.cuda.is_available():
+    # asked in a child process: torch carries its own HIP runtime, and once that one has opened the device in this
+    # process, the library's (ROCm's) runtime sees no device -- every GPU test after this one in the run would fail
+    import subprocess, sys
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"],
+                           capture_output=True, text=True, timeout=300)
+    assert probe.returncode == 0, probe.stderr[-2000:]
+    if probe.stdout.split()[-1] == "True":
         pytest.skip("a GPU is present")
     from flexpart_amd import _lib
     lib = _lib.load()
