@@ -2235,7 +2235,6 @@ struct Engine : EngineBase {
     V.eps = (R)(cfg.par_nxmax > 0 ? cfg.par_nxmax : cfg.nxmax) / (R)3.e5;   // advance.f90:107
     V.numbnests = 0;
     V.nest = nullptr;
-    g_nx = cfg.nx; g_ny = cfg.ny; g_nxmax = cfg.nxmax; g_nymax = cfg.nymax;
 
     const size_t ncol = (size_t)cfg.nx * cfg.ny, nlev = ncol * cfg.nz;
     R *p;
@@ -2360,40 +2359,104 @@ struct Engine : EngineBase {
     return 0;
   }
 
-  // stage one host array and repack it
-  // geometry of the host array being repacked (mother grid by default, a nest during nest uploads)
-  int g_nx = 0, g_ny = 0, g_nxmax = 0, g_nymax = 0;
-  template <typename H>
-  int pack3(const void *host, R *out, int stride, int off) {
-    const size_t n = (size_t)g_nxmax * g_nymax * cfg.nz;   // levels beyond nz are never read
-    int rc = ensure_staging(n * sizeof(H));
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(staging, host, n * sizeof(H), hipMemcpyHostToDevice, stream));
-    dim3 grid((g_nx + 31) / 32, (cfg.nz + 31) / 32, g_ny), block(32, 8);
-    k_pack3<H, R><<<grid, block, 0, stream>>>((const H *)staging, out, g_nx, g_ny, cfg.nz, g_nxmax, g_nymax, stride, off);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));   // staging is reused by the next field
-    return 0;
+  // ---- host arrays -> device packs ----------------------------------------------------------
+  // Extents of the host arrays of grid g (0: the mother grid, l >= 1: nested grid l): nx, ny used of nxmax, nymax allocated.
+  struct HostGrid { int nx, ny, nxmax, nymax; };
+  HostGrid host_grid(int g) const {
+    if (g == 0) return {cfg.nx, cfg.ny, cfg.nxmax, cfg.nymax};
+    return {h_nest[g - 1].nx, h_nest[g - 1].ny, nest_nxmaxn, nest_nymaxn};
   }
-  template <typename H>
-  int pack2(const void *host, R *out, int stride, int off) {
-    const size_t n = (size_t)g_nxmax * g_nymax;
-    int rc = ensure_staging(n * sizeof(H));
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(staging, host, n * sizeof(H), hipMemcpyHostToDevice, stream));
-    int tot = g_nx * g_ny;
-    k_pack2<H, R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>((const H *)staging, out, g_nx, g_ny, g_nxmax, stride, off);
+  // n elements of T from the host through the staging buffer (or, `on_device`, where they are) into launch(), then wait:
+  // staging is reused by the next array
+  template <typename T, typename Launch>
+  int staged_launch(const void *src, size_t n, bool on_device, Launch launch) {
+    if (!on_device) {
+      int rc = ensure_staging(n * sizeof(T));
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(staging, src, n * sizeof(T), hipMemcpyHostToDevice, stream));
+      src = staging;
+    }
+    launch((const T *)src);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(stream));
     return 0;
   }
-  int p3(const void *host, const R *out, int stride, int off) {
-    return cfg.host_real_bytes == 4 ? pack3<float>(host, (R *)out, stride, off) : pack3<double>(host, (R *)out, stride, off);
+  // [nz][nymax][nxmax] -> component `off` of a [ny][nx][nz][stride] pack (x<->z transpose)
+  template <typename H, typename O>
+  int pack3(HostGrid g, const void *src, O *out, int stride, int off, bool on_device = false) {
+    return staged_launch<H>(src, (size_t)g.nxmax * g.nymax * cfg.nz, on_device, [&](const H *in) {   // levels beyond nz are never read
+      dim3 grid((g.nx + 31) / 32, (cfg.nz + 31) / 32, g.ny), block(32, 8);
+      k_pack3<H, O><<<grid, block, 0, stream>>>(in, out, g.nx, g.ny, cfg.nz, g.nxmax, g.nymax, stride, off);
+    });
   }
-  int p2(const void *host, const R *out, int stride, int off) {
-    return cfg.host_real_bytes == 4 ? pack2<float>(host, (R *)out, stride, off) : pack2<double>(host, (R *)out, stride, off);
+  // [nymax][nxmax] -> component `off` of a [ny][nx][stride] pack
+  template <typename H>
+  int pack2(HostGrid g, const void *host, R *out, int stride, int off) {
+    return staged_launch<H>(host, (size_t)g.nxmax * g.nymax, false, [&](const H *in) {
+      const int tot = g.nx * g.ny;
+      k_pack2<H, R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, out, g.nx, g.ny, g.nxmax, stride, off);
+    });
+  }
+  // nlev of [nlevmax][nymax][nxmax] -> compact [nlev][ny][nx], still in the host's real kind
+  template <typename H>
+  int compact_t(HostGrid g, const void *host, void *out, int nlev, int nlevmax) {
+    return staged_launch<H>(host, (size_t)g.nxmax * g.nymax * nlevmax, false, [&](const H *in) {
+      const long long n = (long long)g.nx * g.ny * nlev;
+      k_conv_pack<H, H><<<(int)((n + kBlock - 1) / kBlock), kBlock, 0, stream>>>(in, (H *)out, g.nx, g.ny, nlev, g.nxmax, g.nymax);
+    });
+  }
+  int p3(HostGrid g, const void *host, const R *out, int stride, int off) {
+    return cfg.host_real_bytes == 4 ? pack3<float>(g, host, (R *)out, stride, off) : pack3<double>(g, host, (R *)out, stride, off);
+  }
+  int p2(HostGrid g, const void *host, const R *out, int stride, int off) {
+    return cfg.host_real_bytes == 4 ? pack2<float>(g, host, (R *)out, stride, off) : pack2<double>(g, host, (R *)out, stride, off);
+  }
+  int compact(HostGrid g, const void *host, void *out, int nlev, int nlevmax) {
+    return cfg.host_real_bytes == 4 ? compact_t<float>(g, host, out, nlev, nlevmax) : compact_t<double>(g, host, out, nlev, nlevmax);
   }
 
+  // ---- wind fields of one grid and time slot ---------------------------------------------------
+  struct WindDst { const R *w3, *r2, *sfc, *tropo, *vdep, *hcell, *w3pol, *rhott; };   // w3pol, rhott: the mother grid's alone
+  WindDst wind_dst(int g) const {
+    if (g == 0) return {V.w3, V.r2, V.sfc, V.tropo, V.vdep, V.hcell, V.w3pol, V.rhott};
+    const NestDesc<R> &N = h_nest[g - 1];
+    return {N.w3, N.r2, N.sfc, N.tropo, N.vdep, N.hcell, nullptr, nullptr};
+  }
+  // the 2-D fields (what calcpar / calcpar_nests leave on the host when the 3-D ones come from the device transform)
+  int upload_wind2(int g, int slot, const fpx_fields *f) {
+    const HostGrid G = host_grid(g);
+    const WindDst T = wind_dst(g);
+    const int s = slot - 1;
+    int rc;
+    if ((rc = p2(G, f->ustar, T.sfc, 8, s * 4 + 0)) || (rc = p2(G, f->wstar, T.sfc, 8, s * 4 + 1)) ||
+        (rc = p2(G, f->oli, T.sfc, 8, s * 4 + 2)) || (rc = p2(G, f->hmix, T.sfc, 8, s * 4 + 3))) return rc;
+    if (slot == 1 && (rc = p2(G, f->tropopause, T.tropo, 1, 0))) return rc;   // literal time index 1: advance.f90:253 (tropopausen: advance.f90:263)
+    if (T.vdep) {
+      const size_t plane = (size_t)G.nxmax * G.nymax * cfg.host_real_bytes;
+      for (int ks = 0; ks < cfg.nspec; ks++)
+        if ((rc = p2(G, (const char *)f->vdep + plane * ks, T.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
+    }
+    if (g == 0 && ((rc = diag_alloc()) || (rc = diag2_from_host(diag_tropo[s], f->tropopause, DG_TROPO + s)))) return rc;   // partoutput interpolates it in time
+    return 0;
+  }
+  int upload_wind(int g, int slot, const fpx_fields *f) {
+    const HostGrid G = host_grid(g);
+    const WindDst T = wind_dst(g);
+    const int s = slot - 1;
+    int rc;
+    if ((rc = p3(G, f->uu, T.w3, 6, s * 3 + 0)) || (rc = p3(G, f->vv, T.w3, 6, s * 3 + 1)) || (rc = p3(G, f->ww, T.w3, 6, s * 3 + 2))) return rc;
+    if (g == 0 && T.w3pol)
+      if ((rc = p3(G, f->uupol, T.w3pol, 6, s * 3 + 0)) || (rc = p3(G, f->vvpol, T.w3pol, 6, s * 3 + 1)) || (rc = p3(G, f->ww, T.w3pol, 6, s * 3 + 2))) return rc;
+    if ((rc = p3(G, f->rho, T.r2, 4, s * 2 + 0)) || (rc = p3(G, f->drhodz, T.r2, 4, s * 2 + 1))) return rc;
+    if (g == 0 && slot == 1 && T.rhott)   // literal time index 1: get_settling.f90:83-84
+      if ((rc = p3(G, f->rho, T.rhott, 2, 0)) || (rc = p3(G, f->tt, T.rhott, 2, 1))) return rc;
+    if ((rc = upload_wind2(g, slot, f))) return rc;
+    k_hcell<R><<<(G.nx * G.ny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(T.sfc, (R *)T.hcell, G.nx, G.ny);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    if (g == 0) slot_loaded[s] = true; else nest_loaded[g - 1][s] = true;
+    return 0;
+  }
   int upload_fields(int slot, const fpx_fields *f) override {
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_fields: slot must be 1 or 2");
     if (!f || !f->uu || !f->vv || !f->ww || !f->rho || !f->drhodz || !f->hmix || !f->ustar || !f->wstar || !f->oli || !f->tropopause)
@@ -2401,41 +2464,15 @@ struct Engine : EngineBase {
     if ((cfg.nglobal || cfg.sglobal) && (!f->uupol || !f->vvpol)) return fail(FPX_ERR_ARG, "upload_fields: uupol/vvpol required on a grid with poles");
     if (cfg.drydep && !f->vdep) return fail(FPX_ERR_ARG, "upload_fields: vdep required with DRYDEP");
     if (cfg.lsettling && !f->tt) return fail(FPX_ERR_ARG, "upload_fields: tt required with lsettling");
-    const int s = slot - 1;
-    int rc;
-    if ((rc = p3(f->uu, V.w3, 6, s * 3 + 0))) return rc;
-    if ((rc = p3(f->vv, V.w3, 6, s * 3 + 1))) return rc;
-    if ((rc = p3(f->ww, V.w3, 6, s * 3 + 2))) return rc;
-    if (V.w3pol) {
-      if ((rc = p3(f->uupol, V.w3pol, 6, s * 3 + 0))) return rc;
-      if ((rc = p3(f->vvpol, V.w3pol, 6, s * 3 + 1))) return rc;
-      if ((rc = p3(f->ww, V.w3pol, 6, s * 3 + 2))) return rc;
-    }
-    if ((rc = p3(f->rho, V.r2, 4, s * 2 + 0))) return rc;
-    if ((rc = p3(f->drhodz, V.r2, 4, s * 2 + 1))) return rc;
-    if ((rc = p2(f->ustar, V.sfc, 8, s * 4 + 0))) return rc;
-    if ((rc = p2(f->wstar, V.sfc, 8, s * 4 + 1))) return rc;
-    if ((rc = p2(f->oli, V.sfc, 8, s * 4 + 2))) return rc;
-    if ((rc = p2(f->hmix, V.sfc, 8, s * 4 + 3))) return rc;
-    if ((rc = diag_alloc()) || (rc = diag2_from_host(diag_tropo[s], f->tropopause, DG_TROPO + s))) return rc;   // partoutput interpolates it in time
-    if (slot == 1) {   // literal time index 1 uses: advance.f90:253, get_settling.f90:83-84
-      if ((rc = p2(f->tropopause, V.tropo, 1, 0))) return rc;
-      if (V.rhott) {
-        if ((rc = p3(f->rho, V.rhott, 2, 0))) return rc;
-        if ((rc = p3(f->tt, V.rhott, 2, 1))) return rc;
-      }
-    }
-    if (V.vdep) {
-      const size_t plane = (size_t)cfg.nxmax * cfg.nymax * cfg.host_real_bytes;
-      for (int ks = 0; ks < cfg.nspec; ks++)
-        if ((rc = p2((const char *)f->vdep + plane * ks, V.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
-    }
-    int tot = cfg.nx * cfg.ny;
-    k_hcell<R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>(V.sfc, (R *)V.hcell, cfg.nx, cfg.ny);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    slot_loaded[s] = true;
-    return 0;
+    return upload_wind(0, slot, f);
+  }
+  int upload_nest_fields(int nest, int slot, const fpx_fields *f) override {
+    if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "upload_nest_fields: nest out of range (fpx_nests_init first)");
+    if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_nest_fields: slot must be 1 or 2");
+    if (!f || !f->uu || !f->vv || !f->ww || !f->rho || !f->drhodz || !f->hmix || !f->ustar || !f->wstar || !f->oli || !f->tropopause)
+      return fail(FPX_ERR_ARG, "upload_nest_fields: uun, vvn, wwn, rhon, drhodzn, hmixn, ustarn, wstarn, olin, tropopausen are required");
+    if (cfg.drydep && !f->vdep) return fail(FPX_ERR_ARG, "upload_nest_fields: vdepn required with DRYDEP");
+    return upload_wind(nest, slot, f);
   }
 
 
@@ -2504,8 +2541,8 @@ struct Engine : EngineBase {
     // algorithm on the nest's arrays -- no height initialisation, no polar caps, the nest's own dyn/ylat0n in cosf and
     // the mother's dxconst, dyconst times xresoln, yresoln in the slope term, :346,384-385)
     const int nz = cfg.nz;
-    const int gnx = nest ? h_nest[nest - 1].nx : cfg.nx, gny = nest ? h_nest[nest - 1].ny : cfg.ny;
-    const int gnxmax = nest ? nest_nxmaxn : cfg.nxmax, gnymax = nest ? nest_nymaxn : cfg.nymax;
+    const HostGrid HG = host_grid(nest);
+    const int gnx = HG.nx, gny = HG.ny, gnxmax = HG.nxmax, gnymax = HG.nymax;
     void **vt_dev = vt_sets[nest];
     bool &vt_ready = vt_set_ready[nest];
     const size_t n2 = (size_t)gnxmax * gnymax, n3 = n2 * nz;
@@ -2614,37 +2651,20 @@ struct Engine : EngineBase {
       HIPCHK(hipGetLastError());
       return 0;
     };
-    const R *t_w3 = nest ? h_nest[nest - 1].w3 : V.w3, *t_r2 = nest ? h_nest[nest - 1].r2 : V.r2;
-    const R *t_sfc = nest ? h_nest[nest - 1].sfc : V.sfc, *t_tropo = nest ? h_nest[nest - 1].tropo : V.tropo;
-    const R *t_vdep = nest ? h_nest[nest - 1].vdep : V.vdep, *t_hcell = nest ? h_nest[nest - 1].hcell : V.hcell;
-    if ((rc = pk(D(UU), t_w3, 6, s * 3 + 0)) || (rc = pk(D(VV), t_w3, 6, s * 3 + 1)) || (rc = pk(D(WW), t_w3, 6, s * 3 + 2))) return rc;
-    if (!nest && V.w3pol)
-      if ((rc = pk(D(UPOL), V.w3pol, 6, s * 3 + 0)) || (rc = pk(D(VPOL), V.w3pol, 6, s * 3 + 1)) || (rc = pk(D(WW), V.w3pol, 6, s * 3 + 2))) return rc;
-    if ((rc = pk(D(RHO), t_r2, 4, s * 2 + 0)) || (rc = pk(D(DRHO), t_r2, 4, s * 2 + 1))) return rc;
-    if (!nest && slot == 1 && V.rhott)
-      if ((rc = pk(D(RHO), V.rhott, 2, 0)) || (rc = pk(D(TT), V.rhott, 2, 1))) return rc;
+    const WindDst T = wind_dst(nest);
+    if ((rc = pk(D(UU), T.w3, 6, s * 3 + 0)) || (rc = pk(D(VV), T.w3, 6, s * 3 + 1)) || (rc = pk(D(WW), T.w3, 6, s * 3 + 2))) return rc;
+    if (!nest && T.w3pol)
+      if ((rc = pk(D(UPOL), T.w3pol, 6, s * 3 + 0)) || (rc = pk(D(VPOL), T.w3pol, 6, s * 3 + 1)) || (rc = pk(D(WW), T.w3pol, 6, s * 3 + 2))) return rc;
+    if ((rc = pk(D(RHO), T.r2, 4, s * 2 + 0)) || (rc = pk(D(DRHO), T.r2, 4, s * 2 + 1))) return rc;
+    if (!nest && slot == 1 && T.rhott)
+      if ((rc = pk(D(RHO), T.rhott, 2, 0)) || (rc = pk(D(TT), T.rhott, 2, 1))) return rc;
     if (!nest && wet_on && Wp.ttw) { if ((rc = pk(D(TT), Wp.ttw, 2, s))) return rc; }
-    // the 2-D fields calcpar / calcpar_nests leave on the host
-    g_nx = gnx; g_ny = gny; g_nxmax = gnxmax; g_nymax = gnymax;
-    rc = 0;
-    if (sfc) do {
-      if ((rc = p2(sfc->ustar, t_sfc, 8, s * 4 + 0)) || (rc = p2(sfc->wstar, t_sfc, 8, s * 4 + 1)) ||
-          (rc = p2(sfc->oli, t_sfc, 8, s * 4 + 2)) || (rc = p2(sfc->hmix, t_sfc, 8, s * 4 + 3))) break;
-      if (slot == 1 && (rc = p2(sfc->tropopause, t_tropo, 1, 0))) break;
-      if (t_vdep) {
-        const size_t plane = n2 * cfg.host_real_bytes;
-        for (int ks = 0; ks < cfg.nspec && !rc; ks++) rc = p2((const char *)sfc->vdep + plane * ks, t_vdep, 2 * cfg.nspec, s * cfg.nspec + ks);
-      }
-    } while (0);
-    g_nx = cfg.nx; g_ny = cfg.ny; g_nxmax = cfg.nxmax; g_nymax = cfg.nymax;
-    if (rc) return rc;
-    if (!nest) {
+    if (sfc && (rc = upload_wind2(nest, slot, sfc))) return rc;
+    if (!nest) {   // pv, qv, tt of this slot stay on the device for partoutput
       if ((rc = diag_alloc())) return rc;
-      if (sfc && (rc = diag2_from_host(diag_tropo[s], sfc->tropopause, DG_TROPO + s))) return rc;
-      // pv, qv, tt of this slot stay on the device for partoutput
       if ((rc = diag3(D(PV), true, 0, s)) || (rc = diag3(D(QV), true, 1, s)) || (rc = diag3(D(TT), true, 2, s))) return rc;
     }
-    if (sfc) k_hcell<R><<<(gnx * gny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(t_sfc, (R *)t_hcell, gnx, gny);
+    if (sfc) k_hcell<R><<<(gnx * gny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(T.sfc, (R *)T.hcell, gnx, gny);
     HIPCHK(hipGetLastError());
     if (out) {   // z-level arrays the host still wants (partoutput, convection, cloud diagnostics ...)
       void *dst[10] = {out->uu, out->vv, out->ww, out->tt, out->qv, out->pv, out->rho, out->drhodz, out->uupol, out->vvpol};
@@ -2717,7 +2737,7 @@ struct Engine : EngineBase {
     if (V.vdep) {
       const size_t plane = n2 * cfg.host_real_bytes;
       for (int ks = 0; ks < cfg.nspec; ks++)
-        if ((rc = p2((const char *)c->vdep + plane * ks, V.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
+        if ((rc = p2(host_grid(0), (const char *)c->vdep + plane * ks, V.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
     }
     k_hcell<R><<<(cfg.nx * cfg.ny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(V.sfc, (R *)V.hcell, cfg.nx, cfg.ny);
     HIPCHK(hipGetLastError());
@@ -2800,56 +2820,30 @@ struct Engine : EngineBase {
     return 0;
   }
   // one 3-D field in the host's layout (host memory, or device memory when `on_device`) -> component c of slot s of d3
-  template <typename H>
-  int diag3_pack(const void *src, bool on_device, int c, int s) {
-    const size_t n = (size_t)cfg.nxmax * cfg.nymax * cfg.nz;
-    const H *in = (const H *)src;
-    if (!on_device) {
-      int rc = ensure_staging(n * sizeof(H));
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(staging, src, n * sizeof(H), hipMemcpyHostToDevice, stream));
-      in = (const H *)staging;
-    }
-    dim3 grid((cfg.nx + 31) / 32, (cfg.nz + 31) / 32, cfg.ny), block(32, 8);
-    k_pack3<H, H><<<grid, block, 0, stream>>>(in, (H *)diag_d3, cfg.nx, cfg.ny, cfg.nz, cfg.nxmax, cfg.nymax, 6, s * 3 + c);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    diag_have[DG_PV + 2 * c + s] = true;
-    return 0;
-  }
   int diag3(const void *src, bool on_device, int c, int s) {
-    return cfg.host_real_bytes == 4 ? diag3_pack<float>(src, on_device, c, s) : diag3_pack<double>(src, on_device, c, s);
+    const int rc = cfg.host_real_bytes == 4 ? pack3<float>(host_grid(0), src, (float *)diag_d3, 6, s * 3 + c, on_device)
+                                            : pack3<double>(host_grid(0), src, (double *)diag_d3, 6, s * 3 + c, on_device);
+    if (!rc) diag_have[DG_PV + 2 * c + s] = true;
+    return rc;
   }
   // oron and ttn of a nested wind field for releaseparticles (:216-273): compact copies in the host's real kind
   void *rel_nest_oro[kMaxNests] = {}, *rel_nest_tt2[kMaxNests] = {};
-  template <typename H>
-  int upload_diag_nest_fields_t(int nest, int slot, const fpx_diag_fields *f) {
-    const int l = nest - 1, nxn = h_nest[l].nx, nyn = h_nest[l].ny;
-    const size_t n2 = (size_t)nxn * nyn, n2max = (size_t)nest_nxmaxn * nest_nymaxn;
-    int rc;
-    if (f->oro) {
-      if (!rel_nest_oro[l]) { H *q = nullptr; if ((rc = dalloc(&q, n2))) return rc; rel_nest_oro[l] = q; }
-      if ((rc = ensure_staging(n2max * sizeof(H)))) return rc;
-      HIPCHK(hipMemcpyAsync(staging, f->oro, n2max * sizeof(H), hipMemcpyHostToDevice, stream));
-      k_conv_pack<H, H><<<(int)((n2 + kBlock - 1) / kBlock), kBlock, 0, stream>>>((const H *)staging, (H *)rel_nest_oro[l], nxn, nyn, 1, nest_nxmaxn, nest_nymaxn);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(stream));
-    }
-    if (slot == 2 && f->tt) {
-      const size_t n3 = n2 * cfg.nz;
-      if (!rel_nest_tt2[l]) { H *q = nullptr; if ((rc = dalloc(&q, n3))) return rc; rel_nest_tt2[l] = q; }
-      if ((rc = ensure_staging(n2max * cfg.nz * sizeof(H)))) return rc;
-      HIPCHK(hipMemcpyAsync(staging, f->tt, n2max * cfg.nz * sizeof(H), hipMemcpyHostToDevice, stream));
-      k_conv_pack<H, H><<<(int)((n3 + kBlock - 1) / kBlock), kBlock, 0, stream>>>((const H *)staging, (H *)rel_nest_tt2[l], nxn, nyn, cfg.nz, nest_nxmaxn, nest_nymaxn);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(stream));
-    }
-    return 0;
-  }
   int upload_diag_nest_fields(int nest, int slot, const fpx_diag_fields *f) override {
     if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "upload_diag_nest_fields: nest out of range (fpx_nests_init first)");
     if (!f || slot < 0 || slot > 2) return fail(FPX_ERR_ARG, "upload_diag_nest_fields: slot 0 (oron only), 1 or 2");
-    return cfg.host_real_bytes == 4 ? upload_diag_nest_fields_t<float>(nest, slot, f) : upload_diag_nest_fields_t<double>(nest, slot, f);
+    const HostGrid G = host_grid(nest);
+    const size_t n2 = (size_t)G.nx * G.ny * cfg.host_real_bytes;
+    const int l = nest - 1;
+    int rc;
+    if (f->oro) {
+      if (!rel_nest_oro[l]) { char *q = nullptr; if ((rc = dalloc(&q, n2))) return rc; rel_nest_oro[l] = q; }
+      if ((rc = compact(G, f->oro, rel_nest_oro[l], 1, 1))) return rc;
+    }
+    if (slot == 2 && f->tt) {
+      if (!rel_nest_tt2[l]) { char *q = nullptr; if ((rc = dalloc(&q, n2 * cfg.nz))) return rc; rel_nest_tt2[l] = q; }
+      if ((rc = compact(G, f->tt, rel_nest_tt2[l], cfg.nz, cfg.nz))) return rc;
+    }
+    return 0;
   }
 
   int upload_diag_fields(int slot, const fpx_diag_fields *f) override {
@@ -3797,13 +3791,26 @@ struct Engine : EngineBase {
   // ---- convective mixing -------------------------------------------------------------------------
   bool conv_on = false;
   int conv_nuvz = 0, conv_nconvlev = 0;
-  void *conv_fld[5][2] = {};                 // ps, tt2, td2, tth, qvh of the two slots, compact, host real kind
-  bool conv_slot[2] = {false, false};
+  // per wind-field grid (0: the mother grid, l: nested grid l; a nest's arrays are allocated with its first upload)
+  void *conv_fld[1 + kMaxNests][5][2] = {};  // ps, tt2, td2, tth, qvh of the two slots, compact [ny][nx], host real kind
+  bool conv_slot[1 + kMaxNests][2] = {};
+  void *conv_cb[1 + kMaxNests] = {};         // cbaseflux [ny][nx], cbasefluxn(:,:,l)
   void *conv_tab[4] = {};                    // akz, bkz, akm, bkm
-  void *conv_cb = nullptr;                   // cbaseflux [ny][nx]
-  void *conv_fld_n[kMaxNests][5][2] = {};    // the same five arrays of every nested wind field, compact [nyn][nxn]
-  bool conv_slot_n[kMaxNests][2] = {};
-  void *conv_cb_n[kMaxNests] = {};           // cbasefluxn(:,:,l)
+  size_t conv_cb_bytes(int g) const { const HostGrid G = host_grid(g); return (size_t)G.nx * G.ny * cfg.host_real_bytes; }
+  int conv_alloc(int g) {
+    const size_t n2 = conv_cb_bytes(g);
+    unsigned char *q = nullptr;
+    int rc;
+    for (int f = 0; f < 5; f++)
+      for (int sl = 0; sl < 2; sl++) {
+        if ((rc = dalloc(&q, f < 3 ? n2 : n2 * conv_nuvz))) return rc;
+        conv_fld[g][f][sl] = q;
+      }
+    if ((rc = dalloc(&q, n2))) return rc;
+    HIPCHK(hipMemsetAsync(q, 0, n2, stream));
+    conv_cb[g] = q;
+    return 0;
+  }
   size_t conv_ncol_alloc = 0;                // columns (all domains) the per-column arrays are sized for
   int *conv_pcol = nullptr, *conv_act = nullptr, *conv_lconv = nullptr, *conv_ntop = nullptr, *conv_cflag = nullptr, *conv_ntop_raw = nullptr;
   int4 *conv_colslot = nullptr;
@@ -3821,7 +3828,7 @@ struct Engine : EngineBase {
     if (c->nuvz < 4 || c->nconvlev < 2 || c->nconvlev > c->nuvz - 2) return fail(FPX_ERR_ARG, "conv_init: need 2 <= nconvlev <= nuvz - 2");
     if (!c->akz || !c->bkz || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "conv_init: akz, bkz, akm, bkm are required");
     if (conv_on) return fail(FPX_ERR_STATE, "conv_init: already initialised");
-    const size_t hb = (size_t)cfg.host_real_bytes, n2 = (size_t)cfg.nx * cfg.ny, n3 = n2 * c->nuvz;
+    const size_t hb = (size_t)cfg.host_real_bytes;
     int rc;
     const void *tabs[4] = {c->akz, c->bkz, c->akm, c->bkm};
     for (int i = 0; i < 4; i++) {
@@ -3830,18 +3837,8 @@ struct Engine : EngineBase {
       HIPCHK(hipMemcpyAsync(q, tabs[i], (size_t)c->nuvz * hb, hipMemcpyHostToDevice, stream));
       conv_tab[i] = q;
     }
-    for (int f = 0; f < 5; f++)
-      for (int sl = 0; sl < 2; sl++) {
-        unsigned char *q = nullptr;
-        if ((rc = dalloc(&q, (f < 3 ? n2 : n3) * hb))) return rc;
-        conv_fld[f][sl] = q;
-      }
-    {
-      unsigned char *q = nullptr;
-      if ((rc = dalloc(&q, n2 * hb))) return rc;
-      HIPCHK(hipMemsetAsync(q, 0, n2 * hb, stream));
-      conv_cb = q;
-    }
+    conv_nuvz = c->nuvz; conv_nconvlev = c->nconvlev;
+    if ((rc = conv_alloc(0))) return rc;
     if ((rc = dalloc(&conv_pcol, (size_t)P.cap)) || (rc = dalloc(&conv_draws, (size_t)P.cap))) return rc;
     if ((rc = dalloc(&conv_nmoved, (size_t)1))) return rc;
     {
@@ -3850,27 +3847,17 @@ struct Engine : EngineBase {
       conv_rn = q;
     }
     HIPCHK(hipStreamSynchronize(stream));
-    conv_nuvz = c->nuvz; conv_nconvlev = c->nconvlev;
     conv_on = true;
     return 0;
   }
 
-  template <typename H>
-  int upload_conv_fields_t(int slot, const fpx_conv_fields *f) {
-    const size_t n2max = (size_t)cfg.nxmax * cfg.nymax;
+  int upload_conv(int g, int slot, const fpx_conv_fields *f) {
+    int rc;
+    if (g > 0 && !conv_cb[g] && (rc = conv_alloc(g))) return rc;
     const void *src[5] = {f->ps, f->tt2, f->td2, f->tth, f->qvh};
-    for (int i = 0; i < 5; i++) {
-      const int nlev = i < 3 ? 1 : conv_nuvz;
-      const size_t bytes = n2max * (size_t)(i < 3 ? 1 : f->nuvzmax) * sizeof(H);
-      int rc = ensure_staging(bytes);
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(staging, src[i], bytes, hipMemcpyHostToDevice, stream));
-      const long long n = (long long)cfg.nx * cfg.ny * nlev;
-      k_conv_pack<H, H><<<(int)((n + kBlock - 1) / kBlock), kBlock, 0, stream>>>((const H *)staging, (H *)conv_fld[i][slot - 1], cfg.nx, cfg.ny, nlev, cfg.nxmax, cfg.nymax);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(stream));        // the staging buffer is reused by the next array
-    }
-    conv_slot[slot - 1] = true;
+    for (int i = 0; i < 5; i++)
+      if ((rc = compact(host_grid(g), src[i], conv_fld[g][i][slot - 1], i < 3 ? 1 : conv_nuvz, i < 3 ? 1 : f->nuvzmax))) return rc;
+    conv_slot[g][slot - 1] = true;
     return 0;
   }
   int upload_conv_fields(int slot, const fpx_conv_fields *f) override {
@@ -3878,40 +3865,7 @@ struct Engine : EngineBase {
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_conv_fields: slot must be 1 or 2");
     if (!f || !f->ps || !f->tt2 || !f->td2 || !f->tth || !f->qvh) return fail(FPX_ERR_ARG, "upload_conv_fields: ps, tt2, td2, tth, qvh are required");
     if (f->nuvzmax < conv_nuvz) return fail(FPX_ERR_ARG, "upload_conv_fields: nuvzmax < nuvz");
-    return cfg.host_real_bytes == 4 ? upload_conv_fields_t<float>(slot, f) : upload_conv_fields_t<double>(slot, f);
-  }
-
-  template <typename H>
-  int upload_conv_nest_fields_t(int nest, int slot, const fpx_conv_fields *f) {
-    const int l = nest - 1;
-    const int nxn = h_nest[l].nx, nyn = h_nest[l].ny;
-    const size_t n2 = (size_t)nxn * nyn, n2max = (size_t)nest_nxmaxn * nest_nymaxn;
-    int rc;
-    if (!conv_cb_n[l]) {
-      for (int i = 0; i < 5; i++)
-        for (int sl = 0; sl < 2; sl++) {
-          H *q = nullptr;
-          if ((rc = dalloc(&q, i < 3 ? n2 : n2 * conv_nuvz))) return rc;
-          conv_fld_n[l][i][sl] = q;
-        }
-      H *q = nullptr;
-      if ((rc = dalloc(&q, n2))) return rc;
-      HIPCHK(hipMemsetAsync(q, 0, n2 * sizeof(H), stream));
-      conv_cb_n[l] = q;
-    }
-    const void *src[5] = {f->ps, f->tt2, f->td2, f->tth, f->qvh};
-    for (int i = 0; i < 5; i++) {
-      const int nlev = i < 3 ? 1 : conv_nuvz;
-      const size_t bytes = n2max * (size_t)(i < 3 ? 1 : f->nuvzmax) * sizeof(H);
-      if ((rc = ensure_staging(bytes))) return rc;
-      HIPCHK(hipMemcpyAsync(staging, src[i], bytes, hipMemcpyHostToDevice, stream));
-      const long long n = (long long)n2 * nlev;
-      k_conv_pack<H, H><<<(int)((n + kBlock - 1) / kBlock), kBlock, 0, stream>>>((const H *)staging, (H *)conv_fld_n[l][i][slot - 1], nxn, nyn, nlev, nest_nxmaxn, nest_nymaxn);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(stream));
-    }
-    conv_slot_n[l][slot - 1] = true;
-    return 0;
+    return upload_conv(0, slot, f);
   }
   int upload_conv_nest_fields(int nest, int slot, const fpx_conv_fields *f) override {
     if (!conv_on) return fail(FPX_ERR_STATE, "upload_conv_nest_fields: fpx_conv_init first");
@@ -3919,27 +3873,21 @@ struct Engine : EngineBase {
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_conv_nest_fields: slot must be 1 or 2");
     if (!f || !f->ps || !f->tt2 || !f->td2 || !f->tth || !f->qvh) return fail(FPX_ERR_ARG, "upload_conv_nest_fields: ps, tt2, td2, tth, qvh are required");
     if (f->nuvzmax < conv_nuvz) return fail(FPX_ERR_ARG, "upload_conv_nest_fields: nuvzmax < nuvz");
-    return cfg.host_real_bytes == 4 ? upload_conv_nest_fields_t<float>(nest, slot, f) : upload_conv_nest_fields_t<double>(nest, slot, f);
+    return upload_conv(nest, slot, f);
   }
-  int cbaseflux_nest_io(int nest, void *host, bool set) override {
-    if (!conv_on) return fail(FPX_ERR_STATE, "cbaseflux_nest: fpx_conv_init first");
-    if (nest < 1 || nest > V.numbnests || !conv_cb_n[nest - 1]) return fail(FPX_ERR_STATE, "cbaseflux_nest: fpx_upload_conv_nest_fields of this nest first");
-    if (!host) return fail(FPX_ERR_ARG, "cbaseflux_nest: null");
-    const size_t bytes = (size_t)h_nest[nest - 1].nx * h_nest[nest - 1].ny * cfg.host_real_bytes;
-    if (set) HIPCHK(hipMemcpyAsync(conv_cb_n[nest - 1], host, bytes, hipMemcpyHostToDevice, stream));
-    else HIPCHK(hipMemcpyAsync(host, conv_cb_n[nest - 1], bytes, hipMemcpyDeviceToHost, stream));
+  // cbaseflux of grid g <-> host, for the entry point `who`
+  int cbaseflux_copy(int g, void *host, bool set, const char *who) {
+    if (!conv_on) return fail(FPX_ERR_STATE, std::string(who) + ": fpx_conv_init first");
+    if (g > 0 && (g > V.numbnests || !conv_cb[g])) return fail(FPX_ERR_STATE, std::string(who) + ": fpx_upload_conv_nest_fields of this nest first");
+    if (!host) return fail(FPX_ERR_ARG, std::string(who) + ": null");
+    if (set) HIPCHK(hipMemcpyAsync(conv_cb[g], host, conv_cb_bytes(g), hipMemcpyHostToDevice, stream));
+    else HIPCHK(hipMemcpyAsync(host, conv_cb[g], conv_cb_bytes(g), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     return 0;
   }
-
-  int cbaseflux_io(void *host, bool set) override {
-    if (!conv_on) return fail(FPX_ERR_STATE, "cbaseflux: fpx_conv_init first");
-    if (!host) return fail(FPX_ERR_ARG, "cbaseflux: null");
-    const size_t bytes = (size_t)cfg.nx * cfg.ny * cfg.host_real_bytes;
-    if (set) HIPCHK(hipMemcpyAsync(conv_cb, host, bytes, hipMemcpyHostToDevice, stream));
-    else HIPCHK(hipMemcpyAsync(host, conv_cb, bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    return 0;
+  int cbaseflux_io(void *host, bool set) override { return cbaseflux_copy(0, host, set, "cbaseflux"); }
+  int cbaseflux_nest_io(int nest, void *host, bool set) override {   // (an index below 1 is no nest: kMaxNests + 1 fails the same check)
+    return cbaseflux_copy(nest < 1 ? kMaxNests + 1 : nest, host, set, "cbaseflux_nest");
   }
 
   // sort2.f90 (the reference's quicksort with insertion sort below 7 elements; not stable): the order in which convmix
@@ -4037,13 +3985,13 @@ struct Engine : EngineBase {
     off[0] = 0;
     for (int d = 0; d < F.ndom; d++) {
       conv::Dom<H> &D = F.dom[d];
-      void *(*fld)[2] = d == 0 ? conv_fld : conv_fld_n[d - 1];
+      void *(*fld)[2] = conv_fld[d];
       for (int sl = 0; sl < 2; sl++) {
         D.ps[sl] = (const H *)fld[0][sl]; D.tt2[sl] = (const H *)fld[1][sl]; D.td2[sl] = (const H *)fld[2][sl];
         D.tth[sl] = (const H *)fld[3][sl]; D.qvh[sl] = (const H *)fld[4][sl];
       }
-      D.cb = (H *)(d == 0 ? conv_cb : conv_cb_n[d - 1]);
-      D.nx = d == 0 ? nx : h_nest[d - 1].nx; D.ny = d == 0 ? ny : h_nest[d - 1].ny;
+      D.cb = (H *)conv_cb[d];
+      D.nx = host_grid(d).nx; D.ny = host_grid(d).ny;
       D.off = off[d];
       off[d + 1] = off[d] + D.nx * D.ny;
       if (d > 0) {
@@ -4200,9 +4148,9 @@ struct Engine : EngineBase {
 
   int convmix(int itime, int64_t *nmoved) override {
     if (!conv_on) return fail(FPX_ERR_STATE, "convmix: fpx_conv_init first");
-    if (!conv_slot[0] || !conv_slot[1]) return fail(FPX_ERR_STATE, "convmix: fpx_upload_conv_fields of both slots first");
-    for (int l = 0; l < V.numbnests; l++)
-      if (!conv_slot_n[l][0] || !conv_slot_n[l][1]) return fail(FPX_ERR_STATE, "convmix: fpx_upload_conv_nest_fields of both slots of every nest first");
+    if (!conv_slot[0][0] || !conv_slot[0][1]) return fail(FPX_ERR_STATE, "convmix: fpx_upload_conv_fields of both slots first");
+    for (int l = 1; l <= V.numbnests; l++)
+      if (!conv_slot[l][0] || !conv_slot[l][1]) return fail(FPX_ERR_STATE, "convmix: fpx_upload_conv_nest_fields of both slots of every nest first");
     if (1 + V.numbnests > conv::kConvMaxDom) return fail(FPX_ERR_UNSUPPORTED, "convmix: too many nests");
     if (!window_set) return fail(FPX_ERR_STATE, "convmix: fpx_set_windtime first");
     if (!height_set) return fail(FPX_ERR_STATE, "convmix: set_height first");
@@ -4299,9 +4247,9 @@ struct Engine : EngineBase {
   struct CkptRng { HostRng<float> r4; HostRng<double> r8; Ran1 rel; };
   uint64_t conv_cbase_bytes() const {      // cbaseflux of the mother grid and of every nest that has convection fields
     if (!conv_on) return 0;
-    uint64_t b = (uint64_t)cfg.nx * cfg.ny * cfg.host_real_bytes;
-    for (int l = 0; l < V.numbnests; l++)
-      if (conv_cb_n[l]) b += (uint64_t)h_nest[l].nx * h_nest[l].ny * cfg.host_real_bytes;
+    uint64_t b = 0;
+    for (int g = 0; g <= V.numbnests; g++)
+      if (conv_cb[g]) b += conv_cb_bytes(g);
     return b;
   }
 
@@ -4341,11 +4289,9 @@ struct Engine : EngineBase {
     if (h.n_grid3n && ((rc = ckpt_put_plain(fh, Gp.griduncn, n_grid3n, buf)) || (rc = ckpt_put_plain(fh, Gp.drygriduncn, n_grid2n, buf)) ||
                        (rc = ckpt_put_plain(fh, Gp.wetgriduncn, n_grid2n, buf)))) return rc;
     if (h.n_receptor && (rc = ckpt_put_plain(fh, Gp.creceptor, (size_t)h.n_receptor, buf))) return rc;
-    if (h.cbase_bytes) {
-      if ((rc = ckpt_put_plain(fh, (const unsigned char *)conv_cb, (size_t)cfg.nx * cfg.ny * cfg.host_real_bytes, buf))) return rc;
-      for (int l = 0; l < V.numbnests; l++)
-        if (conv_cb_n[l] && (rc = ckpt_put_plain(fh, (const unsigned char *)conv_cb_n[l], (size_t)h_nest[l].nx * h_nest[l].ny * cfg.host_real_bytes, buf))) return rc;
-    }
+    if (h.cbase_bytes)
+      for (int g = 0; g <= V.numbnests; g++)
+        if (conv_cb[g] && (rc = ckpt_put_plain(fh, (const unsigned char *)conv_cb[g], conv_cb_bytes(g), buf))) return rc;
     closer.f = nullptr;
     if (fclose(fh) != 0) return fail(FPX_ERR_ARG, std::string("checkpoint_write: write error on ") + path);
     return 0;
@@ -4409,11 +4355,9 @@ struct Engine : EngineBase {
     if (g3n && ((rc = ckpt_get_plain(fh, Gp.griduncn, n_grid3n, buf)) || (rc = ckpt_get_plain(fh, Gp.drygriduncn, n_grid2n, buf)) ||
                 (rc = ckpt_get_plain(fh, Gp.wetgriduncn, n_grid2n, buf)))) return ckpt_invalidate(rc);
     if (nr && (rc = ckpt_get_plain(fh, Gp.creceptor, (size_t)nr, buf))) return ckpt_invalidate(rc);
-    if (h.cbase_bytes) {
-      if ((rc = ckpt_get_plain(fh, (unsigned char *)conv_cb, (size_t)cfg.nx * cfg.ny * cfg.host_real_bytes, buf))) return ckpt_invalidate(rc);
-      for (int l = 0; l < V.numbnests; l++)
-        if (conv_cb_n[l] && (rc = ckpt_get_plain(fh, (unsigned char *)conv_cb_n[l], (size_t)h_nest[l].nx * h_nest[l].ny * cfg.host_real_bytes, buf))) return ckpt_invalidate(rc);
-    }
+    if (h.cbase_bytes)
+      for (int g = 0; g <= V.numbnests; g++)
+        if (conv_cb[g] && (rc = ckpt_get_plain(fh, (unsigned char *)conv_cb[g], conv_cb_bytes(g), buf))) return ckpt_invalidate(rc);
     for (bool &v : red_valid) v = false;
     rng4 = rs.r4; rng8 = rs.r8; rel_ran1 = rs.rel;
     step_counter = h.step_counter;
@@ -5247,42 +5191,6 @@ struct Engine : EngineBase {
     V.numbnests = n->numbnests;
     return 0;
   }
-  int upload_nest_fields(int nest, int slot, const fpx_fields *f) override {
-    if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "upload_nest_fields: nest out of range (fpx_nests_init first)");
-    if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_nest_fields: slot must be 1 or 2");
-    if (!f || !f->uu || !f->vv || !f->ww || !f->rho || !f->drhodz || !f->hmix || !f->ustar || !f->wstar || !f->oli || !f->tropopause)
-      return fail(FPX_ERR_ARG, "upload_nest_fields: uun, vvn, wwn, rhon, drhodzn, hmixn, ustarn, wstarn, olin, tropopausen are required");
-    if (cfg.drydep && !f->vdep) return fail(FPX_ERR_ARG, "upload_nest_fields: vdepn required with DRYDEP");
-    const int l = nest - 1, s = slot - 1;
-    g_nx = h_nest[l].nx; g_ny = h_nest[l].ny; g_nxmax = nest_nxmaxn; g_nymax = nest_nymaxn;
-    int rc = 0;
-    do {
-      if ((rc = p3(f->uu, (R *)h_nest[l].w3, 6, s * 3 + 0))) break;
-      if ((rc = p3(f->vv, (R *)h_nest[l].w3, 6, s * 3 + 1))) break;
-      if ((rc = p3(f->ww, (R *)h_nest[l].w3, 6, s * 3 + 2))) break;
-      if ((rc = p3(f->rho, (R *)h_nest[l].r2, 4, s * 2 + 0))) break;
-      if ((rc = p3(f->drhodz, (R *)h_nest[l].r2, 4, s * 2 + 1))) break;
-      if ((rc = p2(f->ustar, (R *)h_nest[l].sfc, 8, s * 4 + 0))) break;
-      if ((rc = p2(f->wstar, (R *)h_nest[l].sfc, 8, s * 4 + 1))) break;
-      if ((rc = p2(f->oli, (R *)h_nest[l].sfc, 8, s * 4 + 2))) break;
-      if ((rc = p2(f->hmix, (R *)h_nest[l].sfc, 8, s * 4 + 3))) break;
-      if (slot == 1 && (rc = p2(f->tropopause, (R *)h_nest[l].tropo, 1, 0))) break;   // tropopausen(nix,njy,1,1,ngrid), advance.f90:263
-      if ((R *)h_nest[l].vdep) {
-        const size_t plane = (size_t)nest_nxmaxn * nest_nymaxn * cfg.host_real_bytes;
-        for (int ks = 0; ks < cfg.nspec && !rc; ks++) rc = p2((const char *)f->vdep + plane * ks, (R *)h_nest[l].vdep, 2 * cfg.nspec, s * cfg.nspec + ks);
-      }
-    } while (0);
-    const int nxl = g_nx, nyl = g_ny;
-    g_nx = cfg.nx; g_ny = cfg.ny; g_nxmax = cfg.nxmax; g_nymax = cfg.nymax;
-    if (rc) return rc;
-    int tot = nxl * nyl;
-    k_hcell<R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>((R *)h_nest[l].sfc, (R *)h_nest[l].hcell, nxl, nyl);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    nest_loaded[l][s] = true;
-    return 0;
-  }
-
   // ---- wet deposition -----------------------------------------------------------
   int wet_init(const fpx_wet_config *w) override {
     if (!w || w->struct_bytes != (int32_t)sizeof(fpx_wet_config)) return fail(FPX_ERR_ARG, "wet_init: null or fpx_wet_config size mismatch (ABI)");
@@ -5310,76 +5218,51 @@ struct Engine : EngineBase {
     wet_on = true;
     return 0;
   }
+  // lsprec, convprec, tcc, ctwc, tt, clouds of one grid and time slot (a nest's: lsprecn ... with strides nxmaxn, nymaxn, nzmax)
+  int upload_wet(int g, int slot, const fpx_wet_fields *f, int readclouds_nest) {
+    const HostGrid G = host_grid(g);
+    const int s = slot - 1;
+    int rc;
+    if (g > 0) {   // a nest's packs are allocated with its first upload
+      WetNest<R> &W = h_wnest[g - 1];
+      if (!W.prec) {
+        const size_t ncol = (size_t)G.nx * G.ny;
+        R *p; signed char *q;
+        if ((rc = dalloc(&p, ncol * 6))) return rc; W.prec = p;
+        if ((rc = dalloc(&p, ncol * 2))) return rc; W.ctwc = p;
+        if ((rc = dalloc(&p, ncol * cfg.nz * 2))) return rc; W.ttw = p;
+        if ((rc = dalloc(&q, ncol * cfg.nz * 2))) return rc; W.clouds = q;
+        if (!d_wnest) { if ((rc = dalloc(&d_wnest, (size_t)kMaxNests))) return rc; }
+      }
+      W.readclouds = readclouds_nest ? 1 : 0;
+    }
+    const WetNest<R> W = g > 0 ? h_wnest[g - 1] : WetNest<R>{Wp.prec, Wp.ctwc, Wp.ttw, Wp.clouds, Wp.readclouds};
+    if ((rc = p2(G, f->lsprec, W.prec, 6, s * 3 + 0)) || (rc = p2(G, f->convprec, W.prec, 6, s * 3 + 1)) || (rc = p2(G, f->tcc, W.prec, 6, s * 3 + 2))) return rc;
+    if (f->ctwc && (rc = p2(G, f->ctwc, W.ctwc, 2, s))) return rc;
+    if ((rc = p3(G, f->tt, W.ttw, 2, s))) return rc;
+    if ((rc = pack3<signed char>(G, f->clouds, (signed char *)W.clouds, 2, s))) return rc;   // integer(1) cloud classes: same x<->z transpose
+    if (g > 0) {   // the kernels find the nests' packs through the device table
+      HIPCHK(hipMemcpyAsync(d_wnest, h_wnest, sizeof(h_wnest), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      Wp.nest = d_wnest;
+      wet_nest_slot[g - 1][s] = true;
+    } else wet_slot[s] = true;
+    return 0;
+  }
   int upload_wet_fields(int slot, const fpx_wet_fields *f) override {
     if (!wet_on) return fail(FPX_ERR_STATE, "upload_wet_fields: fpx_wet_init first");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_wet_fields: slot must be 1 or 2");
     if (!f || !f->lsprec || !f->convprec || !f->tcc || !f->tt || !f->clouds) return fail(FPX_ERR_ARG, "upload_wet_fields: lsprec, convprec, tcc, tt, clouds are required");
     if (Wp.readclouds && !f->ctwc) return fail(FPX_ERR_ARG, "upload_wet_fields: ctwc required with readclouds");
-    const int s = slot - 1;
-    int rc;
-    if ((rc = p2(f->lsprec, Wp.prec, 6, s * 3 + 0))) return rc;
-    if ((rc = p2(f->convprec, Wp.prec, 6, s * 3 + 1))) return rc;
-    if ((rc = p2(f->tcc, Wp.prec, 6, s * 3 + 2))) return rc;
-    if (f->ctwc && (rc = p2(f->ctwc, Wp.ctwc, 2, s))) return rc;
-    if ((rc = p3(f->tt, Wp.ttw, 2, s))) return rc;
-    {   // integer(1) cloud classes: same x<->z transpose, element type int8
-      const size_t n = (size_t)cfg.nxmax * cfg.nymax * cfg.nz;
-      if ((rc = ensure_staging(n))) return rc;
-      HIPCHK(hipMemcpyAsync(staging, f->clouds, n, hipMemcpyHostToDevice, stream));
-      dim3 grid((cfg.nx + 31) / 32, (cfg.nz + 31) / 32, cfg.ny), block(32, 8);
-      k_pack3<signed char, signed char><<<grid, block, 0, stream>>>((const signed char *)staging, (signed char *)Wp.clouds, cfg.nx, cfg.ny, cfg.nz,
-                                                                    cfg.nxmax, cfg.nymax, 2, s);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(stream));
-    }
-    wet_slot[s] = true;
-    return 0;
+    return upload_wet(0, slot, f, 0);
   }
-  // lsprecn, convprecn, tccn, ctwcn, ttn, cloudsn of one nest and time slot (strides nxmaxn, nymaxn, nzmax)
   int upload_wet_nest_fields(int nest, int slot, const fpx_wet_fields *f, int readclouds_nest) override {
     if (!wet_on) return fail(FPX_ERR_STATE, "upload_wet_nest_fields: fpx_wet_init first");
     if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "upload_wet_nest_fields: nest out of range (fpx_nests_init first)");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_wet_nest_fields: slot must be 1 or 2");
     if (!f || !f->lsprec || !f->convprec || !f->tcc || !f->tt || !f->clouds) return fail(FPX_ERR_ARG, "upload_wet_nest_fields: lsprecn, convprecn, tccn, ttn, cloudsn are required");
     if (readclouds_nest && !f->ctwc) return fail(FPX_ERR_ARG, "upload_wet_nest_fields: ctwcn required with readclouds_nest");
-    const int l = nest - 1, s = slot - 1;
-    const int nxl = h_nest[l].nx, nyl = h_nest[l].ny;
-    int rc;
-    WetNest<R> &W = h_wnest[l];
-    if (!W.prec) {
-      const size_t ncol = (size_t)nxl * nyl;
-      R *p; signed char *q;
-      if ((rc = dalloc(&p, ncol * 6))) return rc; W.prec = p;
-      if ((rc = dalloc(&p, ncol * 2))) return rc; W.ctwc = p;
-      if ((rc = dalloc(&p, ncol * cfg.nz * 2))) return rc; W.ttw = p;
-      if ((rc = dalloc(&q, ncol * cfg.nz * 2))) return rc; W.clouds = q;
-      if (!d_wnest) { if ((rc = dalloc(&d_wnest, (size_t)kMaxNests))) return rc; }
-    }
-    W.readclouds = readclouds_nest ? 1 : 0;
-    g_nx = nxl; g_ny = nyl; g_nxmax = nest_nxmaxn; g_nymax = nest_nymaxn;
-    do {
-      if ((rc = p2(f->lsprec, (R *)W.prec, 6, s * 3 + 0))) break;
-      if ((rc = p2(f->convprec, (R *)W.prec, 6, s * 3 + 1))) break;
-      if ((rc = p2(f->tcc, (R *)W.prec, 6, s * 3 + 2))) break;
-      if (f->ctwc && (rc = p2(f->ctwc, (R *)W.ctwc, 2, s))) break;
-      if ((rc = p3(f->tt, (R *)W.ttw, 2, s))) break;
-    } while (0);
-    g_nx = cfg.nx; g_ny = cfg.ny; g_nxmax = cfg.nxmax; g_nymax = cfg.nymax;
-    if (rc) return rc;
-    {
-      const size_t n = (size_t)nest_nxmaxn * nest_nymaxn * cfg.nz;
-      if ((rc = ensure_staging(n))) return rc;
-      HIPCHK(hipMemcpyAsync(staging, f->clouds, n, hipMemcpyHostToDevice, stream));
-      dim3 grid((nxl + 31) / 32, (cfg.nz + 31) / 32, nyl), block(32, 8);
-      k_pack3<signed char, signed char><<<grid, block, 0, stream>>>((const signed char *)staging, (signed char *)W.clouds, nxl, nyl, cfg.nz,
-                                                                    nest_nxmaxn, nest_nymaxn, 2, s);
-      HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(d_wnest, h_wnest, sizeof(h_wnest), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    Wp.nest = d_wnest;
-    wet_nest_slot[l][s] = true;
-    return 0;
+    return upload_wet(nest, slot, f, readclouds_nest);
   }
   int wetdepo(int itime, int ltsample, int loutnext) override {
     if (!wet_on || !wet_slot[0] || !wet_slot[1]) return fail(FPX_ERR_STATE, "wetdepo: fpx_wet_init and both slots of fpx_upload_wet_fields first");

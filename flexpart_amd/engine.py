@@ -39,15 +39,18 @@ def release_tables(sc):
 class Engine:
     def __init__(self, sc, *, compute_real_bytes=8, host_real_bytes=8, rng_mode=RNG_TABLE_SEQ,
                  seed=0x5EED, max_particles=None, device=0, pad=(0, 0, 0), sort_interval=0,
-                 polemaps=None, particle_base=0, blend_mode=0, global_particles=0, pbl_slice_passes=0, options=None):
+                 polemaps=None, particle_base=0, blend_mode=0, global_particles=0, pbl_slice_passes=0, options=None,
+                 nest_pad=(0, 0)):
         """sc: scenario dict (flexpart_amd.synthetic).  pad: extra allocated (nxmax-nx,
-        nymax-ny, nzmax-nz) to exercise the reference's padded-array convention."""
+        nymax-ny, nzmax-nz) to exercise the reference's padded-array convention; nest_pad: the
+        same for the nested wind fields (nxmaxn-nxn, nymaxn-nyn)."""
         self.lib = _lib.load()
         self.sc = sc
         self.hreal = np.float32 if host_real_bytes == 4 else np.float64
         nx, ny, nz = (int(v) for v in sc["grid"])
         self.nx, self.ny, self.nz = nx, ny, nz
         self.nxmax, self.nymax, self.nzmax = nx + pad[0], ny + pad[1], nz + pad[2]
+        self.nest_pad = (int(nest_pad[0]), int(nest_pad[1]))
         dx, dy, xlon0, ylat0 = (float(v) for v in sc["geom"])
         xg, ng, sg = (int(v) for v in sc["globalflags"])
         nspec = int(sc["nspec"])
@@ -147,6 +150,14 @@ class Engine:
     def _host2(self, a, m):
         out = np.zeros((self.nymax, self.nxmax), self.hreal)
         out[: self.ny, : self.nx] = a[m]
+        return out
+
+    def _nest_host(self, a, dtype=None, nlev=None):
+        """compact [...][nyn][nxn] nest array -> the host's [...][nymaxn][nxmaxn] (nest_pad), the leading axis grown to nlev."""
+        a = np.asarray(a)
+        lead = a.shape[:-2] if nlev is None else (nlev,) + a.shape[1:-2]
+        out = np.zeros(lead + (a.shape[-2] + self.nest_pad[1], a.shape[-1] + self.nest_pad[0]), dtype or self.hreal)
+        out[tuple(slice(0, n) for n in a.shape)] = a
         return out
 
     def upload_fields_from_scenario(self, sc):
@@ -271,11 +282,10 @@ class Engine:
         keep = {}
         ml = FpxModelLevels()
         for k in ("uuh", "vvh", "pvh", "wwh", "tth", "qvh"):
-            keep[k] = np.ascontiguousarray(np.zeros((self.nzmax, nyn, nxn), rt))
-            keep[k][: self.nz] = n[k]
+            keep[k] = self._nest_host(n[k], nlev=self.nzmax)
             setattr(ml, k, keep[k].ctypes.data)
         for k in ("ps", "tt2", "td2"):
-            keep[k] = np.ascontiguousarray(np.asarray(n[k]).astype(rt))
+            keep[k] = self._nest_host(n[k])
             setattr(ml, k, keep[k].ctypes.data)
         for k in ("akz", "bkz", "aknew", "bknew"):
             keep[k] = np.ascontiguousarray(np.asarray(n[k]).astype(rt))
@@ -284,17 +294,17 @@ class Engine:
         ml.nest_dy, ml.nest_ylat0 = float(rt(n["geom"][1])), float(rt(n["geom"][3]))
         f = FpxFields()
         for k in ("hmix", "ustar", "wstar", "oli", "tropopause"):
-            keep["s" + k] = np.ascontiguousarray(np.asarray(sfc[k]).astype(rt))
+            keep["s" + k] = self._nest_host(sfc[k])
             setattr(f, k, keep["s" + k].ctypes.data)
         o = FpxFieldsOut()
         res = {}
         for k in want:
             if k in ("uupol", "vvpol"):
                 continue
-            res[k] = np.zeros((self.nzmax, nyn, nxn), rt)
+            res[k] = np.zeros((self.nzmax, nyn + self.nest_pad[1], nxn + self.nest_pad[0]), rt)
             setattr(o, k, res[k].ctypes.data)
         check(self.lib.fpx_verttransform_nest(self.h, 1, int(slot), C.byref(ml), C.byref(f), C.byref(o)), "fpx_verttransform_nest")
-        return {k: v[: self.nz].astype(np.float64) for k, v in res.items()}
+        return {k: v[: self.nz, :nyn, :nxn].astype(np.float64) for k, v in res.items()}
 
     def upload_diag_fields_from_scenario(self, sc):
         """oro and, for both slots, pv, qv, tt (compact arrays) -> fpx_upload_diag_fields."""
@@ -314,16 +324,14 @@ class Engine:
             check(self.lib.fpx_upload_diag_fields(self.h, m + 1, C.byref(f)), "fpx_upload_diag_fields")
 
     def upload_diag_nest_fields(self, nest, oron, ttn2=None):
-        """oron [nyn][nxn] and ttn of time slot 2 [nz][nyn][nxn] of a nested wind field (compact nests in this mirror)."""
+        """oron [nyn][nxn] and ttn of time slot 2 [nz][nyn][nxn] of a nested wind field (compact; padded here by nest_pad)."""
         from ._lib import FpxDiagFields
-        rt = self.hreal
         f = FpxDiagFields()
-        o = np.ascontiguousarray(np.asarray(oron).astype(rt))
+        o = self._nest_host(oron)
         f.oro = o.ctypes.data
         t = None
         if ttn2 is not None:
-            t = np.zeros((self.nzmax,) + tuple(np.asarray(ttn2).shape[1:]), rt)
-            t[: np.asarray(ttn2).shape[0]] = ttn2
+            t = self._nest_host(ttn2, nlev=self.nzmax)
             f.tt = t.ctypes.data
         check(self.lib.fpx_upload_diag_nest_fields(self.h, int(nest), 2 if ttn2 is not None else 0, C.byref(f)), "fpx_upload_diag_nest_fields")
 
@@ -383,23 +391,18 @@ class Engine:
         check(self.lib.fpx_upload_conv_fields(self.h, int(slot), C.byref(f)), "fpx_upload_conv_fields")
 
     def upload_conv_nest_fields(self, nest, slot, ps, tt2, td2, tth, qvh, nuvzmax=None):
-        """The same five arrays of nested wind field `nest` [nyn][nxn] / [nuvz][nyn][nxn] (this mirror declares compact nests:
-        nxmaxn = nxn, nymaxn = nyn)."""
+        """The same five arrays of nested wind field `nest` [nyn][nxn] / [nuvz][nyn][nxn] (compact; padded here by nest_pad)."""
         from ._lib import FpxConvFields
-        rt = self.hreal
-        nuvz, nyn, nxn = (int(v) for v in np.asarray(tth).shape)
+        nuvz = int(np.asarray(tth).shape[0])
         nuvzmax = nuvz + 1 if nuvzmax is None else int(nuvzmax)
         f = FpxConvFields()
         keep = {}
         for k, a in (("ps", ps), ("tt2", tt2), ("td2", td2)):
-            b = np.ascontiguousarray(np.asarray(a).astype(rt))
-            keep[k] = b
-            setattr(f, k, b.ctypes.data)
+            keep[k] = self._nest_host(a)
+            setattr(f, k, keep[k].ctypes.data)
         for k, a in (("tth", tth), ("qvh", qvh)):
-            b = np.zeros((nuvzmax, nyn, nxn), rt)
-            b[:nuvz] = a
-            keep[k] = b
-            setattr(f, k, b.ctypes.data)
+            keep[k] = self._nest_host(a, nlev=nuvzmax)
+            setattr(f, k, keep[k].ctypes.data)
         f.nuvzmax = nuvzmax
         check(self.lib.fpx_upload_conv_nest_fields(self.h, int(nest), int(slot), C.byref(f)), "fpx_upload_conv_nest_fields")
 
@@ -477,7 +480,7 @@ class Engine:
         n = FpxNests()
         n.struct_bytes = C.sizeof(FpxNests)
         n.numbnests = 1
-        n.nxmaxn, n.nymaxn = nxn, nyn
+        n.nxmaxn, n.nymaxn = nxn + self.nest_pad[0], nyn + self.nest_pad[1]
         n.nxn[0], n.nyn[0] = nxn, nyn
         xaux2 = xlon0n + rt(nxn - 1) * dxn
         yaux2 = ylat0n + rt(nyn - 1) * dyn
@@ -487,19 +490,18 @@ class Engine:
         check(self.lib.fpx_nests_init(self.h, C.byref(n)), "fpx_nests_init")
 
     def _upload_nest_slot(self, sc, m):
-        rt = self.hreal
         if True:
             keep = {}
             f = FpxFields()
             for k, kn in (("uu", "uun"), ("vv", "vvn"), ("ww", "wwn"), ("rho", "rhon"), ("drhodz", "drhodzn")):
-                keep[k] = np.ascontiguousarray(np.asarray(sc[kn])[m].astype(rt))
+                keep[k] = self._nest_host(np.asarray(sc[kn])[m])
                 setattr(f, k, keep[k].ctypes.data)
             for k, kn in (("hmix", "hmixn"), ("ustar", "ustarn"), ("wstar", "wstarn"), ("oli", "olin"),
                           ("tropopause", "tropopausen")):
-                keep[k] = np.ascontiguousarray(np.asarray(sc[kn])[m].astype(rt))
+                keep[k] = self._nest_host(np.asarray(sc[kn])[m])
                 setattr(f, k, keep[k].ctypes.data)
             if "vdepn" in sc:
-                keep["vdep"] = np.ascontiguousarray(np.asarray(sc["vdepn"])[m].astype(rt))
+                keep["vdep"] = self._nest_host(np.asarray(sc["vdepn"])[m])
                 f.vdep = keep["vdep"].ctypes.data
             check(self.lib.fpx_upload_nest_fields(self.h, 1, m + 1, C.byref(f)), "fpx_upload_nest_fields")
 
@@ -708,22 +710,15 @@ class Engine:
             keep["cloudsh"] = ch
             f.cloudsh = ch.ctypes.data
             check(self.lib.fpx_upload_wet_fields(self.h, m + 1, C.byref(f)), "fpx_upload_wet_fields")
-        if "lsprecn" in sc:      # the nest's own fields (compact: nxmaxn = nxn, nymaxn = nyn as in upload_nests_from_scenario)
-            rt = self.hreal
+        if "lsprecn" in sc:      # the nest's own fields (nxmaxn, nymaxn as in init_nest)
             for m in (0, 1):
                 keep = {}
                 f = FpxWetFields()
                 for k, kn in (("lsprec", "lsprecn"), ("convprec", "convprecn"), ("tcc", "tccn"), ("tt", "ttn")):
-                    a = np.asarray(sc[kn])[m]
-                    if kn == "ttn" and self.nzmax != self.nz:
-                        b = np.zeros((self.nzmax,) + a.shape[1:]); b[: self.nz] = a; a = b
-                    keep[k] = np.ascontiguousarray(a.astype(rt))
+                    keep[k] = self._nest_host(np.asarray(sc[kn])[m], nlev=self.nzmax if kn == "ttn" else None)
                     setattr(f, k, keep[k].ctypes.data)
-                cn = np.asarray(sc["cloudsn"])[m]
-                c8 = np.zeros((self.nzmax,) + cn.shape[1:], np.int8)
-                c8[: self.nz] = cn
-                keep["clouds"] = c8
-                f.clouds = c8.ctypes.data
+                keep["clouds"] = self._nest_host(np.asarray(sc["cloudsn"])[m], np.int8, nlev=self.nzmax)
+                f.clouds = keep["clouds"].ctypes.data
                 check(self.lib.fpx_upload_wet_nest_fields(self.h, 1, m + 1, C.byref(f), 0), "fpx_upload_wet_nest_fields")
 
     def wetdepo(self, itime=None, ltsample=None, loutnext=None):

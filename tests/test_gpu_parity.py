@@ -495,6 +495,25 @@ def test_padded_host_arrays(built):
     assert_close(got[-1], want[-1], 1e-9, 1e-7)
 
 
+def test_padded_nest_host_arrays(built):
+    """nxmaxn/nymaxn strides of the nested wind and wet fields are honoured, beside a padded mother grid: the padded
+    run meets the oracle as the compact one does, and, padding never being read, equals it bit for bit."""
+    from test_oracle_cpu import golden_scenario
+    sc = golden_scenario("nest_wet")
+    compact, want = run_pair(sc, "r8")
+    padded, _ = run_pair(sc, "r8", pad=(3, 2, 5), nest_pad=(2, 3))
+    assert len(compact) == len(padded) == len(want)
+    for got in (compact, padded):
+        for g, w in zip(got, want):
+            assert_close(g, w, 1e-9, 1e-7)
+            scale = np.abs(w["xmass1"]).max()
+            assert np.abs(g["xmass1"] - w["xmass1"]).max() <= 1e-12 * scale
+    for c, p in zip(compact, padded):
+        assert set(c) == set(p)
+        for k in c:
+            assert np.array_equal(c[k], p[k], equal_nan=True), k
+
+
 def test_rng_table_is_bit_identical(built):
     from flexpart_amd.engine import Engine
     from oracle.oracle import Oracle
