@@ -2107,6 +2107,7 @@ struct Engine : EngineBase {
     int verbose = 0, pbl_blocks_per_cu = 0, prep_lds_pad = 0, permute = 0 /* 0 auto, 1 direct, 2 staged */, vt_unfused = 0;
     long conv_scratch_mb = 0;
     int conv_one_lane = 0, conv_no_walk = 0, conv_rows_plain = 0;
+    int pbl_grid_blocks = 0, finish_blocks = 0;   // tests: upper bounds on the grids of k_pbl_loop / k_pbl_finish (0 = none)
     int pbl_drain_lanes = -1;                     // -1: the engine's default (FPX_DRAIN_LANES)
     int prep_init_always = 0;                     // measurements: every step runs the instance of k_prep that can initialize() new particles
     int pbl_cost_buckets = FPX_COST_BUCKETS;      // -1: by the size of this rank's cloud
@@ -4546,6 +4547,7 @@ struct Engine : EngineBase {
       HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, loop_kernel(), kBlock, loop_smem_bytes()));
       if (opt.pbl_blocks_per_cu > 0) per_cu = std::min(per_cu, opt.pbl_blocks_per_cu);   // experiments: fewer resident waves
       pbl_grid = prop.multiProcessorCount * std::max(per_cu, 1);
+      if (opt.pbl_grid_blocks > 0) pbl_grid = std::min(pbl_grid, opt.pbl_grid_blocks);   // tests: a small cloud on few waves refills like a full-size one
       pbl_per_cu = std::max(per_cu, 1);
       if (opt.verbose) fprintf(stderr, "[fpx] Langevin kernel: %d blocks per CU by the occupancy query, %zu B of dynamic LDS, grid %d\n", per_cu, loop_smem_bytes(), pbl_grid);
     }
@@ -4593,7 +4595,9 @@ struct Engine : EngineBase {
       HIPCHK(rocprim::radix_sort_pairs(d_sel_tmp, need, d_pbl_flag, d_pbl_flag2, d_iota, d_pbl_list, (size_t)numpart, 0u, 6u, stream));
       k_list_counts<<<1, 64, 0, stream>>>(d_pbl_flag2, numpart, d_pbl_ctr, d_stats);
     }
-    const int fin_grid = std::min(nb, 8 * 256 * 4);
+    // (k_pbl_finish needs every lane of its waves in the dry-deposition scatter -- wave_kernel_add: whole blocks of kBlock, no early return)
+    int fin_grid = std::min(nb, 8 * 256 * 4);
+    if (opt.finish_blocks > 0) fin_grid = std::min(fin_grid, opt.finish_blocks);   // tests: several tiles / strides per wave
     HIPCHK(hipEventRecord(ev.e[1], stream));
     for (size_t j = 0; j < slice_caps.size(); j++) {
       // launch j works through the particles launch j-1 suspended (k_pbl_loop); a launch whose list is empty ends at once;
@@ -4664,6 +4668,8 @@ struct Engine : EngineBase {
     auto need_int = [&](long lo) -> bool { return is_int && iv >= lo; };
     if (n == "verbose") { if (!need_int(0)) goto bad; opt.verbose = (int)iv; return 0; }
     if (n == "pbl_blocks_per_cu") { if (!need_int(0)) goto bad; opt.pbl_blocks_per_cu = (int)iv; pbl_grid = 0; return 0; }
+    if (n == "pbl_grid_blocks") { if (!need_int(0)) goto bad; opt.pbl_grid_blocks = (int)iv; pbl_grid = 0; return 0; }
+    if (n == "finish_blocks") { if (!need_int(0)) goto bad; opt.finish_blocks = (int)iv; return 0; }
     if (n == "prep_lds_pad") { if (!need_int(0) || iv > 160 * 1024) goto bad; opt.prep_lds_pad = (int)iv; return 0; }
     if (n == "vt_unfused") { if (!need_int(0)) goto bad; opt.vt_unfused = iv != 0; return 0; }
     if (n == "conv_scratch_mb") { if (!need_int(0)) goto bad; opt.conv_scratch_mb = iv; return 0; }
@@ -4709,6 +4715,14 @@ struct Engine : EngineBase {
       else { const int d[] = {FPX_SLICE_SCHEDULE}; *value = (int64_t)(sizeof(d) / sizeof(d[0])); }
     } else if (n == "pbl_grid") *value = pbl_grid;
     else if (n == "pbl_blocks_per_cu") *value = pbl_per_cu;
+    else if (n == "pbl_list_length") {   // the four class counts k_list_counts left for the first launch of the last step
+      unsigned int hc[4] = {0u, 0u, 0u, 0u};
+      if (step_counter > 0) {
+        HIPCHK(hipMemcpyAsync(hc, d_pbl_ctr + kCtrBase, sizeof(hc), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+      }
+      *value = (int64_t)hc[0] + hc[1] + hc[2] + hc[3];
+    }
     else return fail(FPX_ERR_ARG, "fpx_get_info: unknown name: " + n);
     return 0;
   }
@@ -5050,6 +5064,7 @@ struct Engine : EngineBase {
     if (numpart == 0) return 0;
     const int nb = (int)((numpart + kBlock - 1) / kBlock);
     red_valid[RG_GRID] = red_valid[RG_GRIDN] = red_valid[RG_REC] = false;   // the partial sums move on: earlier reductions are stale
+    // (wave_kernel_add needs every lane of the wave: whole blocks of kBlock, no early return in the kernel)
     k_conccalc<R><<<nb, kBlock, 0, stream>>>(V, Gp, P, numpart, itime, (R)weight);
     HIPCHK(hipGetLastError());
     return 0;
@@ -5272,6 +5287,7 @@ struct Engine : EngineBase {
     if (numpart == 0) return 0;
     const int nb = (int)((numpart + kBlock - 1) / kBlock);
     red_valid[RG_WET] = red_valid[RG_WETN] = false;
+    // (wave_kernel_add needs every lane of the wave: whole blocks of kBlock, no early return in the kernel)
     k_wetdepo<R><<<nb, kBlock, 0, stream>>>(V, Gp, Wp, P, numpart, itime, ltsample, loutnext);
     HIPCHK(hipGetLastError());
     return 0;

@@ -656,7 +656,9 @@ int fpx_lane_stats(fpx_handle h, uint64_t *out, int32_t n, int32_t reset);
 
 /* Tuning and diagnostic knobs of one handle (none of them changes a result; measurements and A/B runs only -- the library
  * reads no environment variable).  Names: "verbose" (0|1: the engine reports its launch geometry on stderr),
- * "pbl_blocks_per_cu" (1..: fewer resident blocks of the Langevin kernel), "pbl_slices" (comma-separated pass budgets of the
+ * "pbl_blocks_per_cu" (1..: fewer resident blocks of the Langevin kernel), "pbl_grid_blocks" (upper bound on the blocks of
+ * its persistent grid, 0 = none; 1 works: no block waits for another), "finish_blocks" (the same bound for the grid of
+ * k_pbl_finish; with both a cloud of a few thousand particles runs the schedule of a full-size one), "pbl_slices" (comma-separated pass budgets of the
  * successive launches of the Langevin kernel, 0 = no budget, e.g. "48,96,0"; overrides fpx_config.pbl_slice_passes),
  * "prep_lds_pad" (bytes of unused dynamic LDS of k_prep: lowers its occupancy), "prep_init_always" (0|1: every step runs the
  * instance of k_prep that can initialize() new particles, as in a run with a continuous release), "pbl_drain_lanes", "pbl_cost_buckets", "permute" ("auto"|"direct"|"staged": the
@@ -667,8 +669,9 @@ int fpx_set_option(fpx_handle h, const char *name, const char *value);
 /* What the engine decided or did, by name: "time_blended_packs" (1 when the steps of this handle blend the wind packs in
  * time: fpx_config.blend_mode / global_particles), "blended_steps" (steps that did so far), "pbl_launches_per_step"
  * (launches of the Langevin kernel per step = time slices + 1), "pbl_grid" (its persistent grid, blocks; 0 before the
- * first step), "pbl_blocks_per_cu" (resident blocks of four waves per CU the grid was sized for).  Unknown names return
- * FPX_ERR_ARG. */
+ * first step; after "pbl_grid_blocks"), "pbl_blocks_per_cu" (resident blocks of four waves per CU the grid was sized for),
+ * "pbl_list_length" (boundary-layer particles in the work list of the last step: one synchronising copy, diagnostics and
+ * tests only).  Unknown names return FPX_ERR_ARG. */
 int fpx_get_info(fpx_handle h, const char *name, int64_t *value);
 
 #ifdef __cplusplus

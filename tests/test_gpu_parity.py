@@ -1187,7 +1187,7 @@ def test_options_and_info_are_checked(built):
         eng = Engine(sc, rng_mode=RNG_PHILOX)
         assert eng.info("time_blended_packs") == 0
         for name, value in (("no_such_option", "1"), ("pbl_slices", "4,x"), ("pbl_slices", "-3"), ("permute", "sideways"), ("pbl_drain_lanes", "65"),
-                            ("pbl_cost_buckets", "9"), ("verbose", "yes")):
+                            ("pbl_cost_buckets", "9"), ("verbose", "yes"), ("pbl_grid_blocks", "-1"), ("finish_blocks", "-1")):
             with pytest.raises(Exception, match="unknown option or malformed value"):
                 eng.set_option(name, value)
         with pytest.raises(Exception, match="unknown name"):
