@@ -837,12 +837,14 @@ FPX_DEV R tlw_unstable(const Turb<R> &T, R z, const MS &M) {   // hanna.f90:78-8
 }
 
 template <typename R, typename MS>
-FPX_DEV void sigw_unstable(Turb<R> &T, const MS &M) {   // hanna.f90:67-70 == hanna_short.f90:60-63
+FPX_DEV void sigw_unstable(Turb<R> &T, R ust2, R wst2, const MS &M) {   // hanna.f90:67-70 == hanna_short.f90:60-63; ust2 = ust*ust, wst2 = wst*wst
   R z23, zm13;
   zeta_powers(T.zeta, M, z23, zm13);
-  T.sigw = m_sqrtp(K(1.2) * (T.wst * T.wst) * (K(1.) - K(.9) * T.zeta) * z23 + (K(1.8) - K(1.4) * T.zeta) * (T.ust * T.ust)) + K(1.e-2);
-  T.dsigwdz = K(0.5) * m_rcp(T.sigw * T.h) * (K(-1.4) * (T.ust * T.ust) + (T.wst * T.wst) * (K(0.8) * zm13 - K(1.8) * z23));
+  T.sigw = m_sqrtp(K(1.2) * wst2 * (K(1.) - K(.9) * T.zeta) * z23 + (K(1.8) - K(1.4) * T.zeta) * ust2) + K(1.e-2);
+  T.dsigwdz = K(0.5) * m_rcp(T.sigw * T.h) * (K(-1.4) * ust2 + wst2 * (K(0.8) * zm13 - K(1.8) * z23));
 }
+template <typename R, typename MS>
+FPX_DEV void sigw_unstable(Turb<R> &T, const MS &M) { sigw_unstable(T, T.ust * T.ust, T.wst * T.wst, M); }
 
 template <typename R, typename MS = PlainMath>
 FPX_DEV void hanna(Turb<R> &T, R z, const MS &M = MS()) {   // hanna.f90:41-106
@@ -875,6 +877,82 @@ FPX_DEV void hanna(Turb<R> &T, R z, const MS &M = MS()) {   // hanna.f90:41-106
   }
   T.tlu = m_max(K(10.), T.tlu);
   T.tlv = m_max(K(10.), T.tlv);
+  T.tlw = m_max(K(30.), T.tlw);
+  if (T.dsigwdz == K(0.)) T.dsigwdz = K(1.e-10);
+}
+
+// What hanna(), hanna_short() and the prologue of a Langevin pass evaluate from h, ol, ust and wst alone.  A particle's
+// horizontal position is fixed while it is in the Langevin kernel, so these four are fixed for the whole step: k_prep takes
+// the invariants once per particle, with all lanes of the wave active, and the particle's hand-over record carries them.
+// Every expression is the one hanna(), hanna_short and the prologue of the pass evaluated per pass before: the bits are the same.
+enum { INV_REGIME = 3, INV_DEEP = 4 };   // StepInv::flags: regime 0 neutral / 1 unstable / 2 stable (hanna.f90:42,59,91); -h/ol > 5 (advance.f90:405)
+template <typename R>
+struct StepInv {
+  R ust;          // as hanna.f90:43 floors it (neutral regime)
+  R iaux;         // 1/ust (neutral), 1/ol (unstable), 0 (stable)
+  R sigu, itlu;   // unstable regime: sigu = sigv (hanna.f90:60-61), 1/tlu = 1/tlv after the floor of :102-103; 0 otherwise
+  int flags;
+};
+template <typename R, typename MS>
+FPX_DEV StepInv<R> step_invariants(R h, R ol, R ust, R wst, const MS &M) {
+  StepInv<R> I;
+  I.ust = ust; I.sigu = K(0.); I.itlu = K(0.);
+  if (h / m_abs(ol) < K(1.)) {
+    I.flags = 0;
+    I.ust = m_max(K(1.e-4), ust);
+    I.iaux = m_rcp(I.ust);
+  } else if (ol < K(0.)) {
+    I.flags = 1;
+    I.iaux = m_rcp(ol);
+    I.sigu = K(1.e-2) + ust * m_pow13(K(12) - K(0.5) * h * I.iaux, M);
+    I.itlu = m_rcp(m_max(K(10.), K(0.15) * h * m_rcp(I.sigu)));
+  } else {
+    I.flags = 2;
+    I.iaux = K(0.);
+  }
+  if (-h / ol > K(5)) I.flags |= INV_DEEP;
+  return I;
+}
+
+// hanna() of a Langevin pass: T.ust is the floored ust, the regime and the reciprocals come from the invariants.  In the
+// unstable regime sigu, sigv and 1/tlu = 1/tlv are the invariants themselves (T.tlu, T.tlv are not set: itlu, itlv are).
+// INV: StashInv, the Langevin kernel's view of the invariants in its stash (defined with the stash, below)
+template <typename R, typename INV, typename MS>
+FPX_DEV void hanna(Turb<R> &T, R z, const INV &I, const MS &M, R &itlu, R &itlv) {   // hanna.f90:41-106
+  const int regime = I.regime();
+  if (regime == 0) {
+    R corr = z * I.get_iaux();
+    T.sigu = K(1.e-2) + K(2.0) * T.ust * M.expt(K(-3.e-4) * corr);
+    T.sigw = K(1.3) * T.ust * M.expt(K(-2.e-4) * corr);
+    T.dsigwdz = K(-2.e-4) * T.sigw;
+    T.sigw = T.sigw + K(1.e-2);
+    T.sigv = T.sigw;
+    T.tlu = K(0.5) * z * m_rcp(T.sigw * (K(1.) + K(1.5e-3) * corr));
+    T.tlv = T.tlu;
+    T.tlw = T.tlu;
+  } else if (regime == 1) {
+    T.sigu = I.get_sigu();
+    T.sigv = T.sigu;
+    sigw_unstable(T, T.ust * T.ust, I.get_wst2(), M);
+    if (z < m_abs(T.ol)) T.tlw = K(0.1) * z * m_rcp(T.sigw * (K(0.55) - K(0.38) * m_abs(z * I.get_iaux())));   // tlw_unstable, 1/ol from the invariants
+    else if (T.zeta < K(0.1)) T.tlw = K(0.59) * z * m_rcp(T.sigw);
+    else T.tlw = K(0.15) * T.h * m_rcp(T.sigw) * (K(1.) - M.expt(K(-5) * T.zeta));
+  } else {
+    T.sigu = K(1.e-2) + K(2.) * T.ust * (K(1.) - T.zeta);
+    T.sigv = K(1.e-2) + K(1.3) * T.ust * (K(1.) - T.zeta);
+    T.sigw = T.sigv;
+    T.dsigwdz = K(-1.3) * T.ust * m_rcp(T.h);
+    T.tlu = K(0.15) * T.h * m_rcp(T.sigu) * m_sqrtp(T.zeta);
+    T.tlv = K(0.467) * T.tlu;
+    T.tlw = K(0.1) * T.h * m_rcp(T.sigw) * m_pow08(T.zeta);
+  }
+  if (regime == 1) {
+    itlu = I.get_itlu(); itlv = itlu;
+  } else {
+    T.tlu = m_max(K(10.), T.tlu);
+    T.tlv = m_max(K(10.), T.tlv);
+    itlu = m_rcp(T.tlu); itlv = m_rcp(T.tlv);
+  }
   T.tlw = m_max(K(30.), T.tlw);
   if (T.dsigwdz == K(0.)) T.dsigwdz = K(1.e-10);
 }
@@ -953,14 +1031,17 @@ enum StashSlot {
   S_DDX, S_DDY,                                                                 // position inside the cell (interpol_all.f90:57-58); p1..p4 follow from it
   S_DX, S_DY, S_DAW, S_DCW,                                                     // dxsave, dysave, dawsave, dcwsave
   S_UP, S_VP,                                                                   // turbulent velocities along/across wind
-  S_UST, S_WST, S_OL, S_TRANS,                                                  // hanna_mod ust, wst, ol; wst^3 * the transition of cbl.f90:79-81
+  S_UST, S_WST2, S_OL, S_TRANS,                                                 // hanna_mod ust (floored, hanna.f90:43), wst^2, ol; wst^3 * the transition of cbl.f90:79-81
+  S_IAUX, S_SIGU, S_ITLU,                                                       // the step's invariants (StepInv, StashInv): 1/ust or 1/ol; unstable regime: sigu = sigv, 1/tlu = 1/tlv
   S_RHOAUX,                                                                     // per-pass invariant of the fine loop: rhograd/rhoa
   S_NPASS,                                                                      // passes the lane has run for its particle in this launch (time slices, k_pbl_loop)
   S_COUNT_LEAN,                                                                 // the gas kernels (LEAN) stop here
   S_TDEP = S_COUNT_LEAN,                                                        // aerosol kernels: sum of |dt| over the passes that ended below 2*href (advance.f90:582-599)
   S_SETCELL,                                                                    // aerosol kernels: column (njy*nx + nix) of get_settling -- so that xt, yt need not stay in registers
   S_SET_NUM, S_SET_DQ6, S_SET_V0,                                               // ... and its species constants 4*ga*dquer/1.e6*density*cunningham (0: no settling), dquer/1.e6, vsetaver
-  S_COUNT_AERO64,                                                               // the fp64 aerosol kernels stop here (22 slots = 45 KB per block: three blocks per CU; with the five below it would be two)
+  // the fp64 aerosol kernels stop here: 25 slots = 50 KB per block + 8 nz + 768 B of tables, so three blocks fit a CU's
+  // 160 KB up to nz = 330 and the occupancy query gives two above that; with the five slots below it would be two at every nz
+  S_COUNT_AERO64,
   S_RT_TAG = S_COUNT_AERO64, S_RT_RHO1, S_RT_TT1, S_RT_RHO2, S_RT_TT2,          // f32 aerosol kernels: rho, tt of get_settling.f90:83-84 for the level pair S_RT_TAG (0: none) of the lane's column
   S_COUNT
 };
@@ -983,30 +1064,32 @@ struct Stash {
   FPX_DEV void add(int k, R v) const { p[k * kStashStride] = p[k * kStashStride] + v; }
 };
 
+// The step's invariants of a lane of the Langevin kernel live in three stash slots and no register.  The flags travel in the
+// signs: 1/ust > 0 is the neutral regime, 1/ol < 0 the unstable one, 0 the stable one (ust and ol finite), and the sign bit of
+// the 1/tlu slot says -h/ol > 5 (1/tlu itself is positive, or 0 outside the unstable regime).
+template <typename R>
+FPX_DEV R inv_pack_itlu(const StepInv<R> &I) { return m_flip(I.itlu, (I.flags & INV_DEEP) ? 0x80000000u : 0u); }
+FPX_DEV bool m_signbit(double x) { return __double2hiint(x) < 0; }
+FPX_DEV bool m_signbit(float x) { return (int)__float_as_uint(x) < 0; }
+template <typename R>
+struct StashInv {
+  const Stash<R> &S;
+  // (each use reads the stash again: nothing of this stays in a register between the uses)
+  FPX_DEV int regime() const { const R iaux = S.get(S_IAUX); return iaux > K(0.) ? 0 : iaux < K(0.) ? 1 : 2; }
+  FPX_DEV bool deep() const { return m_signbit(S.get(S_ITLU)); }
+  FPX_DEV R get_iaux() const { return S.get(S_IAUX); }
+  FPX_DEV R get_sigu() const { return S.get(S_SIGU); }
+  FPX_DEV R get_itlu() const { return m_abs(S.get(S_ITLU)); }
+  FPX_DEV R get_wst2() const { return S.get(S_WST2); }
+};
+
 // hanna_short runs once per fine sub-step with the same h, ol, ust: the stability regime and
-// the reciprocals of the step-invariant divisors are taken once per pass
+// the reciprocals of the step-invariant divisors come from the step's invariants
 template <typename R>
 struct HsInv {
   R ih, iaux;    // 1/h; 1/ust (neutral) or 1/ol (unstable)
   int regime;    // 0 neutral (hanna_short.f90:46-52), 1 unstable (:57-72), 2 stable (:77-81)
 };
-template <typename R>
-FPX_DEV HsInv<R> hanna_short_prepare(Turb<R> &T) {
-  HsInv<R> I;
-  I.ih = m_rcp(T.h);
-  if (T.h / m_abs(T.ol) < K(1.)) {
-    I.regime = 0;
-    T.ust = m_max(K(1.e-4), T.ust);
-    I.iaux = m_rcp(T.ust);
-  } else if (T.ol < K(0.)) {
-    I.regime = 1;
-    I.iaux = m_rcp(T.ol);
-  } else {
-    I.regime = 2;
-    I.iaux = K(0.);
-  }
-  return I;
-}
 
 // ST: where ust, wst, ol are read from (the LDS stash of the loop kernel)
 template <typename R, typename ST>
@@ -1023,8 +1106,8 @@ FPX_DEV void hanna_short(Turb<R> &T, R z, const HsInv<R> &I, const ST &S) {   //
   } else if (I.regime == 1) {
     R z23, zm13;
     zeta_powers(T.zeta, S, z23, zm13);
-    const R ust = S.get(S_UST), wst = S.get(S_WST);
-    const R ust2 = ust * ust, wst2 = wst * wst;
+    const R ust = S.get(S_UST);
+    const R ust2 = ust * ust, wst2 = S.get(S_WST2);
     T.sigw = m_sqrtp(K(1.2) * wst2 * (K(1.) - K(.9) * T.zeta) * z23 + (K(1.8) - K(1.4) * T.zeta) * ust2) + K(1.e-2);
     // tlw (hanna.f90:78-84) and dsigwdz share the reciprocal of sigw
     const bool low = z < m_abs(S.get(S_OL));
@@ -1093,12 +1176,12 @@ template <typename R, typename ST>
 FPX_DEV void cbl(const ST &S, int ldirect, R wp, R zp, R wt /* wst^3 * transition */, R ih /* 1/h */, R rhoaux /* rhograd/rhoa */, R sigmaw, R irw /* 1/sigmaw */, R dsigmawdz, R tlw,
                  R &ath, R &bth, int &flagrein) {
   const R usurad2 = K(0.7071067812), usurad2p = K(0.3989422804), C0 = K(3), costluar4 = K(0.66667), eps = K(0.000001);
-  const R timedir = (R)ldirect;
+  const unsigned int tdir = ldirect < 0 ? 0x80000000u : 0u;   // timedir = ldirect = +-1 as a sign mask: x * timedir = m_flip(x, tdir), exactly
   const R z = zp * ih;
   const R w2 = sigmaw * sigmaw;
   const R rtl = m_rsqrt(tlw);                        // tlw >= 30 (hanna_short.f90:91)
   const R alfa = (K(2.) / C0) * w2 * (rtl * rtl);
-  const R wold = timedir * wp;
+  const R wold = m_flip(wp, tdir);
   const R omz = K(1.) - z;
   const R omz05 = m_sqrtp(omz), omz15 = omz * omz05;
   const R w3 = (K(1.2) * z * omz15 + eps) * wt;
@@ -1169,7 +1252,7 @@ FPX_DEV void cbl(const ST &S, int ldirect, R wp, R zp, R wt /* wst^3 * transitio
   R erfa, erfb;
   m_erf_e2(aperfa, ea - ea * (da2 * cu), aperfb, eb - eb * (db2 * cu), erfa, erfb);
   const R Phi = K(0.5) * (Tb * erfb - Ta * erfa) + Ua * pa + Ub * pb;
-  const R Q = timedir * ((da * isa) * apa + (db * isb) * bpb);
+  const R Q = m_flip((da * isa) * apa + (db * isb) * bpb, tdir);
   ath = m_rcp(ptot) * (-(C0 / K(2.)) * alfa * Q + Phi);
   bth = (sigmaw * K(1.4142135623730951)) * rtl;     // sqrt(C0*alfa) = sigmaw*sqrt(2/tlw)
 }
@@ -2157,13 +2240,28 @@ FPX_DEV void fetch_level_pair(const View<R> &V, const Fld<R> &F, const TimeW<R> 
   }
 }
 
+// What a Langevin pass reads from the particle's hand-over record itself (PblRecord, fpx_engine.hip, which asserts the two
+// constants against its layout): wst, on the cold path of cbl() and in hanna1.  The asm keeps the address arithmetic where the
+// value is read -- hoisted out of the fine loop it would hold two registers through every sub-step.
+constexpr int kRecStride = 16, kRecWst = 9;   // values of R per record; index of wst in PblRecord::v
+template <typename R>
+struct RecCold {
+  const R *v0;         // PblRecord::v of slot 0
+  unsigned int slot;   // the particle's slot
+  FPX_DEV R wst() const {
+    unsigned int s = slot;
+    asm volatile("" : "+v"(s));
+    return v0[(size_t)s * kRecStride + kRecWst];
+  }
+};
+
 template <int T>
 FPX_DEV bool sw(int runtime) { return T < 0 ? runtime != 0 : T != 0; }
 
 template <typename R, bool DRYDEP, bool SETTLE, int TSW, int CBLF, typename RNG>
 FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R> &W, int itime, double xt, double yt,
                      R &zt, R &wp, int &ldt, short &icbt, LoopCtx<R> &A, const Stash<R> &S,
-                     int &indz_last, Stats *st) {
+                     int &indz_last, Stats *st, const RecCold<R> &RC) {
   const R eps = V.eps;
   const R eps2 = K(1.e-9);
   const R href = K(15.);            // par_mod.f90:76
@@ -2176,7 +2274,7 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
   // selects per fine sub-step it compiles to cost 1 % of the kernel; a run with turboff takes the general instance (loop_table)
   const bool turboff = TSW < 0 && V.turboff != 0;
   Turb<R> T;
-  T.ust = S.get(S_UST); T.wst = S.get(S_WST); T.ol = S.get(S_OL); T.h = h;
+  T.h = h;
   T.sigw = K(0.); T.dsigw2dz = K(0.); T.dsigwdz = K(0.);   // only read if hanna1 meets zeta >= 1 (see hanna1)
 
   if (V.method == 1) {
@@ -2215,8 +2313,14 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
     S.put(S_RHOAUX, rhograd * m_rcp(rhoa));
   }
 
-  if (turbswitch) hanna(T, zt, S); else hanna1(T, zt);
-  S.put(S_UST, T.ust);   // hanna may floor ust at 1.e-4 (hanna.f90:43) and the module variable keeps it
+  // the regime, the reciprocals of the step-invariant divisors and, in the unstable regime, sigu and 1/tlu: the step's invariants
+  const StashInv<R> SI{S};
+  // (read here and not at the head of the pass: the stash reads are volatile, and these would stay in registers across the gather)
+  T.ust = S.get(S_UST); T.ol = S.get(S_OL);   // ust as hanna.f90:43 floors it (step_invariants)
+  if (!turbswitch) T.wst = RC.wst();          // hanna1 alone reads wst itself: from the particle's record (the stash holds wst*wst for hanna_short)
+  R itlu, itlv;
+  if (turbswitch) hanna(T, zt, SI, S, itlu, itlv);
+  else { hanna1(T, zt); S.put(S_UST, T.ust); itlu = m_rcp(T.tlu); itlv = m_rcp(T.tlv); }   // (hanna1.f90:43 floors ust where hanna1 is neutral)
   T.isigw = m_rcp(T.sigw);
 
   // counter mode: a pass starts on a block boundary of the generator, so that all lanes of a wave
@@ -2226,7 +2330,7 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
   if (nrand + 1 > V.maxrand) nrand = 1;
   {
     const R g1 = G.at(nrand), g2 = G.at(nrand + 1);
-    const R dttlu = dt * m_rcp(T.tlu), dttlv = dt * m_rcp(T.tlv);
+    const R dttlu = dt * itlu, dttlv = dt * itlv;
     R up = S.get(S_UP), vp = S.get(S_VP);
     if (dttlu < K(.5)) {
       up = (K(1.) - dttlu) * up + g1 * T.sigu * m_sqrtp(K(2.) * dttlu);
@@ -2250,9 +2354,9 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
   if (nrand + V.ifine > V.maxrand) nrand = 1;
   const R dtf = dt * V.fine;
   const R dtftlw = dtf * m_rcp(T.tlw);
-  const bool cbl_on = cblflag && (-h / T.ol > K(5));
+  const bool cbl_on = cblflag && SI.deep();
   const R sqrt_dtf = m_sqrtp(dtf);
-  const HsInv<R> HI = hanna_short_prepare(T);
+  const HsInv<R> HI{m_rcp(h), SI.get_iaux(), SI.regime()};
 
   // vertical Langevin, ifine sub-steps, advance.f90:396-498
   FPX_LANES(st, 0);
@@ -2272,7 +2376,8 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
             wp = m_flip(wp + ath * dtf + bth * G.at(nrand) * sqrt_dtf, flip);
             delz = wp * dtf;
             if (__builtin_expect(flagrein == 1, 0)) {
-              re_initialize_particle(V.ldirect, G, zt, S.get(S_WST), h, T.sigw, old_wp_buf, nrand, S.get(S_OL));
+              const R wst = RC.wst();   // read on this path only
+              re_initialize_particle(V.ldirect, G, zt, wst, h, T.sigw, old_wp_buf, nrand, S.get(S_OL));
               wp = old_wp_buf;
               delz = wp * dtf;
               atomicAdd(&st->nan_count, 1ull);
@@ -2298,7 +2403,9 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
         }
       } else {
         FPX_LANES(st, 4);
-        R rw = S.expt(-dtftlw);
+        R xw = dtftlw;
+        asm volatile("" : "+v"(xw));   // as above: the range reduction of the exponential stays in this arm (ldt at its floor mintime only)
+        R rw = S.expt(-xw);
         wp = m_flip(rw * wp + G.at(nrand + i) * m_sqrtp(K(1.) - rw * rw) + T.tlw * (K(1.) - rw) * (T.dsigwdz + S.get(S_RHOAUX) * T.sigw), flip);
         delz = wp * T.sigw * dtf;
       }
@@ -2311,7 +2418,9 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
     if (turboff) { wp = K(0.); delz = K(0.); }   // advance.f90:464-470 (turboff; the random numbers stay drawn)
 
     // reflection at the ground / mixing height, advance.f90:476-491
-    if (__builtin_expect(m_abs(delz) > h, 0)) delz = m_fmod(delz, h);
+    // (the asm makes the divisor a value of this arm: the loop-invariant head of fmod -- a full division -- otherwise moves in
+    // front of the fine loop and runs in every pass for an arm that practically never does)
+    if (__builtin_expect(m_abs(delz) > h, 0)) { R hh = h; asm volatile("" : "+v"(hh)); delz = m_fmod(delz, hh); }
     {
       // branch-free (three short arms as divergent branches cost more in exec-mask and branch instructions than in work):
       // the same sums in the same order as the three arms of the reference

@@ -525,6 +525,7 @@ template <typename R>
 struct alignas(16 * sizeof(R)) PblRecord {
   // v[0..3]  = dxsave, dysave, dawsave, dcwsave                                  (CONTINUE, DONE, ESCAPED)
   // v[4..7]  = zt, up, vp, wp                                                    (CONTINUE, DONE, ESCAPED)
+  // v[0..2]  = the step's invariants 1/ust | 1/ol, sigu, 1/tlu as StashInv holds them  (FRESH; read by the one-launch kernel only)
   // v[8..10] = ust, wst, ol (interpol_all.f90:80-107; ust as hanna.f90:43 floored it)  (FRESH, CONTINUE)
   //          | interpol_mod u, v, w of the last pass                             (DONE, ESCAPED)
   // v[11]    = CBL transition (cbl.f90:79-81), v[12] = mixing height of the cell (advance.f90:236-262): written by k_prep only
@@ -533,6 +534,8 @@ struct alignas(16 * sizeof(R)) PblRecord {
   int i[3];
 };
 static_assert(sizeof(PblRecord<double>) == 128 && sizeof(PblRecord<float>) == 64, "one cache line / half a line per record");
+static_assert(sizeof(PblRecord<double>) == kRecStride * sizeof(double) && sizeof(PblRecord<float>) == kRecStride * sizeof(float) &&
+              offsetof(PblRecord<double>, v) == 0 && offsetof(PblRecord<float>, v) == 0 && kRecWst < 13, "RecCold (fpx_device.hpp) indexes the records by these");
 // state: bits 0-1, icbt = -1: bit 2, indz (<= 511): bits 3-11, ngrid + 2 (-2 .. kMaxNests): bits 12-14, |itimec - itime| (<= |lsynctime| <= 65535): bits 15-30
 __device__ __forceinline__ int pbl_pack(int state, int icbt, int indz, int ngrid, int elapsed) {
   return state | (icbt < 0 ? 4 : 0) | (indz << 3) | ((ngrid + 2) << 12) | (elapsed << 15);
@@ -599,19 +602,23 @@ __device__ __forceinline__ void prep_body(const View<R> &V, const GridP<R> &Gp, 
     // the lanes are convergent; the Langevin kernel then starts from five numbers per particle
     PblCtx<R> B;
     pbl_begin(V, ps.xt, ps.yt, W, A, B);
+    // ... and what the turbulence scheme derives from them and the mixing height alone: fixed for the whole step, taken here
+    // once instead of in each of the particle's 15 to 150 passes (step_invariants)
+    const StepInv<R> I = step_invariants(A.h, B.ol, B.ust, B.wst, PlainMath());
     {
       PblRecord<R> &r = Q.rec[s];
-      r.v[8] = B.ust; r.v[9] = B.wst; r.v[10] = B.ol; r.v[11] = B.transition;
+      r.v[8] = I.ust; r.v[kRecWst] = B.wst; r.v[10] = B.ol; r.v[11] = B.transition;
       r.v[12] = A.h;
+      r.v[0] = I.iaux; r.v[1] = I.sigu; r.v[2] = inv_pack_itlu(I);   // as the Langevin kernel's stash holds them (StashInv)
       r.i[0] = A.nrand; r.i[2] = pbl_pack(PBL_FRESH, 1, 0, A.ngrid, 0);
     }
     // Regime class of the particle's PBL passes (hanna.f90:42,59,91 and advance.f90:405-406).  The
     // work list is the slots stably sorted by this 3-bit key: class by class, each class in slot
     // (= cell) order, so the lanes of a wave run the same branch of the turbulence scheme.
     unsigned char cls;
-    if (V.cblflag == 1 && V.turbswitch && (-A.h / B.ol > (R)5)) cls = 1;      // skewed CBL scheme
-    else if (A.h / m_abs(B.ol) < (R)1) cls = 3;                               // neutral
-    else if (B.ol < (R)0) cls = 2;                                            // unstable, Gaussian: next to the CBL class, whose
+    if (V.cblflag == 1 && V.turbswitch && (I.flags & INV_DEEP)) cls = 1;      // skewed CBL scheme
+    else if ((I.flags & INV_REGIME) == 0) cls = 3;                            // neutral
+    else if ((I.flags & INV_REGIME) == 1) cls = 2;                                            // unstable, Gaussian: next to the CBL class, whose
                                                                               // hanna_short branch it shares (waves at a class boundary run both classes)
     else cls = 4;                                                             // stable
     // (measured and not kept: the reverse order -- 297.3 instead of 293.7 ms at 1e8, 47.9 instead of 42.2 ms at an eighth
@@ -1497,7 +1504,10 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
           const double l_xt = P.xt[s], l_yt = P.yt[s];
           const unsigned int l_pid = P.pid[s];
           const int r_nrand = rp->i[0], r_ldt = SUSP ? rp->i[1] : 0, r_pk = rp->i[2];
-          const R r_ust = rp->v[8], r_wst = rp->v[9], r_ol = rp->v[10], r_trans = rp->v[11], r_h = rp->v[12];
+          const R r_ust = rp->v[8], r_wst = rp->v[kRecWst], r_ol = rp->v[10], r_trans = rp->v[11], r_h = rp->v[12];
+          // the step's invariants as k_prep took them, same line as the above (a launch that may meet a suspended particle, whose
+          // v[0..7] are in use, takes them here instead: step_invariants below)
+          const R r_iaux = SUSP ? (R)0 : rp->v[0], r_sigu = SUSP ? (R)0 : rp->v[1], r_itlu = SUSP ? (R)0 : rp->v[2];
           // a fresh particle's state is in the particle arrays, a suspended one's in its record: both are requested
           // (one round trip either way; suspended particles are the few)
           R l_zt = P.zt[s], l_wp = P.wp[s], l_up = P.up[s], l_vp = P.vp[s];
@@ -1535,10 +1545,18 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
           S.put(S_DAW, resumed ? c_daw : (R)0); S.put(S_DCW, resumed ? c_dcw : (R)0);
           S.put(S_W, (R)0);
           S.put(S_UP, resumed ? c_up : l_up); S.put(S_VP, resumed ? c_vp : l_vp);
-          S.put(S_UST, r_ust); S.put(S_WST, r_wst); S.put(S_OL, r_ol);
+          S.put(S_WST2, r_wst * r_wst);
+          S.put(S_OL, r_ol);
           S.put(S_TRANS, (r_wst * r_wst * r_wst) * r_trans);   // (wst**3)*transition, cbl.f90:103-104
           if (SUSP) S.put(S_NPASS, (R)0);
           if (!LEAN && V.drydep) S.put(S_TDEP, resumed ? c_tdep : (R)0);
+          if (SUSP) {
+            __builtin_amdgcn_sched_barrier(0);   // last, with everything else of the refill stored: the helper's temporaries do not meet the loaded values
+            const StepInv<R> I = step_invariants(r_h, r_ol, r_ust, r_wst, S);
+            S.put(S_UST, I.ust); S.put(S_IAUX, I.iaux); S.put(S_SIGU, I.sigu); S.put(S_ITLU, inv_pack_itlu(I));
+          } else {
+            S.put(S_UST, r_ust); S.put(S_IAUX, r_iaux); S.put(S_SIGU, r_sigu); S.put(S_ITLU, r_itlu);
+          }
           have = true;
         }
         cur = min(cur + (unsigned int)__popcll(need), end);
@@ -1553,7 +1571,7 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
       Rng<R, RNGM> G;
       make_rng(V, pid, step, G);
       int indz = 1;
-      const int rc = pbl_pass<R, !LEAN, !LEAN, TSW, CBLF>(V, hgt, G, W, itime, xt, yt, zt, wp, ldt, icbt, A, S, indz, st);
+      const int rc = pbl_pass<R, !LEAN, !LEAN, TSW, CBLF>(V, hgt, G, W, itime, xt, yt, zt, wp, ldt, icbt, A, S, indz, st, RecCold<R>{Q.rec[0].v, s});
       R npass = (R)0;
       if (SUSP) { npass = S.get(S_NPASS) + (R)1; S.put(S_NPASS, npass); }
       if (rc != PBL_CONTINUE) {
@@ -1600,6 +1618,41 @@ __global__ void k_math_probe(int fn, const double *__restrict__ x, double *__res
     default: m_cuberoot_parts(v, c, ic2); r = ic2; break;
   }
   y[i] = r;
+}
+
+// diagnostics (fpx_hanna_probe): hanna() of a Langevin pass on plain arrays, ten values per point -- sigu, sigv, sigw, dsigwdz, 1/tlu,
+// 1/tlv, tlw, floored ust, regime, -h/ol > 5.  which = 0: the way the engine goes -- step_invariants() with the plain math as in
+// k_prep, packed as the record carries them, through stash slots and StashInv with the stash's LDS tables as in k_pbl_loop;
+// which = 1: hanna() as it stands.  One launch per form, so that the compiler cannot share a subexpression between them.
+__global__ void __launch_bounds__(kBlock) k_hanna_probe(int which, const double *__restrict__ in, double *__restrict__ out, long long n) {
+  __shared__ double slots[(S_ITLU + 1) * kStashStride];
+  __shared__ double lds_tab[kLdsTabDoubles];
+  for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double h = in[5 * i], ol = in[5 * i + 1], ust = in[5 * i + 2], wst = in[5 * i + 3], z = in[5 * i + 4];
+  double *o = out + 10 * i;
+  Turb<double> T;
+  T.ol = ol; T.h = h; T.zeta = z / h; T.sigw = 0.; T.dsigwdz = 0.;
+  if (which == 0) {
+    const Stash<double> S{(Stash<double>::lds_ptr)(slots + threadIdx.x), (lds_tab_ptr)lds_tab};
+    const StepInv<double> I = step_invariants(h, ol, ust, wst, PlainMath());
+    S.put(S_UST, I.ust); S.put(S_OL, ol); S.put(S_WST2, wst * wst);
+    S.put(S_IAUX, I.iaux); S.put(S_SIGU, I.sigu); S.put(S_ITLU, inv_pack_itlu(I));
+    const StashInv<double> SI{S};
+    T.ust = S.get(S_UST);
+    double itlu, itlv;
+    hanna(T, z, SI, S, itlu, itlv);
+    o[0] = T.sigu; o[1] = T.sigv; o[2] = T.sigw; o[3] = T.dsigwdz; o[4] = itlu; o[5] = itlv; o[6] = T.tlw;
+    o[7] = T.ust; o[8] = (double)SI.regime(); o[9] = SI.deep() ? 1. : 0.;
+  } else {
+    T.ust = ust; T.wst = wst;
+    const bool deep = -h / T.ol > 5.;
+    hanna(T, z, Stash<double>{nullptr, (lds_tab_ptr)lds_tab});   // (the pass called hanna() with the stash's tables)
+    o[0] = T.sigu; o[1] = T.sigv; o[2] = T.sigw; o[3] = T.dsigwdz; o[4] = m_rcp(T.tlu); o[5] = m_rcp(T.tlv); o[6] = T.tlw;
+    o[7] = T.ust; o[8] = h / m_abs(ol) < 1. ? 0. : ol < 0. ? 1. : 2.; o[9] = deep ? 1. : 0.;
+  }
 }
 
 // completion of ONE boundary-layer particle: label 700 if it left the PBL, sigmas for the mesoscale term, label 99 to the end
@@ -5613,6 +5666,22 @@ int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(y, dy, n * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(dx); (void)hipFree(dy);
+  return e == hipSuccess ? FPX_OK : FPX_ERR_DEVICE;
+}
+
+int fpx_hanna_probe(const double *in, double *out, int64_t n) {
+  if (!in || !out || n < 0) return FPX_ERR_ARG;
+  if (n == 0) return FPX_OK;
+  double *dx = nullptr, *dy = nullptr;
+  if (hipMalloc(&dx, 5 * n * sizeof(double)) != hipSuccess) return FPX_ERR_NOMEM;
+  if (hipMalloc(&dy, 10 * n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); return FPX_ERR_NOMEM; }
+  hipError_t e = hipMemcpy(dx, in, 5 * n * sizeof(double), hipMemcpyHostToDevice);
+  for (int which = 0; which < 2 && e == hipSuccess; which++) {   // out: all points of the engine's form, then all of the plain one
+    fpx::k_hanna_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(which, dx, dy, n);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out + 10 * n * which, dy, 10 * n * sizeof(double), hipMemcpyDeviceToHost);
+  }
   (void)hipFree(dx); (void)hipFree(dy);
   return e == hipSuccess ? FPX_OK : FPX_ERR_DEVICE;
 }

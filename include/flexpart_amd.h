@@ -647,6 +647,11 @@ void *fpx_stream(fpx_handle h);
  * 9 m_exp_tab, 10 m_log_abs, 11 m_rcbrt (the table-based helpers of the fine sub-step).  No reference counterpart; used by the parity tests to bound
  * the helpers against libm.  Returns 0 or a negative fpx_status. */
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n);
+/* Diagnostics: the turbulence profiles of one Langevin pass (hanna.f90) for n points in[5i..5i+4] = h, ol, ust, wst, z: ten values
+ * per point -- sigu, sigv, sigw, dsigwdz, 1/tlu, 1/tlv, tlw, ust as hanna.f90:43 floors it, regime (0 neutral, 1 unstable, 2 stable),
+ * -h/ol > 5 (0/1) -- computed the way the engine does, from the step's invariants as k_prep takes them and the Langevin kernel's
+ * stash holds them (out[10i..10i+9]), and by the plain form (out[10n + 10i ..]).  The two halves must agree in every bit. */
+int fpx_hanna_probe(const double *in, double *out, int64_t n);
 /* Diagnostics of a library built with -DFPX_LANE_STATS (all zeros otherwise): for code region r of the Langevin kernel
  * out[2r] = how many times a wave executed it, out[2r+1] = the lanes that were active, summed.  Regions: 0 a pass,
  * 1 a fine sub-step, 2 its CBL branch, 3 the Gaussian branch under cblflag, 4 the exponential-form branch, 5/6/7 hanna_short
