@@ -6,8 +6,8 @@
 // One lane per grid column (the level loops of a column are sequential: running hydrostatic sums, first-crossing
 // searches); consecutive lanes own consecutive ix, so every level access of a wave is one contiguous row segment.
 // Arithmetic in the host's real kind H with FMA contraction off; log, exp, x**y come from the device's libm.
-// Not computed: the dry-deposition velocities (getvdep, calcpar.f90:174-193: land-use tables stay with the host, vdep is
-// an input) and the potential vorticity (calcpv, :270).
+// Not computed here: the dry-deposition velocities (calcpar.f90:171-189) -- fpx_getvdep (fpx_getvdep.hpp) computes them from
+// the ustar and oli this kernel leaves on the device, or the host passes its own vdep -- and the potential vorticity (calcpv, :270).
 #pragma once
 #include "fpx_tu.hpp"
 #include <hip/hip_runtime.h>

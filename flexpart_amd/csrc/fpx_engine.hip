@@ -23,6 +23,7 @@
 #include "fpx_device.hpp"
 #include "fpx_verttransform.hpp"
 #include "fpx_calcpar.hpp"
+#include "fpx_getvdep.hpp"
 #include "fpx_convect.hpp"
 #include "fpx_rng_host.hpp"
 
@@ -1999,6 +2000,9 @@ struct EngineBase {
   virtual int verttransform_nest(int nest, int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) = 0;
   virtual int calcpar(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) = 0;
   virtual double cp_ms() = 0;
+  virtual int getvdep_init(const fpx_getvdep_tables *t) = 0;
+  virtual int getvdep(int slot, const fpx_getvdep_in *g, void *vdep_out) = 0;
+  virtual double gv_ms() = 0;
   virtual int set_windtime(const int32_t mt[2], const int32_t mi[2]) = 0;
   virtual int rng_fill_table() = 0;
   virtual int rng_set_table(const void *t, int n) = 0;
@@ -2733,7 +2737,7 @@ struct Engine : EngineBase {
     vt_last_ms = ms;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     // without sfc the slot's 2-D fields are still those of the previous wind field until fpx_calcpar has run: not loaded
-    if (nest) nest_loaded[nest - 1][s] = true; else slot_loaded[s] = sfc != nullptr;
+    if (nest) nest_loaded[nest - 1][s] = true; else { slot_loaded[s] = sfc != nullptr; vdep_pending[s] = false; }
     if (!nest) vt_slot_on_device = slot;      // whose model-level arrays the buffers hold (fpx_calcpar)
     return 0;
   }
@@ -2788,7 +2792,7 @@ struct Engine : EngineBase {
     if ((rc = pk2(d_ust, V.sfc, 8, s * 4 + 0)) || (rc = pk2(d_wst, V.sfc, 8, s * 4 + 1)) || (rc = pk2(d_oli, V.sfc, 8, s * 4 + 2)) || (rc = pk2(d_hmix, V.sfc, 8, s * 4 + 3))) return rc;
     if (slot == 1 && (rc = pk2(d_trop, V.tropo, 1, 0))) return rc;        // literal time index 1, advance.f90:253
     diag_have[DG_TROPO + s] = true;
-    if (V.vdep) {
+    if (V.vdep && c->vdep) {
       const size_t plane = n2 * cfg.host_real_bytes;
       for (int ks = 0; ks < cfg.nspec; ks++)
         if ((rc = p2(host_grid(0), (const char *)c->vdep + plane * ks, V.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
@@ -2806,19 +2810,188 @@ struct Engine : EngineBase {
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     cp_last_ms = ms;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    slot_loaded[s] = true;
+    cp_slot_on_device = slot;                  // whose ustar, oli the buffer holds (fpx_getvdep)
+    // device_vdep with DRYDEP: the slot's vdep is still the previous wind field's until fpx_getvdep has run: not loaded
+    vdep_pending[s] = V.vdep && !c->vdep;
+    slot_loaded[s] = !vdep_pending[s];
     return 0;
   }
   void *cp_buf = nullptr;
   double cp_last_ms = 0;
+  int cp_slot_on_device = 0;
+  bool vdep_pending[2] = {false, false};
   int calcpar(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) override {
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "calcpar: slot must be 1 or 2");
     if (!c || !c->surfstr || !c->sshf || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "calcpar: surfstr, sshf, akm, bkm are required");
     if (c->lsubgrid == 1 && !c->excessoro) return fail(FPX_ERR_ARG, "calcpar: excessoro required with lsubgrid = 1");
-    if (cfg.drydep && !c->vdep) return fail(FPX_ERR_ARG, "calcpar: vdep (the host's getvdep) required with DRYDEP");
+    if (cfg.drydep && !c->vdep && !c->device_vdep) return fail(FPX_ERR_ARG, "calcpar: vdep (the host's getvdep) required with DRYDEP");
     if (!vt_set_ready[0] || vt_slot_on_device != slot) return fail(FPX_ERR_STATE, "calcpar: fpx_verttransform_ecmwf of this slot first (its model-level arrays are read on the device)");
     return cfg.host_real_bytes == 4 ? calcpar_t<float>(slot, c, out) : calcpar_t<double>(slot, c, out);
   }
+  // ---- getvdep on the device (calcpar.f90:171-189) ------------------------------------------------------------
+  void *gv_tab = nullptr, *gv_land = nullptr, *gv_buf = nullptr;
+  unsigned char *gv_season = nullptr;
+  gv::Layout gv_lay{0, 0, 0};
+  double gv_bdate = 0, gv_last_ms = 0;
+  bool gv_ready = false;
+
+  template <typename H>
+  int getvdep_init_t(const fpx_getvdep_tables *t) {
+    const gv::Layout Ly{t->numclass, t->ni, t->maxspec};
+    const size_t n2 = (size_t)cfg.nxmax * cfg.nymax;
+    int rc;
+    gv_ready = false;
+    if (!gv_tab || Ly.numclass != gv_lay.numclass || Ly.ni != gv_lay.ni || Ly.maxspec != gv_lay.maxspec) {
+      H *q = nullptr;
+      if ((rc = dalloc(&q, (size_t)Ly.total()))) return rc;
+      gv_tab = q;
+      if ((rc = dalloc(&q, n2 * Ly.numclass))) return rc;
+      gv_land = q;
+    }
+    std::vector<H> pk((size_t)Ly.total());
+    auto put = [&](int off, const void *src, size_t n) { memcpy(pk.data() + off, src, n * sizeof(H)); };
+    const int ms = Ly.maxspec, nc = Ly.numclass;
+    put(Ly.z0(), t->z0, nc); put(Ly.ri(), t->ri, 5 * nc); put(Ly.rac(), t->rac, 5 * nc);
+    put(Ly.rcl(), t->rcl, (size_t)ms * 5 * nc); put(Ly.rgs(), t->rgs, (size_t)ms * 5 * nc); put(Ly.rlu(), t->rlu, (size_t)ms * 5 * nc);
+    const void *sp[6] = {t->rm, t->reldiff, t->henry, t->f0, t->density, t->dryvel};
+    for (int i = 0; i < 6; i++) put(Ly.spec() + i * ms, sp[i], ms);
+    put(Ly.vset(), t->vset, (size_t)ms * Ly.ni); put(Ly.vset() + ms * Ly.ni, t->schmi, (size_t)ms * Ly.ni); put(Ly.vset() + 2 * ms * Ly.ni, t->fract, (size_t)ms * Ly.ni);
+    HIPCHK(hipMemcpyAsync(gv_tab, pk.data(), pk.size() * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(gv_land, t->xlanduse, n2 * nc * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    gv_lay = Ly;
+    gv_bdate = t->bdate;
+    gv_ready = true;
+    return 0;
+  }
+  int getvdep_init(const fpx_getvdep_tables *t) override {
+    static_assert(gv::kMaxSpec == FPX_MAXSPEC, "the lane-private species arrays of k_getvdep");
+    if (!t || !t->xlanduse || !t->z0 || !t->ri || !t->rac || !t->rcl || !t->rgs || !t->rlu || !t->rm || !t->reldiff || !t->henry ||
+        !t->f0 || !t->density || !t->dryvel || !t->vset || !t->schmi || !t->fract)
+      return fail(FPX_ERR_ARG, "getvdep_init: xlanduse, z0, ri, rac, rcl, rgs, rlu, rm, reldiff, henry, f0, density, dryvel, vset, schmi, fract are required");
+    if (!cfg.drydep) return fail(FPX_ERR_ARG, "getvdep_init: the run has no dry deposition (DRYDEP)");
+    if (t->numclass < 1 || t->numclass > 255 || t->ni < 1 || t->ni > 4096 || t->maxspec < cfg.nspec || t->maxspec > 64)
+      return fail(FPX_ERR_ARG, "getvdep_init: 1 <= numclass <= 255, 1 <= ni <= 4096, nspec <= maxspec <= 64 expected");
+    const gv::Layout Ly{t->numclass, t->ni, t->maxspec};
+    if ((size_t)Ly.total() * cfg.host_real_bytes > (size_t)60 * 1024) return fail(FPX_ERR_ARG, "getvdep_init: the resistance tables do not fit the LDS of a block (60 KiB)");
+    return cfg.host_real_bytes == 4 ? getvdep_init_t<float>(t) : getvdep_init_t<double>(t);
+  }
+
+  // caldate.f90:42-65 (the date part), its default-real literals in the host's real kind H
+  template <typename H>
+  static int gv_caldate(double juldate) {
+#pragma clang fp contract(off)
+    int julday = (int)juldate;
+    if ((juldate - julday) * 86400. >= 86399.5) {
+      juldate = juldate + juldate - julday - 86399.5 / 86400.;
+      julday = (int)juldate;
+    }
+    int ja;
+    if (julday >= 2299161) {
+      const int jalpha = (int)(((H)(julday - 1867216) - (H)0.25) / (H)36524.25);
+      ja = julday + 1 + jalpha - (int)((H)0.25 * (H)jalpha);
+    } else ja = julday;
+    const int jb = ja + 1524;
+    const int jc = (int)((H)6680. + ((H)(jb - 2439870) - (H)122.1) / (H)365.25);
+    const int jd = 365 * jc + (int)((H)0.25 * (H)jc);
+    const int je = (int)((H)(jb - jd) / (H)30.6001);
+    const int dd = jb - jd - (int)((H)30.6001 * (H)je);
+    int mm = je - 1;
+    if (mm > 12) mm = mm - 12;
+    int yyyy = jc - 4715;
+    if (mm > 2) yyyy = yyyy - 1;
+    if (yyyy <= 0) yyyy = yyyy - 1;
+    return 10000 * yyyy + 100 * mm + dd;
+  }
+  // getvdep.f90:51-77: the seasonal category of every grid row at wind-field time wftime
+  template <typename H>
+  void gv_seasons(int wftime, std::vector<unsigned char> &ls) {
+#pragma clang fp contract(off)
+    ls.resize(cfg.ny);
+    for (int jy = 0; jy < cfg.ny; jy++) {
+      double jul = gv_bdate + (double)wftime / 86400.;
+      const H ylat = (H)jy * (H)cfg.dy + (H)cfg.ylat0;
+      if (ylat < (H)0) jul = jul + (double)(365 / 2);
+      const int yyyymmdd = gv_caldate<H>(jul);
+      const int yyyy = yyyymmdd / 10000;
+      int mmdd = yyyymmdd - 10000 * yyyy;
+      if (ylat > (H)-20 && ylat < (H)20) mmdd = 600;
+      int lseason;
+      if (mmdd >= 1201 || mmdd <= 301) lseason = 4;
+      else if (mmdd >= 1101 || mmdd <= 331) lseason = 3;
+      else if (mmdd >= 401 && mmdd <= 515) lseason = 5;
+      else if (mmdd >= 516 && mmdd <= 915) lseason = 1;
+      else lseason = 2;
+      ls[jy] = (unsigned char)lseason;
+    }
+  }
+
+  template <typename H>
+  int getvdep_t(int slot, const fpx_getvdep_in *g, void *vdep_out) {
+    const int s = slot - 1, nspec = cfg.nspec;
+    const size_t n2 = (size_t)cfg.nxmax * cfg.nymax;
+    int rc;
+    if (!gv_buf) {
+      H *q = nullptr;
+      if ((rc = dalloc(&q, (9 + (size_t)FPX_MAXSPEC) * n2))) return rc;      // ssr, lsprec, convprec, sd, ustar, oli, ps, tt2, td2 | vdep planes
+      HIPCHK(hipMemsetAsync(q, 0, (9 + (size_t)FPX_MAXSPEC) * n2 * sizeof(H), stream));
+      gv_buf = q;
+      if ((rc = dalloc(&gv_season, (size_t)cfg.ny))) return rc;
+    }
+    H *B = (H *)gv_buf;
+    const void *host[9] = {g->ssr, g->lsprec, g->convprec, g->sd, g->ustar, g->oli, g->ps, g->tt2, g->td2};
+    const H *dev[9];
+    for (int i = 0; i < 9; i++) {
+      dev[i] = B + i * n2;
+      if (host[i]) HIPCHK(hipMemcpyAsync(B + i * n2, host[i], n2 * sizeof(H), hipMemcpyHostToDevice, stream));
+    }
+    if (!g->ustar) dev[4] = (const H *)cp_buf + 3 * n2;                        // what fpx_calcpar left (calcpar_t)
+    if (!g->oli) dev[5] = (const H *)cp_buf + 5 * n2;
+    for (int i = 6; i < 9; i++)
+      if (!host[i]) dev[i] = (const H *)vt_sets[0][i];                         // PS, TT2, TD2 of the transform (verttransform_t)
+    std::vector<unsigned char> ls;
+    gv_seasons<H>(g->wftime, ls);
+    HIPCHK(hipMemcpyAsync(gv_season, ls.data(), ls.size(), hipMemcpyHostToDevice, stream));
+    gv::Args<H> A;
+    A.nx = cfg.nx; A.ny = cfg.ny; A.nxmax = cfg.nxmax; A.nymax = cfg.nymax; A.nspec = nspec;
+    A.T = gv_lay; A.tables = (const H *)gv_tab; A.xlanduse = (const H *)gv_land;
+    A.ssr = dev[0]; A.lsprec = dev[1]; A.convprec = dev[2]; A.sd = dev[3]; A.ustar = dev[4]; A.oli = dev[5]; A.ps = dev[6]; A.tt2 = dev[7]; A.td2 = dev[8];
+    A.lseason = gv_season;
+    H *d_vdep = B + 9 * n2;
+    A.vdep = d_vdep;
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, stream));
+    gv::k_getvdep<H><<<(cfg.nx * cfg.ny + 255) / 256, 256, (size_t)gv_lay.total() * sizeof(H), stream>>>(A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, stream));
+    // into the gather pack, as upload_fields does from the host's vdep(0,0,1,n) planes
+    const int tot = cfg.nx * cfg.ny;
+    for (int ks = 0; ks < nspec; ks++) {
+      k_pack2<H, R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>(d_vdep + n2 * ks, (R *)V.vdep, cfg.nx, cfg.ny, cfg.nxmax, 2 * nspec, s * nspec + ks);
+      HIPCHK(hipGetLastError());
+    }
+    if (vdep_out) HIPCHK(hipMemcpyAsync(vdep_out, d_vdep, n2 * nspec * sizeof(H), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    gv_last_ms = ms;
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (vdep_pending[s]) { vdep_pending[s] = false; slot_loaded[s] = true; }   // fpx_calcpar(device_vdep = 1) was waiting for this
+    return 0;
+  }
+  int getvdep(int slot, const fpx_getvdep_in *g, void *vdep_out) override {
+    if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "getvdep: slot must be 1 or 2");
+    if (!cfg.drydep || !V.vdep) return fail(FPX_ERR_ARG, "getvdep: the run has no dry deposition (DRYDEP)");
+    if (!gv_ready) return fail(FPX_ERR_STATE, "getvdep: fpx_getvdep_init first (the land-use inventory and the resistance tables)");
+    if (!g || !g->ssr || !g->lsprec || !g->convprec || !g->sd) return fail(FPX_ERR_ARG, "getvdep: ssr, lsprec, convprec, sd are required");
+    if ((!g->ustar || !g->oli) && (!cp_buf || cp_slot_on_device != slot))
+      return fail(FPX_ERR_ARG, "getvdep: ustar / oli = NULL means the ones fpx_calcpar left on the device: fpx_calcpar of this slot first");
+    if ((!g->ps || !g->tt2 || !g->td2) && (!vt_set_ready[0] || vt_slot_on_device != slot))
+      return fail(FPX_ERR_ARG, "getvdep: ps / tt2 / td2 = NULL means the ones of fpx_verttransform_ecmwf: transform this slot first");
+    return cfg.host_real_bytes == 4 ? getvdep_t<float>(slot, g, vdep_out) : getvdep_t<double>(slot, g, vdep_out);
+  }
+  double gv_ms() override { return gv_last_ms; }
   double vt_last_ms = 0, po_last_ms = 0;
   double po_ms() override { return po_last_ms; }
   double vt_ms() override { return vt_last_ms; }
@@ -5528,6 +5701,9 @@ int fpx_readpartpositions(fpx_handle h, const char *path, const fpx_restart *r, 
 int fpx_concoutput(fpx_handle h, int32_t itime, const fpx_concout *c, const char *prefix, int32_t clear) { FPX_GUARD(h); return h->impl->concoutput(itime, c, prefix, clear); }
 int fpx_partoutput_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_partoutput_time: null"); *ms = h->impl->po_ms(); return FPX_OK; }
 int fpx_calcpar(fpx_handle h, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) { FPX_GUARD(h); return h->impl->calcpar(slot, c, out); }
+int fpx_getvdep_init(fpx_handle h, const fpx_getvdep_tables *t) { FPX_GUARD(h); return h->impl->getvdep_init(t); }
+int fpx_getvdep(fpx_handle h, int32_t slot, const fpx_getvdep_in *g, void *vdep_out) { FPX_GUARD(h); return h->impl->getvdep(slot, g, vdep_out); }
+int fpx_getvdep_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_getvdep_time: null"); *ms = h->impl->gv_ms(); return FPX_OK; }
 int fpx_calcpar_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_calcpar_time: null"); *ms = h->impl->cp_ms(); return FPX_OK; }
 int fpx_verttransform_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_verttransform_time: null"); *ms = h->impl->vt_ms(); return FPX_OK; }
 int fpx_set_windtime(fpx_handle h, const int32_t memtime[2], const int32_t memind[2]) { FPX_GUARD(h); return h->impl->set_windtime(memtime, memind); }

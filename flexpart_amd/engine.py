@@ -242,9 +242,9 @@ class Engine:
         out["call_ms"] = call_s * 1e3
         return out
 
-    def calcpar(self, slot, cin, vdep=None):
+    def calcpar(self, slot, cin, vdep=None, device_vdep=False):
         """fpx_calcpar after verttransform(slot, m, None): cin = synthetic.calcpar_inputs(m).  Returns the five 2-D fields
-        (compact [ny][nx]) and the device time."""
+        (compact [ny][nx]) and the device time.  device_vdep: with DRYDEP no vdep is handed over; getvdep(slot, ..) follows."""
         from ._lib import FpxCalcparIn, FpxCalcparOut
         rt = self.hreal
         keep = {}
@@ -258,6 +258,7 @@ class Engine:
             keep[k] = np.ascontiguousarray(np.asarray(cin[k]).astype(rt))
             setattr(c, k, keep[k].ctypes.data)
         c.lsubgrid = int(cin["lsubgrid"])
+        c.device_vdep = int(bool(device_vdep))
         if vdep is not None:
             v = np.zeros((self.nspec, self.nymax, self.nxmax), rt)
             v[:, : self.ny, : self.nx] = vdep
@@ -274,6 +275,49 @@ class Engine:
         check(self.lib.fpx_calcpar_time(self.h, C.byref(ms)), "fpx_calcpar_time")
         out["device_ms"] = ms.value
         return out
+
+    def getvdep_init(self, tables):
+        """fpx_getvdep_init: tables = synthetic.getvdep_tables() (xlanduse compact [numclass][ny][nx], the small tables in
+        com_mod's shapes, transposed to C order)."""
+        from ._lib import FpxGetvdepTables
+        rt = self.hreal
+        t = FpxGetvdepTables()
+        t.numclass, t.ni, t.maxspec = int(tables["numclass"]), int(tables["ni"]), int(tables["maxspec"])
+        t.bdate = float(tables["bdate"])
+        keep = {}
+        xl = np.zeros((t.numclass, self.nymax, self.nxmax), rt)
+        xl[:, : self.ny, : self.nx] = tables["xlanduse"]
+        keep["xlanduse"] = xl
+        for k in ("z0", "ri", "rac", "rcl", "rgs", "rlu", "rm", "reldiff", "henry", "f0", "density", "dryvel", "vset", "schmi", "fract"):
+            keep[k] = np.ascontiguousarray(np.asarray(tables[k]).astype(rt))
+        for k, a in keep.items():
+            setattr(t, k, a.ctypes.data)
+        check(self.lib.fpx_getvdep_init(self.h, C.byref(t)), "fpx_getvdep_init")
+
+    def getvdep(self, slot, gin, *, given=None):
+        """fpx_getvdep: gin = synthetic.getvdep_inputs() (wftime and compact [ny][nx] ssr, lsprec, convprec, sd); `given`: a
+        dict with any of ustar, oli, ps, tt2, td2 as the host's arrays -- what is missing is taken from the device
+        (fpx_calcpar, fpx_verttransform_ecmwf of this slot).  Returns vdep [nspec][ny][nx] as copied back, and the times."""
+        from ._lib import FpxGetvdepIn
+        import time as _time
+        rt = self.hreal
+        g = FpxGetvdepIn()
+        g.wftime = int(gin["wftime"])
+        keep = {}
+        src = {k: gin[k] for k in ("ssr", "lsprec", "convprec", "sd")}
+        src.update(given or {})
+        for k, v in src.items():
+            a = np.zeros((self.nymax, self.nxmax), rt)
+            a[: self.ny, : self.nx] = v
+            keep[k] = a
+            setattr(g, k, a.ctypes.data)
+        out = np.zeros((self.nspec, self.nymax, self.nxmax), rt)
+        t0 = _time.perf_counter()
+        check(self.lib.fpx_getvdep(self.h, int(slot), C.byref(g), _vp(out)), "fpx_getvdep")
+        call_s = _time.perf_counter() - t0
+        ms = C.c_double(0)
+        check(self.lib.fpx_getvdep_time(self.h, C.byref(ms)), "fpx_getvdep_time")
+        return dict(vdep=out[:, : self.ny, : self.nx].astype(np.float64), device_ms=ms.value, call_ms=call_s * 1e3)
 
     def _verttransform_nest(self, slot, n, sfc, want):
         from ._lib import FpxModelLevels, FpxFieldsOut

@@ -34,6 +34,7 @@ module flexgpu_mod
             flexgpu_upload_diag_fields, flexgpu_partoutput, flexgpu_readpartpositions, &
             flexgpu_concoutput, flexgpu_abi_sizes, flexgpu_comm_init_host, flexgpu_count_particles, flexgpu_set_option, flexgpu_get_info, &
             flexgpu_release_init, flexgpu_releaseparticles, flexgpu_split_particles, flexgpu_calcpar, &
+            flexgpu_getvdep_init, flexgpu_getvdep, &
             flexgpu_redist_plan, flexgpu_redist_bytes, flexgpu_redist_pack, flexgpu_redist_unpack, &
             flexgpu_checkpoint_write, flexgpu_checkpoint_read, &
             flexgpu_conv_init, flexgpu_upload_conv_fields, flexgpu_convmix, flexgpu_cbaseflux
@@ -135,8 +136,20 @@ module flexgpu_mod
   type, bind(C) :: fpx_calcpar_in
     type(c_ptr) :: surfstr, sshf, akm, bkm, excessoro, vdep
     integer(c_int32_t) :: lsubgrid
-    integer(c_int32_t) :: reserved(3)
+    integer(c_int32_t) :: device_vdep
+    integer(c_int32_t) :: reserved(2)
   end type fpx_calcpar_in
+  type, bind(C) :: fpx_getvdep_tables
+    integer(c_int32_t) :: numclass, ni, maxspec, reserved
+    real(c_double) :: bdate
+    type(c_ptr) :: xlanduse, z0, ri, rac, rcl, rgs, rlu
+    type(c_ptr) :: rm, reldiff, henry, f0, density, dryvel, vset, schmi, fract
+  end type fpx_getvdep_tables
+  type, bind(C) :: fpx_getvdep_in
+    integer(c_int32_t) :: wftime, reserved
+    type(c_ptr) :: ssr, lsprec, convprec, sd
+    type(c_ptr) :: ustar, oli, ps, tt2, td2
+  end type fpx_getvdep_in
   type, bind(C) :: fpx_calcpar_out
     type(c_ptr) :: ustar, wstar, oli, hmix, tropopause
   end type fpx_calcpar_out
@@ -181,6 +194,18 @@ module flexgpu_mod
       integer(c_int32_t), value :: slot
       type(fpx_calcpar_in), intent(in) :: c
       type(fpx_calcpar_out), intent(in) :: o
+    end function
+    integer(c_int) function fpx_getvdep_init(h, t) bind(C, name='fpx_getvdep_init')
+      import :: c_ptr, c_int, fpx_getvdep_tables
+      type(c_ptr), value :: h
+      type(fpx_getvdep_tables), intent(in) :: t
+    end function
+    integer(c_int) function fpx_getvdep(h, slot, g, vdep_out) bind(C, name='fpx_getvdep')
+      import :: c_ptr, c_int, c_int32_t, fpx_getvdep_in
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: slot
+      type(fpx_getvdep_in), intent(in) :: g
+      type(c_ptr), value :: vdep_out
     end function
     integer(c_int) function fpx_release_init(h, r) bind(C, name='fpx_release_init')
       import :: c_ptr, c_int, fpx_release
@@ -1054,23 +1079,30 @@ contains
 
   ! particles j1..j2 (Fortran numbering) host -> device / device -> host
   ! Replaces `call calcpar(n,uuh,vvh,pvh)` (getfields.f90:128,163,179) for ustar, wstar, oli, hmix, tropopause of slot n
-  ! (ECMWF fields): call after flexgpu_verttransform(n, ...) with its sfc argument omitted.  vdep (getvdep) and pv
-  ! (calcpv) stay with the host: with DRYDEP the host's vdep(:,:,:,n) must have been computed before this call.
+  ! (ECMWF fields): call after flexgpu_verttransform(n, ...) with its sfc argument omitted.  pv (calcpv) stays with the
+  ! host.  vdep: with DRYDEP either the host's vdep(:,:,:,n) must have been computed before this call, or
+  ! device_vdep = .true. and flexgpu_getvdep(n, ierr) follows (the slot is not usable by the step until it has run).
   ! writeback (default .true.): the five fields are also copied into com_mod for host routines that read them.
   ! (No Fortran-host test: calcpar.f90 itself cannot be compiled in the build image -- class_gribfile needs ecCodes.)
-  subroutine flexgpu_calcpar(n, ierr, writeback)
+  subroutine flexgpu_calcpar(n, ierr, writeback, device_vdep)
     integer, intent(in) :: n
     integer, intent(out) :: ierr
-    logical, intent(in), optional :: writeback
+    logical, intent(in), optional :: writeback, device_vdep
     type(fpx_calcpar_in) :: c
     type(fpx_calcpar_out) :: o
-    logical :: wb
+    logical :: wb, dv
     wb = .true.; if (present(writeback)) wb = writeback
+    dv = .false.; if (present(device_vdep)) dv = device_vdep
     c%surfstr = loc_r(surfstr(0,0,1,n)); c%sshf = loc_r(sshf(0,0,1,n))
     c%akm = loc_r(akm); c%bkm = loc_r(bkm)
     c%excessoro = loc_r(excessoro); c%lsubgrid = lsubgrid
     c%vdep = c_null_ptr
-    if (DRYDEP) c%vdep = loc_r(vdep(0,0,1,n))
+    c%device_vdep = 0
+    if (DRYDEP .and. dv) then
+      c%device_vdep = 1
+    else if (DRYDEP) then
+      c%vdep = loc_r(vdep(0,0,1,n))
+    end if
     c%reserved = 0
     o%ustar = c_null_ptr; o%wstar = c_null_ptr; o%oli = c_null_ptr; o%hmix = c_null_ptr; o%tropopause = c_null_ptr
     if (wb) then
@@ -1079,6 +1111,41 @@ contains
     end if
     ierr = fpx_calcpar(flexgpu_handle, int(n, c_int32_t), c, o)
   end subroutine flexgpu_calcpar
+
+  ! ---- getvdep on the device (the DRYDEP block of calcpar, calcpar.f90:171-189) --------------------------------
+  ! once, after readlanduse / readdepo / readspecies / assignland have filled com_mod and after flexgpu_init: the land-use
+  ! inventory of the mother grid and the resistance tables.  (No nest variant: getvdep_nests / vdepn stay the host's.)
+  subroutine flexgpu_getvdep_init(ierr)
+    integer, intent(out) :: ierr
+    type(fpx_getvdep_tables) :: t
+    t%numclass = numclass; t%ni = ni; t%maxspec = maxspec; t%reserved = 0
+    t%bdate = bdate
+    t%xlanduse = loc_r(xlanduse); t%z0 = loc_r(z0); t%ri = loc_r(ri); t%rac = loc_r(rac)
+    t%rcl = loc_r(rcl); t%rgs = loc_r(rgs); t%rlu = loc_r(rlu)
+    t%rm = loc_r(rm); t%reldiff = loc_r(reldiff); t%henry = loc_r(henry); t%f0 = loc_r(f0)
+    t%density = loc_r(density); t%dryvel = loc_r(dryvel)
+    t%vset = loc_r(vset); t%schmi = loc_r(schmi); t%fract = loc_r(fract)
+    ierr = fpx_getvdep_init(flexgpu_handle, t)
+  end subroutine flexgpu_getvdep_init
+
+  ! vdep(:,:,1:nspec,n) of slot n after flexgpu_calcpar(n, ierr, device_vdep=.true.): ustar and oli are the ones that call
+  ! left on the device, ps, tt2, td2 the ones of flexgpu_verttransform(n, ...); ssr, lsprec, convprec, sd come from com_mod.
+  ! The season is taken at wftime(n), as getvdep.f90:51 does.  writeback (default .true.): vdep is also copied into com_mod.
+  subroutine flexgpu_getvdep(n, ierr, writeback)
+    integer, intent(in) :: n
+    integer, intent(out) :: ierr
+    logical, intent(in), optional :: writeback
+    type(fpx_getvdep_in) :: g
+    type(c_ptr) :: vout
+    logical :: wb
+    wb = .true.; if (present(writeback)) wb = writeback
+    g%wftime = int(wftime(n), c_int32_t); g%reserved = 0
+    g%ssr = loc_r(ssr(0,0,1,n)); g%lsprec = loc_r(lsprec(0,0,1,n)); g%convprec = loc_r(convprec(0,0,1,n)); g%sd = loc_r(sd(0,0,1,n))
+    g%ustar = c_null_ptr; g%oli = c_null_ptr; g%ps = c_null_ptr; g%tt2 = c_null_ptr; g%td2 = c_null_ptr
+    vout = c_null_ptr
+    if (wb) vout = loc_r(vdep(0,0,1,n))
+    ierr = fpx_getvdep(flexgpu_handle, int(n, c_int32_t), g, vout)
+  end subroutine flexgpu_getvdep
 
   ! ---- releaseparticles + the splitting block on the device (SURVEY section 8 f2) ----------------------------
   ! after readreleases (point_mod arrays) and flexgpu_init: hands the release tables to the engine

@@ -803,3 +803,76 @@ def convection_case(nx=24, ny=16, nuvz=46, n=4000, ncalls=3, ldirect=1, lsynctim
                xtra1=0.3 + u[0] * (nx - 1.6), ytra1=0.3 + u[1] * (ny - 1.6), ztra1=16000.0 * u[2] ** 1.5,
                due=(u[3][:, None] + 0.013 * np.arange(ncalls)[None, :]) % 1.0 > 0.1, npart=n)
     return out
+
+
+# --------------------------------------------------------------------------
+# getvdep (calcpar.f90:171-189): land use, resistance tables, the surface fields it reads
+# --------------------------------------------------------------------------
+GV_NUMCLASS, GV_NI, GV_MAXSPEC = 13, 11, 5          # par_mod.f90:211,225
+GV_BDATE = 2458864.0                                # 15 January 2020, 0 UTC (juldate.f90)
+# wind-field times [s] after bdate: 15 January 2020, 10 November 2020 3 UTC, 1 October 2019 6 UTC (a backward run).  The
+# southern rows see the date half a year on (getvdep.f90:54-56), the tropical ones always summer: a winter date (season
+# 4) always meets summer (1) on the other side, so it takes three dates to see all five seasonal categories.
+GV_WFTIMES = (0, 300 * 86400 + 10800, -106 * 86400 + 21600)
+
+
+def getvdep_tables(nx, ny, nspec, seed=4100):
+    """The arrays of com_mod that getvdep and its callees read, in C order (the Fortran shapes transposed): xlanduse
+    [numclass][ny][nx] (most classes absent from a column, fractions summing to one), z0 [numclass], ri, rac
+    [numclass][5], rcl, rgs, rlu [numclass][5][maxspec], the species constants [maxspec] and vset, schmi, fract
+    [ni][maxspec].  Species cycle through the four kinds getvdep distinguishes: a gas (reldiff > 0), an aerosol
+    (density > 0), one with a constant deposition velocity (dryvel > 0) and an inert one."""
+    nc, ni, ms = GV_NUMCLASS, GV_NI, GV_MAXSPEC
+    assert nspec <= ms
+    u = _uniform01(nc * ny * nx, seed).reshape(nc, ny, nx)
+    xl = np.where(u > 0.7, u - 0.7, 0.0)
+    tot = np.zeros((ny, nx))
+    for j in range(nc):
+        tot = tot + xl[j]
+    xl = xl / np.where(tot > 0.0, tot, 1.0)
+    z0 = np.array([0.7, 0.1, 0.1, 1.0, 1.0, 0.7, 1.0e-4, 2.0e-3, 0.15, 0.1, 0.1, 1.0e-3, 0.3])
+    ur = _uniform01(5 * nc, seed + 1).reshape(nc, 5)
+    ri = np.where(ur > 0.8, 9999.0, 60.0 + 800.0 * ur * ur)
+    rac = 2000.0 * _uniform01(5 * nc, seed + 2).reshape(nc, 5) ** 2
+    def res(k):
+        v = _uniform01(ms * 5 * nc, seed + k).reshape(nc, 5, ms)
+        return np.where(v > 0.85, 9999.0, 50.0 + 4000.0 * v * v)
+    kind = np.arange(ms) % 4
+    gas, aero, const = kind == 0, kind == 1, kind == 2
+    step = 1.0 + 0.25 * (np.arange(ms) // 4)
+    reldiff = np.where(gas, 1.6 * step, -9.9)
+    rm = np.where(gas, 10.0 * (step - 1.0), 0.0)
+    henry = np.where(gas, 1.0e5 * step, 0.0)
+    f0 = np.where(gas, 0.1 * step, 0.0)
+    density = np.where(aero, 1400.0 * step, -9.0)
+    dryvel = np.where(const, 0.005 * step, -9.9)
+    vs = np.array([1.0e-6, 3.0e-6, 1.0e-5, 3.0e-5, 1.0e-4, 3.0e-4, 1.0e-3, 3.0e-3, 1.0e-2, 2.0e-2, 5.0e-2])
+    sm = np.array([1.0e-1, 6.0e-2, 3.0e-2, 1.5e-2, 8.0e-3, 4.0e-3, 2.0e-3, 1.0e-3, 5.0e-4, 2.5e-4, 1.0e-4])
+    fr = np.array([1.0, 2.0, 4.0, 8.0, 12.0, 16.0, 12.0, 8.0, 4.0, 2.0, 1.0]) / 70.0
+    on = np.where(aero, 1.0, 0.0)[None, :]
+    return dict(numclass=nc, ni=ni, maxspec=ms, nspec=int(nspec), bdate=GV_BDATE, xlanduse=xl, z0=z0, ri=ri, rac=rac,
+                rcl=res(3), rgs=res(4), rlu=res(5), rm=rm, reldiff=reldiff, henry=henry, f0=f0, density=density, dryvel=dryvel,
+                vset=vs[:, None] * step[None, :] * on, schmi=sm[:, None] / step[None, :] * on, fract=fr[:, None] * on)
+
+
+def getvdep_inputs(m_or_shape, seed=4200, wftime=0):
+    """ssr, lsprec, convprec, sd (compact [ny][nx]) for fpx_getvdep: radiation from night to noon, a quarter of the columns
+    with rain, an eighth under snow.  Given a shape (ny, nx) instead of a synthetic.model_levels() dict, also the fields
+    the device would otherwise take from fpx_calcpar and the transform: ustar (a few columns at calcpar's floor of
+    1e-8), oli (both signs, |L| = 9999 among them), ps, tt2 (from -35 to +50 C), td2 (a fifth of the columns above 90 %
+    relative humidity)."""
+    full = not isinstance(m_or_shape, dict)
+    ny, nx = (int(v) for v in m_or_shape) if full else (int(m_or_shape["grid"][1]), int(m_or_shape["grid"][0]))
+    u = [_uniform01(ny * nx, seed + k).reshape(ny, nx) for k in range(11)]
+    out = dict(wftime=int(wftime),
+               ssr=np.maximum(0.0, 900.0 * u[0] - 100.0),
+               lsprec=np.where(u[1] > 0.8, 3.0 * (u[1] - 0.8), 0.0),
+               convprec=np.where(u[2] > 0.9, 5.0 * (u[2] - 0.9), 0.0),
+               sd=np.where(u[3] > 0.85, 0.05 * (u[3] - 0.85), 0.0))
+    if full:
+        ol = np.where(u[5] < 0.5, 1.0, -1.0) * (5.0 + 2000.0 * u[6] * u[6])
+        ol = np.where(u[5] < 0.06, 9999.0, np.where(u[5] > 0.94, -9999.0, ol))
+        tt2 = 273.15 + (85.0 * u[8] - 35.0)
+        out.update(ustar=np.where(u[4] < 0.03, 1.0e-8, 0.05 + 0.9 * u[4] * u[4]), oli=1.0 / ol,
+                   ps=60000.0 + 45000.0 * u[7], tt2=tt2, td2=tt2 - 30.0 * u[9] * u[9])
+    return out

@@ -236,22 +236,60 @@ int fpx_verttransform_time(fpx_handle h, double *ms);
  * hmixmin/hmixmax, the subgrid-orography excess with lsubgrid = 1) and the thermal tropopause (:199-265).  It runs on the
  * model-level arrays fpx_verttransform_ecmwf(h, slot, m, sfc, ..) uploaded for this slot -- call that first, with
  * sfc = NULL (then the 2-D fields come from here and nothing but ps, tt2, td2, surfstr, sshf crosses PCIe) -- and
- * writes the gather packs of the slot directly.  Not computed: vdep (getvdep, calcpar.f90:174-193: the land-use tables
- * stay with the host; with DRYDEP pass the host's vdep of this slot) and the potential vorticity (calcpv, :270).
+ * writes the gather packs of the slot directly.  Not computed here: vdep (getvdep, calcpar.f90:171-189) -- with DRYDEP
+ * either pass the host's vdep of this slot, or set device_vdep = 1 and call fpx_getvdep(h, slot, ..) next, which computes
+ * it from the ustar and oli this call leaves on the device -- and the potential vorticity (calcpv, :270).
  * The reference calls calcpar before verttransform; the two are independent of each other's results. */
 typedef struct {
   const void *surfstr, *sshf;    /* c_loc(surfstr(0,0,1,n)), c_loc(sshf(0,0,1,n)), com_mod.f90:420-422          */
   const void *akm, *bkm;         /* (nwz) com_mod.f90:328                                                       */
   const void *excessoro;         /* (0:nxmax-1,0:nymax-1) com_mod.f90:343, read with lsubgrid = 1 (else NULL)   */
-  const void *vdep;              /* c_loc(vdep(0,0,1,n)) from the host's getvdep, required with DRYDEP          */
+  const void *vdep;              /* c_loc(vdep(0,0,1,n)) from the host's getvdep, required with DRYDEP unless
+                                    device_vdep = 1                                                             */
   int32_t lsubgrid;              /* com_mod.f90:117                                                             */
-  int32_t reserved[3];
+  int32_t device_vdep;           /* 1 (with DRYDEP): vdep may be NULL; the slot then stays "not loaded" (fpx_step
+                                    refuses it) until fpx_getvdep of this slot has run.  0: as before            */
+  int32_t reserved[2];
 } fpx_calcpar_in;
 /* optional copies back into the host's arrays of slot n (NULL members are skipped), e.g. c_loc(hmix(0,0,1,n)) */
 typedef struct { void *ustar, *wstar, *oli, *hmix, *tropopause; } fpx_calcpar_out;
 int fpx_calcpar(fpx_handle h, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out);
 /* device time of the kernel of the last fpx_calcpar call, milliseconds */
 int fpx_calcpar_time(fpx_handle h, double *ms);
+/* ---- getvdep on the device: the dry-deposition velocities of calcpar (calcpar.f90:171-189) -----------------
+ * Replaces the DRYDEP block of calcpar -- z0(7) from ustar, rh = ew(td2)/ew(tt2), `call getvdep(..)` (getvdep.f90 with
+ * getrb.f90, getrc.f90, raerod.f90, psih.f90, partdep.f90; the season through caldate.f90) and vdep(ix,jy,i,n) = vd(i) --
+ * for the mother grid.  There is no nest variant: getvdep_nests / vdepn stay the host's and remain an input
+ * (fpx_upload_nest_fields, fpx_verttransform_nest).  The land-use inventory and the resistance tables are read once at
+ * start-up by the host and handed over once; what runs on the device is the per-column arithmetic, in the host's real
+ * kind.  All pointers address host arrays of com_mod in their own shapes and real kind. */
+typedef struct {
+  int32_t numclass, ni, maxspec; /* par_mod.f90:211,225; maxspec is the leading dimension of the species tables  */
+  int32_t reserved;
+  double bdate;                  /* com_mod.f90:45, julian date of the start of the simulation                   */
+  const void *xlanduse;          /* (0:nxmax-1,0:nymax-1,numclass) com_mod.f90:345                               */
+  const void *z0;                /* (numclass) com_mod.f90:572; z0(7) is recomputed per column (calcpar.f90:174) */
+  const void *ri, *rac;          /* (5,numclass) com_mod.f90:179                                                 */
+  const void *rcl, *rgs, *rlu;   /* (maxspec,5,numclass) com_mod.f90:179-180                                     */
+  const void *rm, *reldiff, *henry, *f0, *density, *dryvel;   /* (maxspec) com_mod.f90:175-181                  */
+  const void *vset, *schmi, *fract;                           /* (maxspec,ni) com_mod.f90:178                   */
+} fpx_getvdep_tables;
+/* Once, after fpx_create of a run with DRYDEP; a repeated call replaces the tables. */
+int fpx_getvdep_init(fpx_handle h, const fpx_getvdep_tables *t);
+typedef struct {
+  int32_t wftime;                /* wftime(n) of the slot's wind field, com_mod.f90:276 (the season, getvdep.f90:51)  */
+  int32_t reserved;
+  const void *ssr, *lsprec, *convprec, *sd;   /* required: c_loc(ssr(0,0,1,n)) ..., com_mod.f90:411-421              */
+  const void *ustar, *oli;       /* NULL: the ones fpx_calcpar left on the device for this slot (it must have run for
+                                    this slot last); else the host's, c_loc(ustar(0,0,1,n)) ...                       */
+  const void *ps, *tt2, *td2;    /* NULL: the ones fpx_verttransform_ecmwf uploaded for this slot; else the host's     */
+} fpx_getvdep_in;
+/* Writes the deposition velocities of slot `slot` for the species 1..nspec where fpx_step reads them and, with vdep_out
+ * != NULL, also into the host's planes c_loc(vdep(0,0,1,n)) (nxmax*nymax values per species).  Marks a slot loaded that
+ * fpx_calcpar(device_vdep = 1) left waiting.  Refused without DRYDEP and before fpx_getvdep_init. */
+int fpx_getvdep(fpx_handle h, int32_t slot, const fpx_getvdep_in *g, void *vdep_out);
+/* device time of the kernel of the last fpx_getvdep call, milliseconds */
+int fpx_getvdep_time(fpx_handle h, double *ms);
 /* ---- partoutput: the binary particle dump (SURVEY section 8 f, item 4) ----------------------
  * Replaces `call partoutput(itime)` (timemanager.f90:454; the routine: partoutput.f90:63-190):
  * for every particle with itra1 == itime the device interpolates oro, pv, qv, tt, rho, hmix and
