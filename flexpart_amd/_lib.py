@@ -189,7 +189,7 @@ SYMBOLS = [
     "fpx_step", "fpx_step_async", "fpx_sync", "fpx_counters", "fpx_kernel_time", "fpx_kernel_times", "fpx_sort_particles",
     "fpx_seed_particles", "fpx_stream", "fpx_outgrid_init", "fpx_set_output_times", "fpx_conccalc",
     "fpx_get_grids", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
-    "fpx_wetdepo", "fpx_get_wetgrid", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe",
+    "fpx_wetdepo", "fpx_get_wetgrid", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_find_level_probe",
     "fpx_outgrid_nest_init", "fpx_get_grids_nest", "fpx_receptors_init", "fpx_get_receptors", "fpx_upload_wet_nest_fields",
     "fpx_verttransform_ecmwf", "fpx_verttransform_nest", "fpx_verttransform_time", "fpx_calcpar", "fpx_calcpar_time", "fpx_getvdep_init", "fpx_getvdep", "fpx_getvdep_time", "fpx_upload_diag_fields", "fpx_partoutput", "fpx_partoutput_time", "fpx_readpartpositions", "fpx_concoutput",
     "fpx_checkpoint_write", "fpx_checkpoint_read",
@@ -217,6 +217,7 @@ def load():
     lib.fpx_stream.argtypes = [vp]
     lib.fpx_math_probe.argtypes = [C.c_int32, vp, vp, C.c_int64]
     lib.fpx_hanna_probe.argtypes = [vp, vp, C.c_int64]
+    lib.fpx_find_level_probe.argtypes = [C.c_int32, vp, C.c_int32, vp, vp, C.c_int64, vp, vp]
     lib.fpx_upload_wet_nest_fields.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(FpxWetFields), C.c_int32]
     lib.fpx_outgrid_nest_init.argtypes = [vp, C.POINTER(FpxOutgridNest)]
     lib.fpx_get_grids_nest.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32]

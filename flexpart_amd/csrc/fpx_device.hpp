@@ -774,6 +774,32 @@ FPX_DEV int find_level(const R *hgt, int nz, R zt) {
   return lo - 1;
 }
 
+// find_level started from a guess: the level the lane found in its previous pass (0: none, the plain search).  A particle stays
+// in its level in four passes of five and otherwise moves by one or two, so the guess is tested and walked by at most
+// kLevelWalk levels before the bisection takes over.  k is find_level's answer exactly when
+//   (k == 1 || !(hgt[k-1] > zt)) && (k == nz-1 || hgt[k] > zt)
+// (the heights increase strictly; the comparisons are find_level's own, so a z on a level, below hgt[0], at the clamp under
+// hgt[nz-1] or not a number ends where the bisection ends).  zlo, zhi: hgt[k-1], hgt[k], which the pass reads next.
+constexpr int kLevelWalk = 2;
+template <typename R>
+FPX_DEV int find_level_from(const R *hgt, int nz, R zt, int guess, R &zlo, R &zhi) {
+  if (guess >= 1 && guess <= nz - 1) {
+    int k = guess;
+    R a = hgt[k - 1], b = hgt[k];
+    for (int n = 0;; n++) {
+      const bool down = k > 1 && a > zt;
+      const bool up = !down && k < nz - 1 && !(b > zt);
+      if (!down && !up) { zlo = a; zhi = b; return k; }
+      if (n == kLevelWalk) break;
+      if (down) { k = k - 1; b = a; a = hgt[k - 1]; }
+      else { k = k + 1; a = b; b = hgt[k]; }
+    }
+  }
+  const int k = find_level(hgt, nz, zt);
+  zlo = hgt[k - 1]; zhi = hgt[k];
+  return k;
+}
+
 // ---------------------------------------------------------------------------
 // Hanna turbulence state (hanna_mod.f90:5-6)
 // ---------------------------------------------------------------------------
@@ -917,8 +943,9 @@ FPX_DEV StepInv<R> step_invariants(R h, R ol, R ust, R wst, const MS &M) {
 // hanna() of a Langevin pass: T.ust is the floored ust, the regime and the reciprocals come from the invariants.  In the
 // unstable regime sigu, sigv and 1/tlu = 1/tlv are the invariants themselves (T.tlu, T.tlv are not set: itlu, itlv are).
 // INV: StashInv, the Langevin kernel's view of the invariants in its stash (defined with the stash, below)
+// Returns the regime (1: itlv is itlu and T.sigv is T.sigu, the same values).
 template <typename R, typename INV, typename MS>
-FPX_DEV void hanna(Turb<R> &T, R z, const INV &I, const MS &M, R &itlu, R &itlv) {   // hanna.f90:41-106
+FPX_DEV int hanna(Turb<R> &T, R z, const INV &I, const MS &M, R &itlu, R &itlv) {   // hanna.f90:41-106
   const int regime = I.regime();
   if (regime == 0) {
     R corr = z * I.get_iaux();
@@ -955,6 +982,7 @@ FPX_DEV void hanna(Turb<R> &T, R z, const INV &I, const MS &M, R &itlu, R &itlv)
   }
   T.tlw = m_max(K(30.), T.tlw);
   if (T.dsigwdz == K(0.)) T.dsigwdz = K(1.e-10);
+  return regime;
 }
 
 template <typename R>
@@ -2072,7 +2100,8 @@ FPX_DEV void pbl_begin(const View<R> &V, double xt, double yt, const TimeW<R> &W
 
 // One pass of the loop advance.f90:282-609.  DRYDEP: the time below 2*href is summed in the stash (S_TDEP).
 // indz_last receives the level pair of this pass: when the pass ends the interval (PBL_DONE)
-// the caller evaluates usig/vsig/wsig for it (advance.f90:604-606, level_pair_sigma).
+// the caller evaluates usig/vsig/wsig for it (advance.f90:604-606, level_pair_sigma).  On entry it holds the level of
+// the lane's previous pass (0: none), where the level search starts (find_level_from).
 // TSW / CBLF: -1 = read turbswitch / cblflag at run time, 0/1 = fixed at compile time
 // (specialised hot kernels: fewer scalar registers, no dead branches).  SETTLE/DRYDEP false
 // compile the aerosol paths out.
@@ -2287,16 +2316,16 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
   const R dt = (R)ldt;
   T.zeta = zt / h;
 
-  const int indz = find_level(hgt, V.nz, zt);
-  const int indzp = indz + 1;
+  R zlo, zhi;                                  // height(indz), height(indzp)
+  const int indz = find_level_from(hgt, V.nz, zt, indz_last, zlo, zhi);   // indz_last: the lane's level of its previous pass, or 0
   indz_last = indz;
   R lv[2][5];
   fetch_level_pair(V, F, W, A, S, indz, lv);
 
   // advance.f90:342-350
-  const R dz = m_rcp(hgt[indzp - 1] - hgt[indz - 1]);
-  const R dz1 = (zt - hgt[indz - 1]) * dz;
-  const R dz2 = (hgt[indzp - 1] - zt) * dz;
+  const R dz = m_rcp(zhi - zlo);
+  const R dz1 = (zt - zlo) * dz;
+  const R dz2 = (zhi - zt) * dz;
   {
     // grid-scale wind of this pass and its contribution to the displacement sums (advance.f90:539-540;
     // the sums do not depend on the fine loop, so they are taken here and stay out of registers)
@@ -2319,7 +2348,9 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
   T.ust = S.get(S_UST); T.ol = S.get(S_OL);   // ust as hanna.f90:43 floors it (step_invariants)
   if (!turbswitch) T.wst = RC.wst();          // hanna1 alone reads wst itself: from the particle's record (the stash holds wst*wst for hanna_short)
   R itlu, itlv;
-  if (turbswitch) hanna(T, zt, SI, S, itlu, itlv);
+  const R ih = m_rcp(h);   // ahead of hanna(), whose stable arm takes the same reciprocal (T.h is h): one evaluation serves both
+  int regime_h = -1;   // hanna()'s regime; hanna1 has no twin velocities
+  if (turbswitch) regime_h = hanna(T, zt, SI, S, itlu, itlv);
   else { hanna1(T, zt); S.put(S_UST, T.ust); itlu = m_rcp(T.tlu); itlv = m_rcp(T.tlv); }   // (hanna1.f90:43 floors ust where hanna1 is neutral)
   T.isigw = m_rcp(T.sigw);
 
@@ -2330,20 +2361,25 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
   if (nrand + 1 > V.maxrand) nrand = 1;
   {
     const R g1 = G.at(nrand), g2 = G.at(nrand + 1);
-    const R dttlu = dt * itlu, dttlv = dt * itlv;
+    // up = a*up + g1*sigu*b with (a, b) = (1 - dt/tlu, sqrt(2 dt/tlu)) or (ru, sqrt(1 - ru*ru)), ru = exp(-dt/tlu), and the same
+    // for vp.  In the unstable regime 1/tlv IS 1/tlu (step_invariants), so the pair of factors is the same pair: taken once.
+    auto factors = [&](R dttl, R &a, R &b) {
+      if (dttl < K(.5)) {
+        a = K(1.) - dttl;
+        b = m_sqrtp(K(2.) * dttl);
+      } else {
+        R r = S.expt(-dttl);
+        a = r;
+        b = m_sqrtp(K(1.) - r * r);
+      }
+    };
+    R au, bu, av, bv;
+    factors(dt * itlu, au, bu);
+    if (regime_h == 1) { av = au; bv = bu; }
+    else factors(dt * itlv, av, bv);
     R up = S.get(S_UP), vp = S.get(S_VP);
-    if (dttlu < K(.5)) {
-      up = (K(1.) - dttlu) * up + g1 * T.sigu * m_sqrtp(K(2.) * dttlu);
-    } else {
-      R ru = S.expt(-dttlu);
-      up = ru * up + g1 * T.sigu * m_sqrtp(K(1.) - ru * ru);
-    }
-    if (dttlv < K(.5)) {
-      vp = (K(1.) - dttlv) * vp + g2 * T.sigv * m_sqrtp(K(2.) * dttlv);
-    } else {
-      R rv = S.expt(-dttlv);
-      vp = rv * vp + g2 * T.sigv * m_sqrtp(K(1.) - rv * rv);
-    }
+    up = au * up + g1 * T.sigu * bu;
+    vp = av * vp + g2 * T.sigv * bv;
     if (turboff) { up = K(0.); vp = K(0.); }   // advance.f90:464-467: zeroed in the fine loop, before :541-542 read them
     S.put(S_UP, up); S.put(S_VP, vp);
     S.add(S_DAW, up * dt);   // advance.f90:541-542
@@ -2356,7 +2392,7 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
   const R dtftlw = dtf * m_rcp(T.tlw);
   const bool cbl_on = cblflag && SI.deep();
   const R sqrt_dtf = m_sqrtp(dtf);
-  const HsInv<R> HI{m_rcp(h), SI.get_iaux(), SI.regime()};
+  const HsInv<R> HI{ih, SI.get_iaux(), SI.regime()};
 
   // vertical Langevin, ifine sub-steps, advance.f90:396-498
   FPX_LANES(st, 0);

@@ -611,7 +611,8 @@ __device__ __forceinline__ void prep_body(const View<R> &V, const GridP<R> &Gp, 
       r.v[8] = I.ust; r.v[kRecWst] = B.wst; r.v[10] = B.ol; r.v[11] = B.transition;
       r.v[12] = A.h;
       r.v[0] = I.iaux; r.v[1] = I.sigu; r.v[2] = inv_pack_itlu(I);   // as the Langevin kernel's stash holds them (StashInv)
-      r.i[0] = A.nrand; r.i[2] = pbl_pack(PBL_FRESH, 1, 0, A.ngrid, 0);
+      // (the level of the particle's height travels with it: the Langevin kernel's first level search starts there, find_level_from)
+      r.i[0] = A.nrand; r.i[2] = pbl_pack(PBL_FRESH, 1, find_level(hgt, V.nz, ps.zt), A.ngrid, 0);
     }
     // Regime class of the particle's PBL passes (hanna.f90:42,59,91 and advance.f90:405-406).  The
     // work list is the slots stably sorted by this 3-bit key: class by class, each class in slot
@@ -1402,6 +1403,7 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
   R zt = 0, wp = 0;
   int ldt = 0;
   short icbt = 1;
+  int lvl = 0;                       // the level of the lane's last pass, where the next pass starts its level search (find_level_from); 0: none
   LoopCtx<R> A;
 
   // the lanes of `who` (all of them hold a particle) hand their particles on: record written, slot appended to the next
@@ -1422,7 +1424,7 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
   auto suspend = [&](bool mine_goes) {   // convergent: every lane of the wave calls it
     const unsigned long long sm = __ballot(mine_goes);
     if (sm == 0ull) return;
-    if (mine_goes) { write_record(PBL_CONTINUE, 1); have = false; }
+    if (mine_goes) { write_record(PBL_CONTINUE, lvl); have = false; }
     unsigned int base = 0;
     if (lane == 0) base = atomicAdd(next_cnt + wcls, (unsigned int)__popcll(sm));
     base = __builtin_amdgcn_readfirstlane(base);
@@ -1526,6 +1528,7 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
           zt = resumed ? c_zt : l_zt; wp = resumed ? c_wp : l_wp;
           ldt = resumed ? r_ldt : l_idt;
           icbt = resumed ? (short)pbl_icbt(r_pk) : l_cbt;
+          lvl = pbl_indz(r_pk);   // k_prep's level of the particle's height (FRESH), or that of its last pass (CONTINUE): a guess, tested before use
           {
             R ddx, ddy;
             adv_begin_known(V, xt, yt, pbl_ngrid(r_pk), r_h, A, ddx, ddy);
@@ -1571,15 +1574,14 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
     if (have) {
       Rng<R, RNGM> G;
       make_rng(V, pid, step, G);
-      int indz = 1;
-      const int rc = pbl_pass<R, !LEAN, !LEAN, TSW, CBLF>(V, hgt, G, W, itime, xt, yt, zt, wp, ldt, icbt, A, S, indz, st, RecCold<R>{Q.rec[0].v, s});
+      const int rc = pbl_pass<R, !LEAN, !LEAN, TSW, CBLF>(V, hgt, G, W, itime, xt, yt, zt, wp, ldt, icbt, A, S, lvl, st, RecCold<R>{Q.rec[0].v, s});
       R npass = (R)0;
       if (SUSP) { npass = S.get(S_NPASS) + (R)1; S.put(S_NPASS, npass); }
       if (rc != PBL_CONTINUE) {
         FPX_LANES(st, 9);
         // the particle's state at the end of its last pass goes into its hand-over record: one contiguous line;
         // k_pbl_finish writes the particle arrays from it
-        write_record(rc, indz);
+        write_record(rc, lvl);
         have = false;
       } else over_budget = SUSP && npass >= cap_r;
     }
@@ -1654,6 +1656,25 @@ __global__ void __launch_bounds__(kBlock) k_hanna_probe(int which, const double 
     o[0] = T.sigu; o[1] = T.sigv; o[2] = T.sigw; o[3] = T.dsigwdz; o[4] = m_rcp(T.tlu); o[5] = m_rcp(T.tlv); o[6] = T.tlw;
     o[7] = T.ust; o[8] = h / m_abs(ol) < 1. ? 0. : ol < 0. ? 1. : 2.; o[9] = deep ? 1. : 0.;
   }
+}
+
+// diagnostics (fpx_find_level_probe): the level search of a Langevin pass on plain arrays, the height column in LDS as in k_pbl_loop.
+// which = 0: find_level_from with the point's guess (0: none); which = 1: find_level and the two heights the pass read after it.
+// One launch per form.  idx[i] = the level, zz[2i], zz[2i+1] = height(indz), height(indz+1).
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_find_level_probe(int which, const R *__restrict__ height, int nz, const R *__restrict__ z,
+                                                            const int *__restrict__ guess, long long n, int *__restrict__ idx, R *__restrict__ zz) {
+  __shared__ R hgt[kMaxNz];
+  for (int k = threadIdx.x; k < nz; k += blockDim.x) hgt[k] = height[k];
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const R zt = z[i];
+  R zlo, zhi;
+  int k;
+  if (which == 0) k = find_level_from(hgt, nz, zt, guess[i], zlo, zhi);
+  else { k = find_level(hgt, nz, zt); zlo = hgt[k - 1]; zhi = hgt[k]; }
+  idx[i] = k; zz[2 * i] = zlo; zz[2 * i + 1] = zhi;
 }
 
 // completion of ONE boundary-layer particle: label 700 if it left the PBL, sigmas for the mesoscale term, label 99 to the end
@@ -5860,6 +5881,38 @@ int fpx_hanna_probe(const double *in, double *out, int64_t n) {
   }
   (void)hipFree(dx); (void)hipFree(dy);
   return e == hipSuccess ? FPX_OK : FPX_ERR_DEVICE;
+}
+
+}  // extern "C"
+template <typename R>
+static int find_level_probe(const R *height, int32_t nz, const R *z, const int32_t *guess, int64_t n, int32_t *idx, R *zz) {
+  R *dh = nullptr, *dz = nullptr, *dzz = nullptr;
+  int *dg = nullptr, *di = nullptr;
+  hipError_t e = hipMalloc(&dh, nz * sizeof(R));
+  if (e == hipSuccess) e = hipMalloc(&dz, n * sizeof(R));
+  if (e == hipSuccess) e = hipMalloc(&dg, n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&di, n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&dzz, 2 * n * sizeof(R));
+  const bool nomem = e != hipSuccess;
+  if (e == hipSuccess) e = hipMemcpy(dh, height, nz * sizeof(R), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dz, z, n * sizeof(R), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dg, guess, n * sizeof(int), hipMemcpyHostToDevice);
+  for (int which = 0; which < 2 && e == hipSuccess; which++) {   // all points of the search from the guess, then all of the plain one
+    fpx::k_find_level_probe<R><<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(which, dh, nz, dz, dg, n, di, dzz);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(idx + n * which, di, n * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(zz + 2 * n * which, dzz, 2 * n * sizeof(R), hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dh); (void)hipFree(dz); (void)hipFree(dg); (void)hipFree(di); (void)hipFree(dzz);
+  return e == hipSuccess ? FPX_OK : nomem ? FPX_ERR_NOMEM : FPX_ERR_DEVICE;
+}
+
+extern "C" {
+int fpx_find_level_probe(int32_t real_bytes, const void *height, int32_t nz, const void *z, const int32_t *guess, int64_t n, int32_t *idx, void *zz) {
+  if ((real_bytes != 4 && real_bytes != 8) || !height || nz < 2 || nz > fpx::kMaxNz || !z || !guess || !idx || !zz || n < 0) return FPX_ERR_ARG;
+  if (n == 0) return FPX_OK;
+  if (real_bytes == 8) return find_level_probe<double>((const double *)height, nz, (const double *)z, guess, n, idx, (double *)zz);
+  return find_level_probe<float>((const float *)height, nz, (const float *)z, guess, n, idx, (float *)zz);
 }
 
 }  // extern "C"

@@ -690,6 +690,12 @@ int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n);
  * -h/ol > 5 (0/1) -- computed the way the engine does, from the step's invariants as k_prep takes them and the Langevin kernel's
  * stash holds them (out[10i..10i+9]), and by the plain form (out[10n + 10i ..]).  The two halves must agree in every bit. */
 int fpx_hanna_probe(const double *in, double *out, int64_t n);
+/* Diagnostics: the level search of a Langevin pass for n heights z[i] in the column height[0..nz-1] (2 <= nz, strictly increasing;
+ * real_bytes 4 or 8 is the type of height, z and zz), started from guess[i] -- the level of the lane's previous pass, 1..nz-1, or
+ * 0 for none (any other value counts as none) -- and the plain bisection.  idx[i], zz[2i], zz[2i+1] = the level indz and
+ * height(indz), height(indz+1) of the search from the guess; idx[n+i], zz[2n+2i], zz[2n+2i+1] those of the plain one.  The two
+ * halves must agree in every bit. */
+int fpx_find_level_probe(int32_t real_bytes, const void *height, int32_t nz, const void *z, const int32_t *guess, int64_t n, int32_t *idx, void *zz);
 /* Diagnostics of a library built with -DFPX_LANE_STATS (all zeros otherwise): for code region r of the Langevin kernel
  * out[2r] = how many times a wave executed it, out[2r+1] = the lanes that were active, summed.  Regions: 0 a pass,
  * 1 a fine sub-step, 2 its CBL branch, 3 the Gaussian branch under cblflag, 4 the exponential-form branch, 5/6/7 hanna_short
