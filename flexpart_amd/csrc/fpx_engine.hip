@@ -24,6 +24,7 @@
 #include "fpx_verttransform.hpp"
 #include "fpx_calcpar.hpp"
 #include "fpx_getvdep.hpp"
+#include "fpx_calcpv.hpp"
 #include "fpx_convect.hpp"
 #include "fpx_rng_host.hpp"
 
@@ -2024,6 +2025,9 @@ struct EngineBase {
   virtual int getvdep_init(const fpx_getvdep_tables *t) = 0;
   virtual int getvdep(int slot, const fpx_getvdep_in *g, void *vdep_out) = 0;
   virtual double gv_ms() = 0;
+  virtual int calcpv_init(const fpx_calcpv_cfg *c) = 0;
+  virtual int get_pvh(int nest, void *pvh_out) = 0;
+  virtual double pv_ms() = 0;
   virtual int set_windtime(const int32_t mt[2], const int32_t mi[2]) = 0;
   virtual int rng_fill_table() = 0;
   virtual int rng_set_table(const void *t, int n) = 0;
@@ -2656,6 +2660,7 @@ struct Engine : EngineBase {
     }
     const void *src[13] = {m->uuh, m->vvh, m->pvh, m->wwh, m->tth, m->qvh, m->ps, m->tt2, m->td2, m->akz, m->bkz, m->aknew, m->bknew};
     for (int i = 0; i < 13; i++) {
+      if (i == PVH && !m->pvh) continue;                                  // computed below, on the device
       const size_t n = (i >= PS && i <= TD2) ? n2 : (i >= AKZ) ? (size_t)nz : n3;
       if (m->pin_host && n >= n2) pin_host_range(src[i], n * sizeof(H));
       HIPCHK(hipMemcpyAsync(D(i), src[i], n * sizeof(H), hipMemcpyHostToDevice, stream));
@@ -2678,6 +2683,25 @@ struct Engine : EngineBase {
     for (int i = 0; i < 9; i++) { G.northpolemap[i] = (H)cfg.northpolemap[i]; G.southpolemap[i] = (H)cfg.southpolemap[i]; }
     vt::In<H> I{D(UUH), D(VVH), D(PVH), D(WWH), D(TTH), D(QVH), D(PS), D(TT2), D(TD2), D(AKZ), D(BKZ), D(AKN), D(BKN), D(HGT)};
     vt::Out<H> O{D(UU), D(VV), D(WW), D(TT), D(QV), D(PV), D(RHO), D(DRHO), D(UPOL), D(VPOL), D(UVZ), D(WZ), D(RHOH), D(PINM)};
+    // pvh = NULL: calcpv.f90 / calcpv_nests.f90 on the arrays just uploaded, into D(PVH), under an event pair of its own.
+    // ppml and theta go to UVZ and WZ, which the transform below overwrites anyway.
+    hipEvent_t p0 = nullptr, p1 = nullptr;
+    if (!m->pvh) {
+      pv::Args<H> P;
+      P.nx = gnx; P.ny = gny; P.nuvz = m->nuvz; P.nxmax = gnxmax; P.nymax = gnymax;
+      P.xglobal = nest ? 0 : cfg.xglobal; P.nglobal = nest ? 0 : cfg.nglobal; P.sglobal = nest ? 0 : cfg.sglobal;
+      P.dx = nest ? (H)pv_dxn[nest - 1] : (H)cfg.dx; P.dy = G.dy; P.ylat0 = G.ylat0;
+      P.uuh = D(UUH); P.vvh = D(VVH); P.tth = D(TTH); P.ps = D(PS); P.akz = D(AKZ); P.bkz = D(BKZ);
+      P.ppml = D(UVZ); P.theta = D(WZ); P.pvh = D(PVH);
+      HIPCHK(hipEventCreate(&p0)); HIPCHK(hipEventCreate(&p1));
+      HIPCHK(hipEventRecord(p0, stream));
+      const dim3 gp((gnx * gny + 255) / 256, m->nuvz);
+      pv::k_theta<H><<<gp, 256, 0, stream>>>(P);
+      pv::k_pv<H><<<gp, 256, 0, stream>>>(P);
+      if (P.nglobal || P.sglobal) pv::k_pole<H><<<dim3((m->nuvz + 63) / 64, 2), 64, 0, stream>>>(P);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(p1, stream));
+    }
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     HIPCHK(hipEventRecord(e0, stream));
@@ -2757,12 +2781,42 @@ struct Engine : EngineBase {
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     vt_last_ms = ms;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    pv_last_ms = 0;
+    if (p0) {
+      HIPCHK(hipEventElapsedTime(&ms, p0, p1));
+      pv_last_ms = ms;
+      (void)hipEventDestroy(p0); (void)hipEventDestroy(p1);
+    }
+    pvh_on_device[nest] = true;
     // without sfc the slot's 2-D fields are still those of the previous wind field until fpx_calcpar has run: not loaded
     if (nest) nest_loaded[nest - 1][s] = true; else { slot_loaded[s] = sfc != nullptr; vdep_pending[s] = false; }
     if (!nest) vt_slot_on_device = slot;      // whose model-level arrays the buffers hold (fpx_calcpar)
     return 0;
   }
   int vt_slot_on_device = 0;
+
+  // ---- calcpv / calcpv_nests on the device (fpx_calcpv.hpp; launched by verttransform_t when pvh = NULL) ----------
+  double pv_dxn[kMaxNests] = {};       // com_mod's dxn(l): calcpv_nests.f90:168,171 divides by it (dx/xresoln need not round to it)
+  bool pv_ready = false;
+  bool pvh_on_device[1 + kMaxNests] = {};
+  double pv_last_ms = 0;
+  int calcpv_init(const fpx_calcpv_cfg *c) override {
+    if (!c || c->struct_bytes != (int32_t)sizeof(fpx_calcpv_cfg)) return fail(FPX_ERR_ARG, "calcpv_init: null or fpx_calcpv_cfg size mismatch (ABI)");
+    for (int l = 0; l < kMaxNests; l++) pv_dxn[l] = c->dxn[l];
+    pv_ready = true;
+    return 0;
+  }
+  int get_pvh(int nest, void *pvh_out) override {
+    if (nest < 0 || nest > V.numbnests) return fail(FPX_ERR_ARG, "get_pvh: nest out of range (0 = the mother grid)");
+    if (!pvh_out) return fail(FPX_ERR_ARG, "get_pvh: null");
+    if (!vt_set_ready[nest] || !pvh_on_device[nest]) return fail(FPX_ERR_STATE, "get_pvh: no transform of this grid has run yet");
+    const HostGrid HG = host_grid(nest);
+    const size_t bytes = (size_t)HG.nxmax * HG.nymax * cfg.nz * cfg.host_real_bytes;
+    HIPCHK(hipMemcpyAsync(pvh_out, vt_sets[nest][2], bytes, hipMemcpyDeviceToHost, stream));   // [2]: PVH of verttransform_t
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  double pv_ms() override { return pv_last_ms; }
 
   // ---- calcpar on the device ----------------------------------------------------------
   template <typename H>
@@ -3020,24 +3074,30 @@ struct Engine : EngineBase {
 
   int verttransform(int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) override {
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "verttransform: slot must be 1 or 2");
-    if (!m || !m->uuh || !m->vvh || !m->pvh || !m->wwh || !m->tth || !m->qvh || !m->ps || !m->tt2 || !m->td2 || !m->akz || !m->bkz || !m->aknew || !m->bknew)
-      return fail(FPX_ERR_ARG, "verttransform: uuh, vvh, pvh, wwh, tth, qvh, ps, tt2, td2, akz, bkz, aknew, bknew are required");
+    if (!m || !m->uuh || !m->vvh || !m->wwh || !m->tth || !m->qvh || !m->ps || !m->tt2 || !m->td2 || !m->akz || !m->bkz || !m->aknew || !m->bknew)
+      return fail(FPX_ERR_ARG, "verttransform: uuh, vvh, wwh, tth, qvh, ps, tt2, td2, akz, bkz, aknew, bknew are required (pvh = NULL: calcpv on the device)");
     if (m->nuvz != cfg.nz || m->nwz != cfg.nz) return fail(FPX_ERR_ARG, "verttransform: nuvz = nwz = nz expected (gridcheck_ecmwf.f90 sets them equal)");
     if (cfg.nz < 3 || cfg.nz > 65535 || cfg.ny > 65535) return fail(FPX_ERR_ARG, "verttransform: 3 <= nz <= 65535, ny <= 65535");
     if (sfc && (!sfc->hmix || !sfc->ustar || !sfc->wstar || !sfc->oli || !sfc->tropopause)) return fail(FPX_ERR_ARG, "verttransform: the 2-D fields hmix, ustar, wstar, oli, tropopause are required (or sfc = NULL and fpx_calcpar)");
     if (sfc && cfg.drydep && !sfc->vdep) return fail(FPX_ERR_ARG, "verttransform: vdep required with DRYDEP");
+    if (!m->pvh && (cfg.nx < 3 || cfg.ny < 4)) return fail(FPX_ERR_ARG, "verttransform: calcpv on the device (pvh = NULL) needs nx >= 3, ny >= 4");
     return cfg.host_real_bytes == 4 ? verttransform_t<float>(0, slot, m, sfc, out) : verttransform_t<double>(0, slot, m, sfc, out);
   }
   int verttransform_nest(int nest, int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) override {
     if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "verttransform_nest: nest out of range (fpx_nests_init first)");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "verttransform_nest: slot must be 1 or 2");
     if (!height_set) return fail(FPX_ERR_STATE, "verttransform_nest: the z levels come from the mother grid's first transform (or fpx_set_height)");
-    if (!m || !m->uuh || !m->vvh || !m->pvh || !m->wwh || !m->tth || !m->qvh || !m->ps || !m->tt2 || !m->td2 || !m->akz || !m->bkz || !m->aknew || !m->bknew)
-      return fail(FPX_ERR_ARG, "verttransform_nest: uuhn, vvhn, pvhn, wwhn, tthn, qvhn, psn, tt2n, td2n, akz, bkz, aknew, bknew are required");
+    if (!m || !m->uuh || !m->vvh || !m->wwh || !m->tth || !m->qvh || !m->ps || !m->tt2 || !m->td2 || !m->akz || !m->bkz || !m->aknew || !m->bknew)
+      return fail(FPX_ERR_ARG, "verttransform_nest: uuhn, vvhn, wwhn, tthn, qvhn, psn, tt2n, td2n, akz, bkz, aknew, bknew are required (pvhn = NULL: calcpv_nests on the device)");
     if (m->nuvz != cfg.nz || m->nwz != cfg.nz) return fail(FPX_ERR_ARG, "verttransform_nest: nuvz = nwz = nz expected");
     if (!(m->nest_dy > 0)) return fail(FPX_ERR_ARG, "verttransform_nest: nest_dy (dyn) and nest_ylat0 (ylat0n) of fpx_model_levels are required");
     if (!sfc || !sfc->hmix || !sfc->ustar || !sfc->wstar || !sfc->oli || !sfc->tropopause) return fail(FPX_ERR_ARG, "verttransform_nest: hmixn, ustarn, wstarn, olin, tropopausen are required");
     if (cfg.drydep && !sfc->vdep) return fail(FPX_ERR_ARG, "verttransform_nest: vdepn required with DRYDEP");
+    if (!m->pvh) {
+      if (!pv_ready) return fail(FPX_ERR_STATE, "verttransform_nest: fpx_calcpv_init first (dxn of the nests) to compute pvhn on the device");
+      if (!(pv_dxn[nest - 1] > 0)) return fail(FPX_ERR_ARG, "verttransform_nest: dxn of this nest (fpx_calcpv_init) must be positive");
+      if (h_nest[nest - 1].nx < 3 || h_nest[nest - 1].ny < 4) return fail(FPX_ERR_ARG, "verttransform_nest: calcpv_nests on the device (pvhn = NULL) needs nxn >= 3, nyn >= 4");
+    }
     return cfg.host_real_bytes == 4 ? verttransform_t<float>(nest, slot, m, sfc, out) : verttransform_t<double>(nest, slot, m, sfc, out);
   }
 
@@ -5724,6 +5784,9 @@ int fpx_partoutput_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) retur
 int fpx_calcpar(fpx_handle h, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) { FPX_GUARD(h); return h->impl->calcpar(slot, c, out); }
 int fpx_getvdep_init(fpx_handle h, const fpx_getvdep_tables *t) { FPX_GUARD(h); return h->impl->getvdep_init(t); }
 int fpx_getvdep(fpx_handle h, int32_t slot, const fpx_getvdep_in *g, void *vdep_out) { FPX_GUARD(h); return h->impl->getvdep(slot, g, vdep_out); }
+int fpx_calcpv_init(fpx_handle h, const fpx_calcpv_cfg *c) { FPX_GUARD(h); return h->impl->calcpv_init(c); }
+int fpx_get_pvh(fpx_handle h, int32_t nest, void *pvh_out) { FPX_GUARD(h); return h->impl->get_pvh(nest, pvh_out); }
+int fpx_calcpv_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_calcpv_time: null"); *ms = h->impl->pv_ms(); return FPX_OK; }
 int fpx_getvdep_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_getvdep_time: null"); *ms = h->impl->gv_ms(); return FPX_OK; }
 int fpx_calcpar_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_calcpar_time: null"); *ms = h->impl->cp_ms(); return FPX_OK; }
 int fpx_verttransform_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_verttransform_time: null"); *ms = h->impl->vt_ms(); return FPX_OK; }

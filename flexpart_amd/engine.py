@@ -51,6 +51,7 @@ class Engine:
         self.nx, self.ny, self.nz = nx, ny, nz
         self.nxmax, self.nymax, self.nzmax = nx + pad[0], ny + pad[1], nz + pad[2]
         self.nest_pad = (int(nest_pad[0]), int(nest_pad[1]))
+        self._nest_extent = (0, 0)                      # nxn, nyn of nest 1 once init_nest has run
         dx, dy, xlon0, ylat0 = (float(v) for v in sc["geom"])
         xg, ng, sg = (int(v) for v in sc["globalflags"])
         nspec = int(sc["nspec"])
@@ -180,18 +181,21 @@ class Engine:
         self.set_windtime(sc["memtime"], sc["memind"])
 
     def verttransform(self, slot, m, sfc, *, init=False, want=("uu", "vv", "ww", "tt", "qv", "pv", "rho", "drhodz", "uupol", "vvpol"),
-                      host_arrays=None, nest=None):
+                      host_arrays=None, nest=None, device_pv=False):
         """fpx_verttransform_ecmwf: m = synthetic.model_levels() dict (compact [nz][ny][nx] arrays),
         sfc = dict of compact 2-D fields (hmix, ustar, wstar, oli, tropopause[, vdep]) for this slot.
+        device_pv: pvh = NULL, the potential vorticity is computed on the device (calcpv / calcpv_nests); m needs no pvh.
         Returns the z-level arrays asked for (compact), height and nmixz."""
         from ._lib import FpxModelLevels, FpxFieldsOut
         rt = self.hreal
         if nest is not None:      # m is the nest's input (synthetic.nest_model_levels): fpx_verttransform_nest, nest 1
-            return self._verttransform_nest(slot, m, sfc, want)
+            return self._verttransform_nest(slot, m, sfc, want, device_pv)
         keep = {} if host_arrays is None else host_arrays     # host_arrays: a dict the caller keeps alive -> arrays stay put and are pinned
         ml = FpxModelLevels()
         ml.pin_host = 0 if host_arrays is None else 1
         for k in ("uuh", "vvh", "pvh", "wwh", "tth", "qvh"):
+            if k == "pvh" and device_pv:
+                continue
             if k not in keep:
                 keep[k] = np.zeros((self.nzmax, self.nymax, self.nxmax), rt)
             keep[k][: self.nz, : self.ny, : self.nx] = m[k]
@@ -239,8 +243,31 @@ class Engine:
         ms = C.c_double(0)
         check(self.lib.fpx_verttransform_time(self.h, C.byref(ms)), "fpx_verttransform_time")
         out["device_ms"] = ms.value
+        check(self.lib.fpx_calcpv_time(self.h, C.byref(ms)), "fpx_calcpv_time")
+        out["calcpv_ms"] = ms.value
         out["call_ms"] = call_s * 1e3
         return out
+
+    def calcpv_init(self, dxn):
+        """fpx_calcpv_init: dxn = com_mod's dxn(1:numbnests), for verttransform(.., nest=.., device_pv=True)."""
+        from ._lib import FpxCalcpvCfg
+        c = FpxCalcpvCfg()
+        c.struct_bytes = C.sizeof(FpxCalcpvCfg)
+        for i, v in enumerate(np.atleast_1d(np.asarray(dxn, dtype=np.float64))):
+            c.dxn[i] = float(self.hreal(v))
+        check(self.lib.fpx_calcpv_init(self.h, C.byref(c)), "fpx_calcpv_init")
+
+    def get_pvh(self, nest=None, padded=False):
+        """fpx_get_pvh: the model-level PV of the last transform of the mother grid (nest=None) or of nest 1, compact
+        [nz][ny][nx] (padded: the whole host-shaped array as copied, strides nxmax, nymax or nxmaxn, nymaxn)."""
+        if nest is None:
+            shape, nx, ny, g = (self.nzmax, self.nymax, self.nxmax), self.nx, self.ny, 0
+        else:
+            nxn, nyn = self._nest_extent
+            shape, nx, ny, g = (self.nzmax, nyn + self.nest_pad[1], nxn + self.nest_pad[0]), nxn, nyn, 1
+        out = np.zeros(shape, self.hreal)
+        check(self.lib.fpx_get_pvh(self.h, g, _vp(out)), "fpx_get_pvh")
+        return out if padded else out[: self.nz, :ny, :nx].astype(np.float64)
 
     def calcpar(self, slot, cin, vdep=None, device_vdep=False):
         """fpx_calcpar after verttransform(slot, m, None): cin = synthetic.calcpar_inputs(m).  Returns the five 2-D fields
@@ -319,13 +346,15 @@ class Engine:
         check(self.lib.fpx_getvdep_time(self.h, C.byref(ms)), "fpx_getvdep_time")
         return dict(vdep=out[:, : self.ny, : self.nx].astype(np.float64), device_ms=ms.value, call_ms=call_s * 1e3)
 
-    def _verttransform_nest(self, slot, n, sfc, want):
+    def _verttransform_nest(self, slot, n, sfc, want, device_pv=False):
         from ._lib import FpxModelLevels, FpxFieldsOut
         rt = self.hreal
         nxn, nyn = int(n["grid"][0]), int(n["grid"][1])
         keep = {}
         ml = FpxModelLevels()
         for k in ("uuh", "vvh", "pvh", "wwh", "tth", "qvh"):
+            if k == "pvh" and device_pv:
+                continue
             keep[k] = self._nest_host(n[k], nlev=self.nzmax)
             setattr(ml, k, keep[k].ctypes.data)
         for k in ("ps", "tt2", "td2"):
@@ -519,6 +548,7 @@ class Engine:
         """fpx_nests_init for one nested grid: geometry as gridcheck_nests.f90:359-372 derives it."""
         rt = self.hreal
         nxn, nyn = (int(v) for v in nest)
+        self._nest_extent = (nxn, nyn)
         dxn, dyn, xlon0n, ylat0n = (rt(v) for v in nestgeom)
         dx, dy, xlon0, ylat0 = (rt(self.cfg.dx), rt(self.cfg.dy), rt(self.cfg.xlon0), rt(self.cfg.ylat0))
         n = FpxNests()

@@ -150,6 +150,10 @@ module flexgpu_mod
     type(c_ptr) :: ssr, lsprec, convprec, sd
     type(c_ptr) :: ustar, oli, ps, tt2, td2
   end type fpx_getvdep_in
+  type, bind(C) :: fpx_calcpv_cfg
+    integer(c_int32_t) :: struct_bytes, reserved
+    real(c_double) :: dxn(4)
+  end type fpx_calcpv_cfg
   type, bind(C) :: fpx_calcpar_out
     type(c_ptr) :: ustar, wstar, oli, hmix, tropopause
   end type fpx_calcpar_out
@@ -206,6 +210,22 @@ module flexgpu_mod
       integer(c_int32_t), value :: slot
       type(fpx_getvdep_in), intent(in) :: g
       type(c_ptr), value :: vdep_out
+    end function
+    integer(c_int) function fpx_calcpv_init(h, c) bind(C, name='fpx_calcpv_init')
+      import :: c_ptr, c_int, fpx_calcpv_cfg
+      type(c_ptr), value :: h
+      type(fpx_calcpv_cfg), intent(in) :: c
+    end function
+    integer(c_int) function fpx_get_pvh(h, nest, pvh_out) bind(C, name='fpx_get_pvh')
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: nest
+      type(c_ptr), value :: pvh_out
+    end function
+    integer(c_int) function fpx_calcpv_time(h, ms) bind(C, name='fpx_calcpv_time')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: ms
     end function
     integer(c_int) function fpx_release_init(h, r) bind(C, name='fpx_release_init')
       import :: c_ptr, c_int, fpx_release
@@ -702,12 +722,14 @@ contains
   ! cloud diagnostics); height(:) and nmixz are set on the first call as the reference does.
   ! pin_host = .true.: uuh ... td2 keep their addresses for the whole run (static arrays): registered once for DMA.
   ! device_calcpar = .true.: the 2-D fields of calcpar are not taken from com_mod; flexgpu_calcpar(n, ierr) computes them.
-  subroutine flexgpu_verttransform(n, uuh, vvh, wwh, pvh, ierr, writeback, pin_host, device_calcpar)
+  ! device_pv = .true.: pvh is not read; the device computes it from uuh, vvh, tth, ps (calcpv.f90, which calcpar.f90:270
+  ! calls) before the transform -- the host drops that call; flexgpu_get_pvh copies the array back if something needs it.
+  subroutine flexgpu_verttransform(n, uuh, vvh, wwh, pvh, ierr, writeback, pin_host, device_calcpar, device_pv)
     integer, intent(in) :: n
     real, intent(in) :: uuh(0:nxmax-1,0:nymax-1,nuvzmax), vvh(0:nxmax-1,0:nymax-1,nuvzmax)
     real, intent(in) :: pvh(0:nxmax-1,0:nymax-1,nuvzmax), wwh(0:nxmax-1,0:nymax-1,nwzmax)
     integer, intent(out) :: ierr
-    logical, intent(in), optional :: writeback, pin_host, device_calcpar
+    logical, intent(in), optional :: writeback, pin_host, device_calcpar, device_pv
     logical, save :: first = .true.
     type(fpx_model_levels) :: m
     type(fpx_fields), target :: f
@@ -723,6 +745,9 @@ contains
     m%nuvz = nuvz; m%nwz = nwz; m%init = merge(1, 0, first)
     m%pin_host = 0; if (present(pin_host)) m%pin_host = merge(1, 0, pin_host)
     m%nest_dy = 0; m%nest_ylat0 = 0
+    if (present(device_pv)) then
+      if (device_pv) m%pvh = c_null_ptr
+    end if
     f%uu = c_null_ptr; f%vv = c_null_ptr; f%ww = c_null_ptr; f%uupol = c_null_ptr; f%vvpol = c_null_ptr
     f%rho = c_null_ptr; f%drhodz = c_null_ptr; f%tt = c_null_ptr
     f%hmix = loc_r(hmix(0,0,1,n)); f%ustar = loc_r(ustar(0,0,1,n)); f%wstar = loc_r(wstar(0,0,1,n))
@@ -750,6 +775,13 @@ contains
     nmixz = nmixz_c
     first = .false.
   end subroutine flexgpu_verttransform
+
+  ! The model-level PV the last flexgpu_verttransform read -- the device's own after device_pv = .true. -- into pvh.
+  subroutine flexgpu_get_pvh(pvh, ierr)
+    real, intent(out) :: pvh(0:nxmax-1,0:nymax-1,nuvzmax)
+    integer, intent(out) :: ierr
+    ierr = fpx_get_pvh(flexgpu_handle, 0_c_int32_t, loc_r(pvh))
+  end subroutine flexgpu_get_pvh
 
   ! oro (slot = 0) or pv, qv, tt of one time slot: the fields only partoutput reads.  Not needed for
   ! slots that went through flexgpu_verttransform (the device keeps its own pv, qv, tt then).
@@ -1016,18 +1048,20 @@ contains
 
   ! Replaces `call verttransform_nests(n,uuhn,vvhn,wwhn,pvhn)` (getfields.f90:133,168,184) and the upload of slot n of
   ! every nest; writeback as in flexgpu_verttransform (uun ... drhodzn of slot n).
-  subroutine flexgpu_verttransform_nests(n, uuhn, vvhn, wwhn, pvhn, ierr, writeback)
+  ! device_pv = .true.: pvhn is not read; the device computes it (calcpv_nests.f90) -- flexgpu_calcpv_init first.
+  subroutine flexgpu_verttransform_nests(n, uuhn, vvhn, wwhn, pvhn, ierr, writeback, device_pv)
     integer, intent(in) :: n
     real, intent(in) :: uuhn(0:nxmaxn-1,0:nymaxn-1,nuvzmax,maxnests), vvhn(0:nxmaxn-1,0:nymaxn-1,nuvzmax,maxnests)
     real, intent(in) :: pvhn(0:nxmaxn-1,0:nymaxn-1,nuvzmax,maxnests), wwhn(0:nxmaxn-1,0:nymaxn-1,nwzmax,maxnests)
     integer, intent(out) :: ierr
-    logical, intent(in), optional :: writeback
+    logical, intent(in), optional :: writeback, device_pv
     type(fpx_model_levels) :: m
     type(fpx_fields) :: f
     type(fpx_fields_out) :: o
     integer :: l
-    logical :: wb
+    logical :: wb, dpv
     wb = .true.; if (present(writeback)) wb = writeback
+    dpv = .false.; if (present(device_pv)) dpv = device_pv
     ierr = 0
     do l = 1, numbnests
       m%uuh = loc_r(uuhn(0:,0,1,l)); m%vvh = loc_r(vvhn(0:,0,1,l)); m%pvh = loc_r(pvhn(0:,0,1,l)); m%wwh = loc_r(wwhn(0:,0,1,l))
@@ -1036,6 +1070,7 @@ contains
       m%akz = loc_r(akz); m%bkz = loc_r(bkz); m%aknew = loc_r(aknew); m%bknew = loc_r(bknew)
       m%nuvz = nuvz; m%nwz = nwz; m%init = 0; m%pin_host = 0
       m%nest_dy = dyn(l); m%nest_ylat0 = ylat0n(l)
+      if (dpv) m%pvh = c_null_ptr
       f%uu = c_null_ptr; f%vv = c_null_ptr; f%ww = c_null_ptr; f%uupol = c_null_ptr; f%vvpol = c_null_ptr
       f%rho = c_null_ptr; f%drhodz = c_null_ptr; f%tt = c_null_ptr
       f%hmix = loc_r(hmixn(0:,0,1,n,l)); f%ustar = loc_r(ustarn(0:,0,1,n,l)); f%wstar = loc_r(wstarn(0:,0,1,n,l))
@@ -1053,6 +1088,31 @@ contains
       if (ierr /= 0) return
     end do
   end subroutine flexgpu_verttransform_nests
+
+  ! once, after gridcheck_nests and flexgpu_nests_init: com_mod's dxn, which calcpv_nests.f90:168,171 divides by
+  subroutine flexgpu_calcpv_init(ierr)
+    integer, intent(out) :: ierr
+    type(fpx_calcpv_cfg) :: c
+    integer :: l
+    c%struct_bytes = int(c_sizeof(c), c_int32_t); c%reserved = 0
+    c%dxn = 0
+    do l = 1, min(numbnests, 4)
+      c%dxn(l) = dxn(l)
+    end do
+    ierr = fpx_calcpv_init(flexgpu_handle, c)
+  end subroutine flexgpu_calcpv_init
+
+  ! pvhn(:,:,:,l) of every nest as the last flexgpu_verttransform_nests read it
+  subroutine flexgpu_get_pvh_nests(pvhn, ierr)
+    real, intent(out) :: pvhn(0:nxmaxn-1,0:nymaxn-1,nuvzmax,maxnests)
+    integer, intent(out) :: ierr
+    integer :: l
+    ierr = 0
+    do l = 1, numbnests
+      ierr = fpx_get_pvh(flexgpu_handle, int(l, c_int32_t), loc_r(pvhn(0:,0,1,l)))
+      if (ierr /= 0) return
+    end do
+  end subroutine flexgpu_get_pvh_nests
 #endif
 
   subroutine flexgpu_set_windtime(ierr)

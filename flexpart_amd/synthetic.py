@@ -876,3 +876,108 @@ def getvdep_inputs(m_or_shape, seed=4200, wftime=0):
         out.update(ustar=np.where(u[4] < 0.03, 1.0e-8, 0.05 + 0.9 * u[4] * u[4]), oli=1.0 / ol,
                    ps=60000.0 + 45000.0 * u[7], tt2=tt2, td2=tt2 - 30.0 * u[9] * u[9])
     return out
+
+
+# --------------------------------------------------------------------------
+# calcpv / calcpv_nests: model-level input that drives every branch of the theta-surface search
+# --------------------------------------------------------------------------
+PV_NX, PV_NY, PV_NZ = 37, 29, 20           # nlck = nuvz/3 = 6: searches do run out
+PV_NXMAX, PV_NYMAX = 40, 32                # the strides of the host's arrays differ from the extents
+PV_CASES = ("limited", "global", "nest")
+PV_GEOM = {"limited": (1.0, 0.75, -20.0, 20.5),                         # dx, dy, xlon0, ylat0
+           "global": (360.0 / (PV_NX - 1), 180.0 / (PV_NY - 1), -180.0, -90.0),
+           "nest": (0.25, 0.2, -10.0, 30.1)}                            # dxn, dyn, xlon0n, ylat0n inside the 'limited' grid
+PV_HOT = ((20, 12), (21, 12), (22, 12), (20, 13), (21, 13), (22, 13), (20, 14), (21, 14), (22, 14),   # a 3 x 3 block ...
+          (28, 20), (30, 8), (0, 15), (14, 0))                          # ... and single columns, two of them on an edge
+PV_TIES = ((8, 18, 6), (25, 6, 9), (16, 22, 3))                         # (ix, jy, kl 1-based): theta met within 4e-6 K next door
+PV_TIE_REL = 6.0e-9
+
+
+def _ln_series(x):
+    """ln x for x near 1 from +, *, / alone (2 atanh((x-1)/(x+1))): the same bits on every platform."""
+    z = (x - 1.0) / (x + 1.0)
+    z2, t, acc = z * z, z, 0.0
+    for n in range(40):
+        acc = acc + t / float(2 * n + 1)
+        t = t * z2
+    return 2.0 * acc
+
+
+def _exp_series(y):
+    t, acc = 1.0, 1.0
+    for n in range(1, 40):
+        t = t * y / float(n)
+        acc = acc + t
+    return acc
+
+
+def _hash01(shape, seed):
+    return _uniform01(int(np.prod(shape)), seed).reshape(shape)
+
+
+def calcpv_case(name):
+    """Model-level input of one of the three cases of tests/golden/pv_r*.npz as compact [nz][ny][nx] float64 arrays, from
+    integer hashes and IEEE-exact operations only (+, -, *, /, comparisons, rounding to a binary fraction), so that the
+    tests regenerate the fixture's inputs bit for bit.  Besides what calcpv reads (akz, bkz, ps, tth, uuh, vvh) the dict
+    has everything fpx_verttransform_ecmwf needs (wwh, qvh, tt2, td2, aknew, bknew, an arbitrary pvh) and grid, geom,
+    globalflags.  The temperature has
+      * noise and a patch with a warm level 2 and a cold level 4: theta inversions near the ground, which put a bracket
+        below the level searched from and give non-adjacent brackets;
+      * columns 150 K warmer than their neighbours at all levels (PV_HOT): their theta is not met next door within six
+        levels, and theirs is not met from next door -- no bracket on one side (next to the block, on its rim) and on
+        both (the single columns);
+      * three columns (PV_TIES, ix + 1) whose levels kl, kl + 1 bracket the theta of (ix, jy, kl) within 6e-9 relative
+        on either side: dt = dt1 + dt2 < eps in r8 (calcpv.f90:153), each endpoint 6e-9 away from its own decision.
+    'global' carries the duplicated meridian (column nx-1 = column 0) and sets xglobal, nglobal, sglobal; 'nest' is the
+    input of calcpv_nests: the same arrays on the nest's geometry (dxn != dyn, its own ylat0n)."""
+    if name not in PV_CASES:
+        raise ValueError(name)
+    nx, ny, nz = PV_NX, PV_NY, PV_NZ
+    per = nx - 1
+    i = np.arange(nx, dtype=np.int64)[None, None, :]
+    j = np.arange(ny, dtype=np.int64)[None, :, None]
+    k = np.arange(nz, dtype=np.int64)[:, None, None]
+    s = np.arange(ny, dtype=np.float64)[None, :, None] / float(ny - 1)
+    clat = 4.0 * s * (1.0 - s)
+    q = 1.0 - np.arange(nz, dtype=np.float64) / float(nz - 1)
+    eta = 0.002 + 0.998 * q * q
+    eta[0] = 1.0
+    bk = eta * eta
+    ak = 101325.0 * (eta - bk)
+    ak[0] = 0.0
+    mount = np.maximum(0.0, _wave(2 * i[0] + 3 * j[0], per)) * np.maximum(0.0, _wave(3 * j[0] + 7, 2 * (ny - 1)))
+    ps = np.rint((101200.0 + 900.0 * _wave(i[0] + 2 * j[0], per) - 30000.0 * mount * mount) * 8.0) / 8.0
+    for ix, jy, _ in PV_TIES:
+        ps[jy, ix + 1] = ps[jy, ix]
+    p3 = ak[:, None, None] + bk[:, None, None] * ps[None]
+    rel = p3 / 101325.0
+    base = np.maximum(288.0 - 80.0 * (1.0 - rel), 216.0) + 2.0 * _wave(i + j + 2 * k, per) + 6.0 * (clat - 0.5)
+    tth = base + 1.5 * (_hash01((nz, ny, nx), 7100) - 0.5)
+    tth[1, 4:11, 5:13] += 6.0
+    tth[3, 4:11, 5:13] -= 5.0
+    tth = np.rint(tth * 1024.0) / 1024.0
+    for ix, jy in PV_HOT:
+        tth[:, jy, ix] += 150.0
+    for ix, jy, kl in PV_TIES:
+        # theta(ix+1, kl) = theta(ix, kl) (1 + d): same ps, same level, so the same ppmk; theta(ix+1, kl+1) = theta(ix, kl) (1 - d)
+        # through the ratio of the two levels' (100000/p)**kappa, from the series above (accurate to 1e-15, far inside d)
+        r = _exp_series(0.286 * _ln_series(float(p3[kl, jy, ix]) / float(p3[kl - 1, jy, ix])))
+        tth[kl - 1, jy, ix + 1] = tth[kl - 1, jy, ix] * (1.0 + PV_TIE_REL)
+        tth[kl, jy, ix + 1] = tth[kl - 1, jy, ix] * r * (1.0 - PV_TIE_REL)
+    uuh = np.rint((22.0 * clat * (1.0 + 0.3 * _wave(k, nz)) + 6.0 * _wave(3 * i, per) + 0.0 * j + 3.0 * (_hash01((nz, ny, nx), 7200) - 0.5)) * 64.0) / 64.0
+    vvh = np.rint((6.0 * _wave(2 * i + 0 * j, per) * clat + 2.0 * _wave(k + 3 * j, 40) + 3.0 * (_hash01((nz, ny, nx), 7300) - 0.5)) * 64.0) / 64.0
+    qvh = 0.012 * rel * rel * rel * (0.6 + 0.4 * _wave(2 * i + j, per))
+    wwh = 0.4 * _wave(i, per) * _wave(2 * j + 0 * i, ny - 1) * rel
+    pvh = 1.0e-6 * (1.0 + 0.5 * _wave(i + k, per)) * (2.0 * s - 1.0) / (rel + 0.05)
+    tt2 = base[0] + 0.5 * _wave(3 * i[0] + j[0], per)
+    td2 = tt2 - 3.0 - 2.0 * (1.0 + _wave(i[0] + 5 * j[0], per))
+    out = dict(akz=ak, bkz=bk, aknew=ak.copy(), bknew=bk.copy(), ps=ps, tt2=tt2, td2=td2, tth=tth, qvh=qvh, uuh=uuh, vvh=vvh,
+               pvh=pvh, wwh=wwh)
+    glob = name == "global"
+    if glob:
+        for key in ("ps", "tt2", "td2", "tth", "qvh", "uuh", "vvh", "pvh", "wwh"):
+            out[key][..., nx - 1] = out[key][..., 0]
+    out["grid"] = np.array([nx, ny, nz], np.int32)
+    out["geom"] = np.array(PV_GEOM[name], np.float64)
+    out["globalflags"] = np.array([int(glob)] * 3, np.int32)
+    return out

@@ -195,9 +195,13 @@ int fpx_upload_fields(fpx_handle h, int32_t slot, const fpx_fields *f);
  * stereographic winds) runs there and its result is repacked straight into the gather layout.
  * The cloud diagnostics of verttransform_ecmwf.f90:604-880 and `prs` are not computed (not read
  * by the particle path; a host that needs them keeps its own loop over `out->tt, qv, rho`).
+ * pvh = NULL: the potential vorticity on model levels is computed on the device first, from the uuh, vvh, tth, ps, akz, bkz
+ * of this call (calcpv.f90:42-313, which calcpar.f90:270 calls; for fpx_verttransform_nest calcpv_nests.f90 with the nest's
+ * dxn from fpx_calcpv_init and nest_dy, nest_ylat0 below), and the host neither runs calcpv nor ships the array.  With
+ * pvh != NULL the host's array is used as before.  fpx_get_pvh returns the model-level array either way.
  * All pointers address host arrays in the reference's own shapes. */
 typedef struct {
-  const void *uuh, *vvh, *pvh;   /* (0:nxmax-1,0:nymax-1,nuvzmax), verttransform_ecmwf.f90:62  */
+  const void *uuh, *vvh, *pvh;   /* (0:nxmax-1,0:nymax-1,nuvzmax), verttransform_ecmwf.f90:62; pvh may be NULL (see above) */
   const void *wwh;               /* (0:nxmax-1,0:nymax-1,nwzmax),  :63                          */
   const void *tth, *qvh;         /* c_loc(tth(0,0,1,n)), com_mod.f90:372-373                    */
   const void *ps, *tt2, *td2;    /* c_loc(ps(0,0,1,n)) ..., com_mod.f90:410-417                 */
@@ -211,7 +215,8 @@ typedef struct {
                                     arrays): register them once for DMA (hipHostRegister) -- the 433 MB
                                     host-to-device copy then runs at PCIe speed instead of the pageable path */
   double nest_dy, nest_ylat0;    /* fpx_verttransform_nest only: dyn(l), ylat0n(l) of the nest (com_mod.f90:477-479),
-                                    used in cosf (verttransform_nests.f90:346)                       */
+                                    used in cosf (verttransform_nests.f90:346) and, with pvh = NULL, in
+                                    calcpv_nests.f90:56,241,244                                     */
 } fpx_model_levels;
 /* Optional copies back to the host (NULL members are skipped): the z-level arrays in the host's
  * shapes (0:nxmax-1,0:nymax-1,nzmax) for slot n, e.g. c_loc(tt(0,0,1,n)); height(nz); nmixz. */
@@ -228,8 +233,24 @@ int fpx_verttransform_ecmwf(fpx_handle h, int32_t slot, const fpx_model_levels *
  * fpx_upload_nest_fields of that slot.  Pointers address the nest's arrays of that nest, e.g. c_loc(uuhn(0,0,1,l)),
  * c_loc(tthn(0,0,1,n,l)), strides nxmaxn, nymaxn; the z levels are the mother grid's. */
 int fpx_verttransform_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out);
-/* device time of the transform kernels of the last call, milliseconds */
+/* device time of the transform kernels of the last call, milliseconds (without the PV kernels of a call with pvh = NULL) */
 int fpx_verttransform_time(fpx_handle h, double *ms);
+/* ---- calcpv / calcpv_nests on the device (run by the two transforms above when pvh = NULL) -----------------
+ * The mother grid needs nothing beyond fpx_config (dx, dy, ylat0, xglobal, nglobal, sglobal).  A nest needs com_mod's
+ * dxn(l) itself: calcpv_nests.f90:168,171 divides by it, and dx/xresoln(l) need not round to the same number.  Call once
+ * after fpx_nests_init; fpx_verttransform_nest with pvh = NULL before it returns FPX_ERR_STATE. */
+typedef struct {
+  int32_t struct_bytes;
+  int32_t reserved;
+  double dxn[FPX_MAXNESTS];      /* dxn(1:numbnests), com_mod.f90:477 */
+} fpx_calcpv_cfg;
+int fpx_calcpv_init(fpx_handle h, const fpx_calcpv_cfg *c);
+/* The model-level PV the last transform of grid `nest` (0 = mother grid, l = nest l) read, in the host's shape and real
+ * kind: (0:nxmax-1,0:nymax-1,nz) for nest = 0, strides nxmaxn, nymaxn for a nest.  The device's own result after a call
+ * with pvh = NULL, the host's array after a call that passed one.  FPX_ERR_STATE before any transform of that grid. */
+int fpx_get_pvh(fpx_handle h, int32_t nest, void *pvh_out);
+/* device time of the PV kernels of the last transform, milliseconds; 0 if that transform was handed pvh */
+int fpx_calcpv_time(fpx_handle h, double *ms);
 /* ---- calcpar on the device (SURVEY section 8 f, item 1, second half) -------------------------------------
  * Replaces `call calcpar(n,uuh,vvh,pvh)` (getfields.f90:128,163,179; the routine: calcpar.f90:76-265, ECMWF branch) for the
  * fields the particle path reads: ustar (scalev.f90), oli (obukhov.f90), hmix and wstar (richardson.f90 with qvsat.f90,
@@ -238,7 +259,8 @@ int fpx_verttransform_time(fpx_handle h, double *ms);
  * sfc = NULL (then the 2-D fields come from here and nothing but ps, tt2, td2, surfstr, sshf crosses PCIe) -- and
  * writes the gather packs of the slot directly.  Not computed here: vdep (getvdep, calcpar.f90:171-189) -- with DRYDEP
  * either pass the host's vdep of this slot, or set device_vdep = 1 and call fpx_getvdep(h, slot, ..) next, which computes
- * it from the ustar and oli this call leaves on the device -- and the potential vorticity (calcpv, :270).
+ * it from the ustar and oli this call leaves on the device.  The potential vorticity (calcpv, :270) is the transform's:
+ * fpx_verttransform_ecmwf with pvh = NULL computes it on the device.
  * The reference calls calcpar before verttransform; the two are independent of each other's results. */
 typedef struct {
   const void *surfstr, *sshf;    /* c_loc(surfstr(0,0,1,n)), c_loc(sshf(0,0,1,n)), com_mod.f90:420-422          */
