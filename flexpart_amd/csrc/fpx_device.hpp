@@ -12,6 +12,7 @@
 #include "fpx_tu.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "fpx_erfcx_tab.hpp"
 
 namespace fpx {
 FPX_TU_OPEN
@@ -243,6 +244,24 @@ FPX_DEV double m_exp_tab(double x, TP tab /* kExpTab layout */) {
   p = fma(r, p, 1.0);
   return ldexp(fma(t, r * p, t), ki >> 5);
 }
+// exp(-u/2) = m_exp_tab(-(0.5*u)) without the multiplication in front: the factor -1/2 sits in the constants.  k is the same
+// integer (the scaled product rounds alike), r here is -2 times the r there and every coefficient carries the matching power of
+// -1/2 (one more for the product r*p), all of them powers of two: each intermediate is the other form's times a power of two,
+// so the result has the same bits.
+template <typename TP>
+FPX_DEV double m_exp_tab_nh(double u, TP tab /* kExpTab layout */) {
+  const double k = rint(u * -23.083120654223414);
+  double r = fma(k, 0.04332169877307024, u);
+  r = fma(k, 1.1926343307941173e-11, r);
+  const int ki = (int)k;
+  const double t = tab[ki & 31];
+  double p = m_fma_k(r, 1.3888888888888888889e-03 / 64.0, -8.3333333333333333333e-03 / 32.0);
+  p = m_fma_k(r, p, 4.1666666666666666667e-02 / 16.0);
+  p = m_fma_k(r, p, -1.6666666666666666667e-01 / 8.0);
+  p = fma(r, p, 0.125);
+  p = fma(r, p, -0.5);
+  return ldexp(fma(t, r * p, t), ki >> 5);
+}
 // x**(-1/3) for x in the f32 exponent range: f32 seed, two Newton steps r <- r + r*(1 - x*r^3)/3
 FPX_DEV double m_rcbrt(double x) {
   double r = (double)__builtin_amdgcn_exp2f(__log2f((float)x) * (-1.0f / 3.0f));
@@ -321,6 +340,46 @@ FPX_DEV void m_erf_e2(T xa, T Ea, T xb, T Eb, T &ra, T &rb) {
   const T qa = (T)1.0 - Ea * pa, qb = (T)1.0 - Eb * pb;
   // the sign of x by a bit-field insert instead of a compare and two selects; qa, qb >= 0 up to the rounding of 1 - E*p at x = 0,
   // where the two forms can differ by an ulp of 1 in the sign of a value of that size
+  ra = m_sign(qa, xa);
+  rb = m_sign(qb, xb);
+}
+// The same pair with g from the piecewise table of fpx_erfcx_tab.hpp (tools/fit_erfcx_table.py): polynomials in d = |x| - centre
+// on uniform intervals of |x| itself, so there is no reciprocal for the rational map and the Horner chain is kErfcxDegree steps
+// instead of 17.  `tab` is the block's LDS copy of kErfcxTab (lane-divergent ds_read_b64: no VALU cycles); a row starts with
+// its centre.  Same bound (5e-16 absolute) and the same edges as m_erf_e2: the clamp at 6.5 holds beyond it (fmin drops a NaN,
+// so the index is always that of a finite number in 0 .. 6.5, and the unsigned minimum keeps it inside the table whatever
+// comes), x = +-0 gives +-0 or an ulp of 1, and a NaN or infinite x leaves through E.
+// Registers decide the shape.  The coefficients arrive in vector registers, not in scalar ones as those of m_erf_e2 do, and the
+// flagship instance has 15 to spare at three waves per SIMD (with 16-byte reads of both rows up front it spilled 36 to
+// scratch memory).  So a chain reads one coefficient ahead of the one in use and no more -- the empty asm makes the next
+// read's address depend on the chain's value, else the compiler issues all reads of a row at once -- and the two chains run
+// one after the other, not interleaved: a dependent fp64 fma issues for longer than its result takes, so the second chain
+// has nothing to hide (m_erf_e2 interleaves to share its scalar loads, not for latency).
+typedef __attribute__((address_space(3))) const double *lds_erft_ptr;
+template <typename TP>
+FPX_DEV double m_erfcx_tab(double c /* min(|x|, kErfcxMax) */, TP tab /* kErfcxTab layout */) {
+  static_assert(kErfcxRow >= kErfcxDegree + 2, "a row is its centre and degree + 1 coefficients");
+  const unsigned int i = min((unsigned int)(int)(c * kErfcxPerUnit), (unsigned int)(kErfcxIntervals - 1));
+  TP row = tab + i * kErfcxRow;
+  const double centre = row[0];
+  double p = row[1], w = row[2];
+  const double d = c - centre;
+#pragma unroll
+  for (int k = 2; k < kErfcxDegree + 2; k++) {
+    const double v = w;
+    if (k + 1 < kErfcxDegree + 2) {
+      asm volatile("" : "+v"(row), "+v"(p));
+      w = row[k + 1];
+    }
+    p = fma(p, d, v);
+  }
+  return p;
+}
+template <typename TP>
+FPX_DEV void m_erf_tab2(double xa, double Ea, double xb, double Eb, TP tab, double &ra, double &rb) {
+  const double pa = m_erfcx_tab(m_min(m_abs(xa), kErfcxMax), tab);
+  const double pb = m_erfcx_tab(m_min(m_abs(xb), kErfcxMax), tab);
+  const double qa = 1.0 - Ea * pa, qb = 1.0 - Eb * pb;
   ra = m_sign(qa, xa);
   rb = m_sign(qb, xb);
 }
@@ -1087,10 +1146,30 @@ struct Stash {
   FPX_DEV double expt(double x) const { return m_exp_tab(x, tab + kLdsExpTabAt); }
   FPX_DEV float logabs(float x) const { return m_logp(x); }
   FPX_DEV float expt(float x) const { return m_expp(x); }
+  FPX_DEV double exp_nh(double u) const { return m_exp_tab_nh(u, tab + kLdsExpTabAt); }   // exp(-u/2), the bits of expt(-(0.5*u))
+  FPX_DEV float exp_nh(float u) const { return m_expp(-(0.5f * u)); }
+  template <typename T> FPX_DEV void erf_pair(T xa, T Ea, T xb, T Eb, T &ra, T &rb) const { m_erf_e2(xa, Ea, xb, Eb, ra, rb); }
   FPX_DEV R get(int k) const { return p[k * kStashStride]; }
   FPX_DEV void put(int k, R v) const { p[k * kStashStride] = v; }
   FPX_DEV void add(int k, R v) const { p[k * kStashStride] = p[k * kStashStride] + v; }
 };
+
+// The stash of the instances whose block has LDS to spare for the table of the error-function pair (fp64 gas kernels: 19 or 20
+// slots; the fp64 aerosol kernels' 25 leave no room at three blocks per CU, and f32 keeps its own polynomial): cbl() takes the
+// pair from whichever stash type it is handed.
+struct StashErfTab : Stash<double> {
+  lds_erft_ptr erft;   // the block's copy of kErfcxTab
+  FPX_DEV void erf_pair(double xa, double Ea, double xb, double Eb, double &ra, double &rb) const { m_erf_tab2(xa, Ea, xb, Eb, erft, ra, rb); }
+};
+template <typename R, bool ERFTAB> struct StashFor { typedef Stash<R> type; };
+template <> struct StashFor<double, true> { typedef StashErfTab type; };
+template <typename R, bool ERFTAB>
+FPX_DEV typename StashFor<R, ERFTAB>::type make_stash(typename Stash<R>::lds_ptr p, lds_tab_ptr tab, lds_erft_ptr erft) {
+  if constexpr (ERFTAB) return StashErfTab{{p, tab}, erft};
+  else return Stash<R>{p, tab};
+}
+// does a Langevin kernel instance carry the table?  (the kernel sizes its static LDS by the same rule)
+template <typename R> constexpr bool stash_has_erf_tab(bool lean) { return lean && sizeof(R) == 8; }
 
 // The step's invariants of a lane of the Langevin kernel live in three stash slots and no register.  The flags travel in the
 // signs: 1/ust > 0 is the neutral regime, 1/ol < 0 the unstable one, 0 the stable one (ust and ol finite), and the sign bit of
@@ -1194,21 +1273,24 @@ FPX_DEV R cbl_transition(R h, R ol) {   // cbl.f90:79-81
 //     for the second quotient +0.5*al*rs^3*(dal*a1 - al*bl*ffd);
 //   sigmawa*dwa - wa*dsigmawa = dfluarw*sigmawa^2 (dwa = df*sigmawa + f*dsigmawa, wa = f*sigmawa), so the last bracket
 //     of :193-194 is wold*dfluarw (and -wold*dfluarw in :198-199);
-//   alfa = 2 w2/(C0 tlw) and bth = sqrt(C0 alfa) = sw*sqrt(2/tlw) from one rsqrt(tlw);
+//   alfa = 2 w2/(C0 tlw) is only used as -(C0/2)*alfa*Q = -(w2/tlw)*Q, and bth = sqrt(C0 alfa) = sw*sqrt(2/tlw): one rsqrt(tlw)
+//     and neither constant;
+//   the 1/sqrt(2 pi) of the two Gaussians multiplies every term of ptot and Q and all of Phi but the error-function term:
+//     it is left out of pa, pb and divided out of that term's 0.5 instead;
 //   the two cube roots of cbl.f90:115-121 from one x**(-1/3) (m_cuberoot_parts).
 // What is left is 2 reciprocals, 1 sqrt, 2 coupled sqrt+rsqrt, 1 rsqrt, 2 exp and 2 erf per call
 // (the straightforward form has 20 divisions, 7 square roots, 1 log and 4 exp).
 // `wt` = wst^3 * transition (cbl.f90:79-81,103-104): depends on h, ol, wst only and is passed in.
-// ST: the source of the lookup tables of exp (the loop kernel's stash)
+// `z` = zp/h as zp*ih: the caller has it already (the zeta of the sub-step before, or its own product in a pass's first).
+// ST: the source of the lookup tables of exp and of the error-function pair (the loop kernel's stash)
 template <typename R, typename ST>
-FPX_DEV void cbl(const ST &S, int ldirect, R wp, R zp, R wt /* wst^3 * transition */, R ih /* 1/h */, R rhoaux /* rhograd/rhoa */, R sigmaw, R irw /* 1/sigmaw */, R dsigmawdz, R tlw,
+FPX_DEV void cbl(const ST &S, int ldirect, R wp, R z /* zp * ih */, R wt /* wst^3 * transition */, R ih /* 1/h */, R rhoaux /* rhograd/rhoa */, R sigmaw, R irw /* 1/sigmaw */, R dsigmawdz, R tlw,
                  R &ath, R &bth, int &flagrein) {
-  const R usurad2 = K(0.7071067812), usurad2p = K(0.3989422804), C0 = K(3), costluar4 = K(0.66667), eps = K(0.000001);
+  const R usurad2 = K(0.7071067812), usurad2p = K(0.3989422804), costluar4 = K(0.66667), eps = K(0.000001);
   const unsigned int tdir = ldirect < 0 ? 0x80000000u : 0u;   // timedir = ldirect = +-1 as a sign mask: x * timedir = m_flip(x, tdir), exactly
-  const R z = zp * ih;
   const R w2 = sigmaw * sigmaw;
   const R rtl = m_rsqrt(tlw);                        // tlw >= 30 (hanna_short.f90:91)
-  const R alfa = (K(2.) / C0) * w2 * (rtl * rtl);
+  const R w2tl = w2 * (rtl * rtl);                   // (C0/2)*alfa
   const R wold = m_flip(wp, tdir);
   const R omz = K(1.) - z;
   const R omz05 = m_sqrtp(omz), omz15 = omz * omz05;
@@ -1260,13 +1342,13 @@ FPX_DEV void cbl(const ST &S, int ldirect, R wp, R zp, R wt /* wst^3 * transitio
   const R da = deltawa * isa, db = deltawb * isb;
   if (m_abs(da) > K(6.) && m_abs(db) > K(6.)) flagrein = 1;   // abs(deltawa) > 6*sigmawa .and. abs(deltawb) > 6*sigmawb
   const R da2 = da * da, db2 = db * db;
-  const R ea = S.expt(-(K(0.5) * da2)), eb = S.expt(-(K(0.5) * db2));
-  const R pa = (usurad2p * isa) * ea;
-  const R pb = (usurad2p * isb) * eb;
+  const R ea = S.exp_nh(da2), eb = S.exp_nh(db2);
+  const R pa = isa * ea;                             // the two Gaussians times sqrt(2 pi)
+  const R pb = isb * eb;
   const R aperfa = da * usurad2;
   const R aperfb = db * usurad2;
   // The air density multiplies every term of ptot, Q and Phi (cbl.f90:175-205) and cancels in
-  // ath = (-(C0/2)*alfa*Q + Phi)/ptot; what is left of it is rx = rhograd/rhoa.
+  // ath = (-(C0/2)*alfa*Q + Phi)/ptot; what is left of it is rx = rhograd/rhoa.  So does the Gaussians' 1/sqrt(2 pi).
   const R rx = rhoaux;
   const R apa = aluarw * pa, bpb = bluarw * pb;
   const R ptot = apa + bpb;
@@ -1278,10 +1360,10 @@ FPX_DEV void cbl(const ST &S, int ldirect, R wp, R zp, R wt /* wst^3 * transitio
   // exp(-aperf^2) from exp(-d^2/2): aperf = d*usurad2 and usurad2^2 - 0.5 = 5.9e-12 (the reference's 10-digit 1/sqrt(2))
   const R cu = usurad2 * usurad2 - K(0.5);
   R erfa, erfb;
-  m_erf_e2(aperfa, ea - ea * (da2 * cu), aperfb, eb - eb * (db2 * cu), erfa, erfb);
-  const R Phi = K(0.5) * (Tb * erfb - Ta * erfa) + Ua * pa + Ub * pb;
+  S.erf_pair(aperfa, ea - ea * (da2 * cu), aperfb, eb - eb * (db2 * cu), erfa, erfb);
+  const R Phi = (K(0.5) / usurad2p) * (Tb * erfb - Ta * erfa) + Ua * pa + Ub * pb;
   const R Q = m_flip((da * isa) * apa + (db * isb) * bpb, tdir);
-  ath = m_rcp(ptot) * (-(C0 / K(2.)) * alfa * Q + Phi);
+  ath = m_rcp(ptot) * (Phi - w2tl * Q);
   bth = (sigmaw * K(1.4142135623730951)) * rtl;     // sqrt(C0*alfa) = sigmaw*sqrt(2/tlw)
 }
 
@@ -2287,9 +2369,9 @@ struct RecCold {
 template <int T>
 FPX_DEV bool sw(int runtime) { return T < 0 ? runtime != 0 : T != 0; }
 
-template <typename R, bool DRYDEP, bool SETTLE, int TSW, int CBLF, typename RNG>
+template <typename R, bool DRYDEP, bool SETTLE, int TSW, int CBLF, typename RNG, typename ST /* Stash<R> or StashErfTab */>
 FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R> &W, int itime, double xt, double yt,
-                     R &zt, R &wp, int &ldt, short &icbt, LoopCtx<R> &A, const Stash<R> &S,
+                     R &zt, R &wp, int &ldt, short &icbt, LoopCtx<R> &A, const ST &S,
                      int &indz_last, Stats *st, const RecCold<R> &RC) {
   const R eps = V.eps;
   const R eps2 = K(1.e-9);
@@ -2397,6 +2479,11 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
   // vertical Langevin, ifine sub-steps, advance.f90:396-498
   FPX_LANES(st, 0);
   unsigned int flip = icbt < 0 ? 0x80000000u : 0u;   // icbt as a sign mask inside the loop (m_flip)
+  // cbl() takes z/h as the product zt * ih, which is what the tail of a sub-step leaves in T.zeta for the next; the first
+  // sub-step gets the same product here (hanna() above was the last to read the quotient zt / h).  Only in the instances
+  // compiled for the scheme: the general one, where cblflag is a run-time value, spilled two registers with it.
+  constexpr bool zeta_is_product = CBLF > 0;
+  if (zeta_is_product) T.zeta = zt * HI.ih;
   for (int i = 1; i <= V.ifine; i++) {
     R delz;
     FPX_LANES(st, 1);
@@ -2408,7 +2495,7 @@ FPX_DEV int pbl_pass(const View<R> &V, const R *hgt, const RNG &G, const TimeW<R
             int flagrein = 0;
             nrand = nrand + 1;
             R old_wp_buf = wp, ath, bth;
-            cbl(S, V.ldirect, wp, zt, S.get(S_TRANS), HI.ih, S.get(S_RHOAUX), T.sigw, T.isigw, T.dsigwdz, T.tlw, ath, bth, flagrein);
+            cbl(S, V.ldirect, wp, zeta_is_product ? T.zeta : zt * HI.ih, S.get(S_TRANS), HI.ih, S.get(S_RHOAUX), T.sigw, T.isigw, T.dsigwdz, T.tlw, ath, bth, flagrein);
             wp = m_flip(wp + ath * dtf + bth * G.at(nrand) * sqrt_dtf, flip);
             delz = wp * dtf;
             if (__builtin_expect(flagrein == 1, 0)) {

@@ -1367,8 +1367,17 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
   __shared__ double lds_tab[sizeof(R) == 8 ? kLdsTabDoubles : 1];
   if (sizeof(R) == 8)
     for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
+  // ... and, where the block has the room (the fp64 gas kernels), of the table of the error-function pair (m_erf_tab2): 2.4 KB,
+  // static like the tables above, so the host's rule for the dynamic part (loop_smem_bytes) does not change.  With it a
+  // one-launch fp64 gas kernel has 19 x 2 KB + 8 nz + 768 B + 2496 B per block: 43.3 KB at nz = 138, three blocks per CU
+  // (53248 B each) up to nz = 1380.
+  constexpr bool ERFTAB = stash_has_erf_tab<R>(LEAN);
+  __shared__ __align__(16) double lds_erft[ERFTAB ? kErfcxIntervals * kErfcxRow : 2];
+  if (ERFTAB)
+    for (int k = threadIdx.x; k < kErfcxIntervals * kErfcxRow; k += blockDim.x) lds_erft[k] = kErfcxTab[k];
   __syncthreads();
-  const Stash<R> S{(typename Stash<R>::lds_ptr)(stash_mem + threadIdx.x), (lds_tab_ptr)lds_tab};
+  typedef typename StashFor<R, ERFTAB>::type stash_t;
+  const stash_t S = make_stash<R, ERFTAB>((typename Stash<R>::lds_ptr)(stash_mem + threadIdx.x), (lds_tab_ptr)lds_tab, (lds_erft_ptr)lds_erft);
   const int lane = threadIdx.x & 63;
   const TimeW<R> W = time_weights(V, itime);   // wave-uniform
   const R cap_r = cap_passes > 0 ? (R)cap_passes : (R)1e30;
@@ -1622,6 +1631,28 @@ __global__ void k_math_probe(int fn, const double *__restrict__ x, double *__res
     default: m_cuberoot_parts(v, c, ic2); r = ic2; break;
   }
   y[i] = r;
+}
+
+// diagnostics (fpx_math_probe, fn 12 .. 14): the error function with E = exp(-x*x) handed in, x = in[0 .. n), E = in[n .. 2n) --
+// 12: the polynomial form (m_erf_e2), 13: the table form with the table in LDS as in k_pbl_loop (m_erf_tab2); both take the
+// point as either member of the pair, which must agree, else NaN -- and 14: exp(-x/2) with the factor in the constants
+// (m_exp_tab_nh; x = in[0 .. n) alone).
+__global__ void __launch_bounds__(kBlock) k_erf_probe(int fn, const double *__restrict__ in, double *__restrict__ y, long long n) {
+  __shared__ __align__(16) double lds_erft[kErfcxIntervals * kErfcxRow];
+  for (int k = threadIdx.x; k < kErfcxIntervals * kErfcxRow; k += blockDim.x) lds_erft[k] = kErfcxTab[k];
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double v = in[i];
+  if (fn == 14) { y[i] = m_exp_tab_nh(v, &kExpTab[0]); return; }
+  const double E = in[n + i];
+  const long long j = i + 1 < n ? i + 1 : 0;   // the pair's other member: a neighbour
+  const double v2 = in[j], E2 = in[n + j];
+  double a, b, c, d;
+  if (fn == 12) { m_erf_e2(v, E, v2, E2, a, b); m_erf_e2(v2, E2, v, E, c, d); }
+  else { m_erf_tab2(v, E, v2, E2, (lds_erft_ptr)lds_erft, a, b); m_erf_tab2(v2, E2, v, E, (lds_erft_ptr)lds_erft, c, d); }
+  const bool same = a == d || (a != a && d != d);
+  y[i] = same ? a : __builtin_nan("");
 }
 
 // diagnostics (fpx_hanna_probe): hanna() of a Langevin pass on plain arrays, ten values per point -- sigu, sigv, sigw, dsigwdz, 1/tlu,
@@ -5915,14 +5946,16 @@ int fpx_receptors_init(fpx_handle h, int32_t numreceptor, const void *xreceptor,
 int fpx_get_receptors(fpx_handle h, void *creceptor, int32_t ld, int32_t allreduce, int32_t clear) { FPX_GUARD(h); return h->impl->get_receptors(creceptor, ld, allreduce, clear); }
 
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n) {
-  if (fn < 0 || fn > 11 || !x || !y || n < 0) return FPX_ERR_ARG;
+  if (fn < 0 || fn > 14 || !x || !y || n < 0) return FPX_ERR_ARG;
   if (n == 0) return FPX_OK;
+  const int64_t nin = (fn == 12 || fn == 13) ? 2 * n : n;   // fn 12, 13: x[0 .. n) the points, x[n .. 2n) their exp(-x*x)
   double *dx = nullptr, *dy = nullptr;
-  if (hipMalloc(&dx, n * sizeof(double)) != hipSuccess) return FPX_ERR_NOMEM;
+  if (hipMalloc(&dx, nin * sizeof(double)) != hipSuccess) return FPX_ERR_NOMEM;
   if (hipMalloc(&dy, n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); return FPX_ERR_NOMEM; }
-  hipError_t e = hipMemcpy(dx, x, n * sizeof(double), hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpy(dx, x, nin * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    fpx::k_math_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(fn, dx, dy, n);
+    if (fn >= 12) fpx::k_erf_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(fn, dx, dy, n);
+    else fpx::k_math_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(fn, dx, dy, n);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(y, dy, n * sizeof(double), hipMemcpyDeviceToHost);

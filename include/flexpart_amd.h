@@ -704,7 +704,9 @@ void *fpx_stream(fpx_handle h);
  * replacements of exp/log/sqrt/division used inside the Langevin loop) on n host values, on the
  * current device.  fn: 0 m_expp, 1 m_logp, 2 m_sqrtp, 3 m_rcp, 4 m_rsqrt, 5 x**0.333333333 and
  * 6 x**(-2*0.333333333) (m_cuberoot_parts), 7 m_erf_e(x, m_expp(-x*x)), 8 m_pow08,
- * 9 m_exp_tab, 10 m_log_abs, 11 m_rcbrt (the table-based helpers of the fine sub-step).  No reference counterpart; used by the parity tests to bound
+ * 9 m_exp_tab, 10 m_log_abs, 11 m_rcbrt (the table-based helpers of the fine sub-step); 12 and 13 the error function of
+ * cbl() with its Gaussian handed in -- x[0 .. n) the points, x[n .. 2n) their exp(-x*x), y[0 .. n) the result -- as the
+ * polynomial form (m_erf_e2) and as the table form (m_erf_tab2); 14 exp(-x/2) (m_exp_tab_nh).  No reference counterpart; used by the parity tests to bound
  * the helpers against libm.  Returns 0 or a negative fpx_status. */
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n);
 /* Diagnostics: the turbulence profiles of one Langevin pass (hanna.f90) for n points in[5i..5i+4] = h, ol, ust, wst, z: ten values
