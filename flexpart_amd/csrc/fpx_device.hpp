@@ -70,25 +70,47 @@ FPX_HD double m_sign(double a, double b) { return __builtin_copysign(a, b); }
 // (results are within 1-2 ulp instead of correctly rounded) for 2-4x fewer cycles.
 // The float overloads keep the plain operations.
 // ---------------------------------------------------------------------------
+// The fp64 roots and reciprocals refine a seed of relative error e0 by Newton-type steps.  Two quadratic steps (e0 -> e0^2 -> e0^4)
+// overshoot the 2^-53 that is wanted from a 2^-23 seed by 39 bits; ONE cubic step (e0 -> C*e0^3, C <= 1) lands at 2^-69 with
+// fewer operations and a shorter dependent chain, where the seed is good enough (the hardware's: everywhere; the f32 ones: inside
+// m_in_cubic_range, two steps outside it).  Both forms are kept: m_*_q2 the two quadratic steps, m_*_c1 the cubic one.
+// FPX_NEWTON_HW (m_rcp, m_divf, m_rsqrt, m_sqrtp, m_sqrt_rsqrt: seeds of v_rcp_f64 / v_rsq_f64) and FPX_NEWTON_F32 (m_rcbrt,
+// m_cuberoot_parts, m_pow08, through m_rcbrt m_pow13 and zeta_powers: seeds of v_log_f32 / v_exp_f32) choose which one the
+// kernels call: 1 (the default) the cubic step, 0 the two quadratic ones, one switch per seed family so that a measurement
+// build (-DFPX_NEWTON_HW=0 ...) can take either part alone.  Measured seed errors and the bound a cubic step needs: DESIGN.md,
+// "Round 8"; tools/newton_tail_model.py has both forms in exact arithmetic.
+#ifndef FPX_NEWTON_HW
+#define FPX_NEWTON_HW 1
+#endif
+#ifndef FPX_NEWTON_F32
+#define FPX_NEWTON_F32 1
+#endif
 FPX_DEV float m_rcp(float b) { return __builtin_amdgcn_rcpf(b); }   // v_rcp_f32, 1 ulp
-FPX_DEV double m_rcp(double b) {   // 1/b, b finite and non-zero: hardware seed + two Newton steps (34 cycles)
+// 1/b, b finite and non-zero (0, +-inf and NaN all give NaN, in either form).
+FPX_DEV double m_rcp_q2(double b) {   // hardware seed + two Newton steps: 4 operations behind the seed (34 cycles)
   double r = __builtin_amdgcn_rcp(b);
   double e = fma(-b, r, 1.0);
   r = fma(r, e, r);
   e = fma(-b, r, 1.0);
   return fma(r, e, r);
 }
+FPX_DEV double m_rcp_c1(double b) {   // hardware seed + one cubic step r*(1 + e + e^2), e = 1 - b*r: 3 operations (29 cycles)
+  double r = __builtin_amdgcn_rcp(b);
+  const double e = fma(-b, r, 1.0);
+  const double t = fma(e, e, e);
+  return fma(r, t, r);
+}
+FPX_DEV double m_rcp(double b) { return FPX_NEWTON_HW ? m_rcp_c1(b) : m_rcp_q2(b); }
 // a/b where the divisor is finite and non-zero by construction: m_rcp + one residual correction
 FPX_DEV float m_divf(float a, float b) { return a / b; }
-FPX_DEV double m_divf(double a, double b) {
-  double r = m_rcp(b);
+FPX_DEV double m_divf_with(double a, double b, double r /* 1/b */) {
   double q = a * r;
   return fma(fma(-b, q, a), r, q);
 }
-// sqrt(x) and 1/sqrt(x) together for x > 0 (normal range): v_rsq_f64 + one coupled
-// Goldschmidt step + one residual correction each (56 cycles for both)
+FPX_DEV double m_divf(double a, double b) { return m_divf_with(a, b, m_rcp(b)); }
+// sqrt(x) and 1/sqrt(x) together for x > 0 (normal range; 0, +inf, negative and NaN arguments give NaN for both, in either form)
 FPX_DEV void m_sqrt_rsqrt(float x, float &s, float &rs) { s = __builtin_amdgcn_sqrtf(x); rs = __builtin_amdgcn_rsqf(x); }   // v_sqrt_f32 / v_rsq_f32, 1 ulp
-FPX_DEV void m_sqrt_rsqrt(double x, double &s, double &rs) {
+FPX_DEV void m_sqrt_rsqrt_q2(double x, double &s, double &rs) {   // v_rsq_f64 + one coupled Goldschmidt step + one residual correction each: 10 operations (60 cycles)
   double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
   double r = fma(-h, g, 0.5);
@@ -101,8 +123,20 @@ FPX_DEV void m_sqrt_rsqrt(double x, double &s, double &rs) {
   s = g;
   rs = h + h;
 }
+// with g = x*y, h = y/2 and r = 1/2 - h*g = (1 - x*y^2)/2: (1 - 2r)^(-1/2) = 1 + r + 3/2 r^2 + O(r^3), the same factor for both
+FPX_DEV void m_sqrt_rsqrt_c1(double x, double &s, double &rs) {   // v_rsq_f64 + one cubic step for both: 8 operations (51 cycles)
+  const double y = __builtin_amdgcn_rsq(x);
+  const double g = x * y, h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  const double rt = r * fma(r, 1.5, 1.0);
+  s = fma(g, rt, g);
+  const double h1 = fma(h, rt, h);
+  rs = h1 + h1;
+}
+FPX_DEV void m_sqrt_rsqrt(double x, double &s, double &rs) { if (FPX_NEWTON_HW) m_sqrt_rsqrt_c1(x, s, rs); else m_sqrt_rsqrt_q2(x, s, rs); }
+// 1/sqrt(x), x > 0 (0, +inf, negative, NaN: NaN, in either form)
 FPX_DEV float m_rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
-FPX_DEV double m_rsqrt(double x) {   // x > 0
+FPX_DEV double m_rsqrt_q2(double x) {   // 8 operations behind the seed (51 cycles)
   double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
   double r = fma(-h, g, 0.5);
@@ -112,9 +146,18 @@ FPX_DEV double m_rsqrt(double x) {   // x > 0
   h = fma(h, r, h);
   return h + h;
 }
-// sqrt(x) for x >= 0 (0 allowed), 47 cycles
+FPX_DEV double m_rsqrt_c1(double x) {   // one cubic step y*(1 + e/2 + 3/8 e^2), e = 1 - x*y^2: 5 operations (38 cycles)
+  const double y = __builtin_amdgcn_rsq(x);
+  const double t = x * y;
+  const double e = fma(-t, y, 1.0);
+  const double p = fma(e, 0.375, 0.5);
+  return fma(y, e * p, y);
+}
+FPX_DEV double m_rsqrt(double x) { return FPX_NEWTON_HW ? m_rsqrt_c1(x) : m_rsqrt_q2(x); }
+// sqrt(x) for x >= 0 (+0 allowed and exactly +0, subnormals too; -0, +inf and NaN: NaN; negative: -inf, the bounded seed below
+// being finite for them -- in either form)
 FPX_DEV float m_sqrtp(float x) { return __builtin_amdgcn_sqrtf(x); }
-FPX_DEV double m_sqrtp(double x) {
+FPX_DEV double m_sqrtp_q2(double x) {   // the v_min and 7 operations (51 cycles)
   // rsq(0) = inf would make 0 * inf = NaN: bounded by 1e300 (1/sqrt of the smallest subnormal is 4.5e161) every step below
   // gives exactly 0 for x = 0 -- one v_min_f64 instead of a compare and two conditional moves on the result
   double y = __builtin_fmin(__builtin_amdgcn_rsq(x), 1.0e300);
@@ -126,6 +169,14 @@ FPX_DEV double m_sqrtp(double x) {
   g = fma(d, h, g);
   return g;
 }
+FPX_DEV double m_sqrtp_c1(double x) {   // the v_min and 6 operations (47 cycles); x = 0: g = 0, r = 1/2, fma(0, 7/8, 0) = 0
+  const double y = __builtin_fmin(__builtin_amdgcn_rsq(x), 1.0e300);   // as above
+  const double g = x * y, h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  const double t = fma(r, 1.5, 1.0);
+  return fma(g, r * t, g);
+}
+FPX_DEV double m_sqrtp(double x) { return FPX_NEWTON_HW ? m_sqrtp_c1(x) : m_sqrtp_q2(x); }
 // log(x) for the x**y = exp(y*log x) of the turbulence profiles: argument reduction to
 // [sqrt(1/2), sqrt(2)) and the degree-7 series in s = f/(2+f) (the classical fdlibm scheme);
 // absolute error < 3e-16 * max(1, |log x|).  Zero, negative, subnormal, inf and NaN take the
@@ -262,9 +313,18 @@ FPX_DEV double m_exp_tab_nh(double u, TP tab /* kExpTab layout */) {
   p = fma(r, p, -0.5);
   return ldexp(fma(t, r * p, t), ki >> 5);
 }
-// x**(-1/3) for x in the f32 exponent range: f32 seed, two Newton steps r <- r + r*(1 - x*r^3)/3
-FPX_DEV double m_rcbrt(double x) {
-  double r = (double)__builtin_amdgcn_exp2f(__log2f((float)x) * (-1.0f / 3.0f));
+// is x a positive number the f32 seeds below can hold (2^-122 <= x < 2^122)?  One integer subtraction and one unsigned compare on
+// the high word instead of two fp64 compares: zero, negative numbers, subnormals, infinities and NaN all fall outside.
+FPX_DEV bool m_in_seed_range(double x) { return (unsigned int)(__double2hiint(x) - 0x38500000) < (unsigned int)(0x47900000 - 0x38500000); }
+// is x where the f32 seeds are good enough for ONE cubic step (2^-48 <= x < 2^64)?  The seeds' error grows with |log2 x| (the f32
+// logarithm is rounded to 2^-24 of its own size): measured on MI355X 2^-23.9 at x = 1, 2^-19.5 (x**(-1/3)) and 2^-20.0 (x**(-1/5))
+// at the ends of this window, 2^-18.1 and 2^-19.0 at the ends of the seed range, where the step's third-order term would be a
+// whole ulp.  The arguments of the Langevin loop (zeta, |skewness|, 12 - h/2L) lie inside; what does not takes two Newton steps.
+FPX_DEV bool m_in_cubic_range(double x) { return (unsigned int)(__double2hiint(x) - 0x3CF00000) < (unsigned int)(0x43F00000 - 0x3CF00000); }
+// x**(-1/3) for x in the f32 exponent range, from the f32 seed exp2(-log2(x)/3).  With e = 1 - x*r^3:
+// (1 - e)^(-1/3) = 1 + e/3 + 2/9 e^2 + 14/81 e^3 + ...
+FPX_DEV double m_rcbrt_seed(float l2) { return (double)__builtin_amdgcn_exp2f(l2 * (-1.0f / 3.0f)); }
+FPX_DEV double m_rcbrt_q2(double x, double r) {   // two Newton steps r <- r + r*(1 - x*r^3)/3: 10 operations
   const double third = 1.0 / 3.0;
 #pragma unroll
   for (int it = 0; it < 2; it++) {
@@ -273,6 +333,17 @@ FPX_DEV double m_rcbrt(double x) {
   }
   return r;
 }
+FPX_DEV double m_rcbrt_c1(double x, double r) {   // one cubic step r <- r + r*e*(1/3 + 2/9 e): 6 operations
+  const double e = fma(-(x * (r * r)), r, 1.0);
+  const double t = fma(e, 2.0 / 9.0, 1.0 / 3.0);
+  return fma(r * e, t, r);
+}
+template <bool CUBIC>
+FPX_DEV double m_rcbrt_refine(double x, double r) {
+  if (!CUBIC || __builtin_expect(!m_in_cubic_range(x), 0)) return m_rcbrt_q2(x, r);
+  return m_rcbrt_c1(x, r);
+}
+FPX_DEV double m_rcbrt(double x) { return m_rcbrt_refine<FPX_NEWTON_F32 != 0>(x, m_rcbrt_seed(__log2f((float)x))); }
 // exp(x): k = rint(x/ln2), r = x - k*ln2 (two-part ln2), exp(r) by the degree-13 Taylor polynomial
 // split into even and odd halves (|r| <= 0.347: truncation 4e-18), scaled by ldexp.  Leaves out the
 // library's range screening: v_ldexp_f64 saturates to 0 / inf by itself, NaN propagates.
@@ -414,55 +485,75 @@ FPX_DEV double m_coslat(double x) {
 // int -> fp64 conversion and a multiplication (8.7 issue cycles) in every fine sub-step; the same bits
 FPX_DEV double m_flip(double x, unsigned int flip) { return __hiloint2double(__double2hiint(x) ^ (int)flip, __double2loint(x)); }
 FPX_DEV float m_flip(float x, unsigned int flip) { return __uint_as_float(__float_as_uint(x) ^ flip); }
-// is x a positive number the f32 seeds below can hold (2^-122 <= x < 2^122)?  One integer subtraction and one unsigned compare on
-// the high word instead of two fp64 compares: zero, negative numbers, subnormals, infinities and NaN all fall outside.
-FPX_DEV bool m_in_seed_range(double x) { return (unsigned int)(__double2hiint(x) - 0x38500000) < (unsigned int)(0x47900000 - 0x38500000); }
 // x**0.8 for 0 <= x (hanna.f90:97, hanna_short.f90:80: tlw = 0.1*h/sigw*zeta**0.8): 0.8 = 4/5, so x**0.8 = x*r with
-// r = x**(-1/5) from an f32 seed and two Newton steps r <- r + r*(1 - x*r^5)/5 (the literal 0.8 differs from 4/5
-// by 4e-17: invisible).  19 instructions instead of log + exp (58).
+// r = x**(-1/5) from the f32 seed exp2(-log2(x)/5) (the literal 0.8 differs from 4/5 by 4.4e-17: times |ln x| < 45 under
+// 2e-15 where the cubic step is taken; outside that window the difference is put back).  With e = 1 - x*r^5:
+// (1 - e)^(-1/5) = 1 + e/5 + 3/25 e^2 + 11/125 e^3 + ...  Instead of log + exp (58 instructions).
 FPX_DEV float m_pow08(float x) { return x > 0.0f ? __expf(0.8f * __logf(x)) : 0.0f; }
-FPX_DEV double m_pow08(double x) {
-  if (__builtin_expect(!m_in_seed_range(x), 0)) return x > 0.0 ? m_expp(0.8 * m_logp(x)) : (x == 0.0 ? 0.0 : x * __builtin_nan(""));   // x < 0: NaN like pow
-  double r = (double)__builtin_amdgcn_exp2f(__log2f((float)x) * -0.2f);
+FPX_DEV double m_rfifth_seed(double x) { return (double)__builtin_amdgcn_exp2f(__log2f((float)x) * -0.2f); }
+FPX_DEV double m_rfifth_q2(double x, double r) {   // two Newton steps r <- r + r*(1 - x*r^5)/5: 12 operations
 #pragma unroll
   for (int it = 0; it < 2; it++) {
     const double r2 = r * r, r5 = (r2 * r2) * r;
     const double e = fma(-x, r5, 1.0);
     r = fma(r * 0.2, e, r);
   }
-  return x * r;
+  return r;
 }
+FPX_DEV double m_rfifth_c1(double x, double r) {   // one cubic step r <- r + r*e*(1/5 + 3/25 e): 7 operations
+  const double r2 = r * r, r5 = (r2 * r2) * r;
+  const double e = fma(-x, r5, 1.0);
+  const double t = fma(e, 0.12, 0.2);
+  return fma(r * e, t, r);
+}
+template <bool CUBIC>
+FPX_DEV double m_pow08_as(double x) {
+  if (__builtin_expect(!(CUBIC ? m_in_cubic_range(x) : m_in_seed_range(x)), 0)) {
+    if (CUBIC && m_in_seed_range(x)) {
+      // |ln x| > 33 here, up to 85, and the literal 0.8 of hanna.f90 and 4/5 stop being the same power to 3e-15:
+      // x**0.8 = x**(4/5) * (1 + (0.8 - 4/5) * ln x) with 0.8 - 4/5 = 2^-54 * 0.8 as a double has it.  Off the hot path.
+      const double p = x * m_rfifth_q2(x, m_rfifth_seed(x));
+      return fma(p, 4.440892098500626e-17 * (double)(__log2f((float)x) * 0.693147181f), p);
+    }
+    return x > 0.0 ? m_expp(0.8 * m_logp(x)) : (x == 0.0 ? 0.0 : x * __builtin_nan(""));   // x < 0: NaN like pow
+  }
+  return x * (CUBIC ? m_rfifth_c1(x, m_rfifth_seed(x)) : m_rfifth_q2(x, m_rfifth_seed(x)));
+}
+FPX_DEV double m_pow08(double x) { return m_pow08_as<FPX_NEWTON_F32 != 0>(x); }
 // c = x**0.333333333 and ic2 = x**(-2*0.333333333) for x > 0 (the two "cuberoot" calls of cbl.f90:115-121,
-// exponent as written at cbl.f90:227).  fp64: r = x**(-1/3) from an f32 seed and two Newton steps
-// r <- r + r*(1 - x*r^3)/3, then the difference between 1/3 and 0.333333333 as the first-order
-// factor exp(-+delta*ln x) with ln x from the f32 logarithm (delta = 3.3e-10, so its 1e-7 relative
-// error is invisible).  Arguments outside the f32 exponent range take the exp/log path.
+// exponent as written at cbl.f90:227).  fp64: r = x**(-1/3) from the f32 seed, refined as in m_rcbrt, then the difference
+// between 1/3 and 0.333333333 as the first-order factor exp(-+delta*ln x) with ln x from the f32 logarithm
+// (delta = 3.3e-10, so its 1e-7 relative error is invisible).  Arguments outside the f32 exponent range take the exp/log path.
 FPX_DEV void m_cuberoot_parts(float x, float &c, float &ic2) {
   const float l = __logf(x);
   c = __expf(0.333333333f * l);
   ic2 = __expf(-2.0f * 0.333333333f * l);
 }
-FPX_DEV void m_cuberoot_parts(double x, double &c, double &ic2) {
-  if (__builtin_expect(!m_in_seed_range(x), 0)) {
-    const double l = log(x);
-    c = exp(0.333333333 * l);
-    ic2 = exp(-2.0 * 0.333333333 * l);
-    return;
-  }
-  const float l2 = __log2f((float)x);
-  double r = (double)__builtin_amdgcn_exp2f(l2 * (-1.0f / 3.0f));
-  const double third = 1.0 / 3.0;
-#pragma unroll
-  for (int it = 0; it < 2; it++) {
-    const double e = fma(-(x * (r * r)), r, 1.0);
-    r = fma(r * third, e, r);
-  }
+FPX_DEV void m_cuberoot_finish(double x, float l2 /* log2 x */, double r /* x**(-1/3) */, double &c, double &ic2) {
   const double dl = (1.0 / 3.0 - 0.333333333) * (double)(l2 * 0.693147181f);   // delta * ln x
   const double rc = fma(r, dl, r);              // x**(-0.333333333)
   const double c0 = x * (r * r);                // x**(1/3)
   c = fma(-c0, dl, c0);                         // x**(0.333333333)
   ic2 = rc * rc;
 }
+template <bool CUBIC>
+FPX_DEV void m_cuberoot_parts_as(double x, double &c, double &ic2) {
+  if (__builtin_expect(!(CUBIC ? m_in_cubic_range(x) : m_in_seed_range(x)), 0)) {
+    if (CUBIC && m_in_seed_range(x)) {
+      const float l2 = __log2f((float)x);
+      m_cuberoot_finish(x, l2, m_rcbrt_q2(x, m_rcbrt_seed(l2)), c, ic2);
+      return;
+    }
+    const double l = log(x);
+    c = exp(0.333333333 * l);
+    ic2 = exp(-2.0 * 0.333333333 * l);
+    return;
+  }
+  const float l2 = __log2f((float)x);
+  const double r0 = m_rcbrt_seed(l2);
+  m_cuberoot_finish(x, l2, CUBIC ? m_rcbrt_c1(x, r0) : m_rcbrt_q2(x, r0), c, ic2);
+}
+FPX_DEV void m_cuberoot_parts(double x, double &c, double &ic2) { m_cuberoot_parts_as<FPX_NEWTON_F32 != 0>(x, c, ic2); }
 FPX_HD float m_fmod(float x, float y) { return fmodf(x, y); }
 FPX_HD double m_fmod(double x, double y) { return fmod(x, y); }
 FPX_HD double d_modulo(double a, double p) { double r = fmod(a, p); if (r != 0.0 && ((r < 0) != (p < 0))) r += p; return r; }

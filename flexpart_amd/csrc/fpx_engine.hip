@@ -1628,6 +1628,26 @@ __global__ void k_math_probe(int fn, const double *__restrict__ x, double *__res
     case 9: r = m_exp_tab(v, &kExpTab[0]); break;
     case 10: r = m_log_abs(v); break;
     case 11: r = m_rcbrt(v); break;
+    // 15 .. 18: the raw seeds the root helpers refine -- v_rcp_f64, v_rsq_f64, and the f32 paths of x**(-1/3) and x**(-1/5)
+    case 15: r = __builtin_amdgcn_rcp(v); break;
+    case 16: r = __builtin_amdgcn_rsq(v); break;
+    case 17: r = m_rcbrt_seed(__log2f((float)v)); break;
+    case 18: r = m_rfifth_seed(v); break;
+    // 19 .. 27, 31: the forms with two quadratic steps, whatever FPX_NEWTON_HW / FPX_NEWTON_F32 make the kernels call
+    case 19: r = m_rcp_q2(v); break;
+    case 20: r = m_rsqrt_q2(v); break;
+    case 21: r = m_sqrtp_q2(v); break;
+    case 22: m_sqrt_rsqrt_q2(v, c, ic2); r = c; break;
+    case 23: m_sqrt_rsqrt_q2(v, c, ic2); r = ic2; break;
+    case 24: r = m_rcbrt_q2(v, m_rcbrt_seed(__log2f((float)v))); break;
+    case 25: r = m_pow08_as<false>(v); break;
+    case 26: m_cuberoot_parts_as<false>(v, c, ic2); r = c; break;
+    case 27: m_cuberoot_parts_as<false>(v, c, ic2); r = ic2; break;
+    case 31: r = m_divf_with(3.0, v, m_rcp_q2(v)); break;
+    // 28 .. 30: the forms the kernels call that have no number above -- m_sqrt_rsqrt's two results, m_divf as 3/x
+    case 28: m_sqrt_rsqrt(v, c, ic2); r = c; break;
+    case 29: m_sqrt_rsqrt(v, c, ic2); r = ic2; break;
+    case 30: r = m_divf(3.0, v); break;
     default: m_cuberoot_parts(v, c, ic2); r = ic2; break;
   }
   y[i] = r;
@@ -5946,7 +5966,7 @@ int fpx_receptors_init(fpx_handle h, int32_t numreceptor, const void *xreceptor,
 int fpx_get_receptors(fpx_handle h, void *creceptor, int32_t ld, int32_t allreduce, int32_t clear) { FPX_GUARD(h); return h->impl->get_receptors(creceptor, ld, allreduce, clear); }
 
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n) {
-  if (fn < 0 || fn > 14 || !x || !y || n < 0) return FPX_ERR_ARG;
+  if (fn < 0 || fn > 31 || !x || !y || n < 0) return FPX_ERR_ARG;
   if (n == 0) return FPX_OK;
   const int64_t nin = (fn == 12 || fn == 13) ? 2 * n : n;   // fn 12, 13: x[0 .. n) the points, x[n .. 2n) their exp(-x*x)
   double *dx = nullptr, *dy = nullptr;
@@ -5954,7 +5974,7 @@ int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n) {
   if (hipMalloc(&dy, n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); return FPX_ERR_NOMEM; }
   hipError_t e = hipMemcpy(dx, x, nin * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    if (fn >= 12) fpx::k_erf_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(fn, dx, dy, n);
+    if (fn >= 12 && fn <= 14) fpx::k_erf_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(fn, dx, dy, n);
     else fpx::k_math_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(fn, dx, dy, n);
     e = hipGetLastError();
   }

@@ -706,7 +706,11 @@ void *fpx_stream(fpx_handle h);
  * 6 x**(-2*0.333333333) (m_cuberoot_parts), 7 m_erf_e(x, m_expp(-x*x)), 8 m_pow08,
  * 9 m_exp_tab, 10 m_log_abs, 11 m_rcbrt (the table-based helpers of the fine sub-step); 12 and 13 the error function of
  * cbl() with its Gaussian handed in -- x[0 .. n) the points, x[n .. 2n) their exp(-x*x), y[0 .. n) the result -- as the
- * polynomial form (m_erf_e2) and as the table form (m_erf_tab2); 14 exp(-x/2) (m_exp_tab_nh).  No reference counterpart; used by the parity tests to bound
+ * polynomial form (m_erf_e2) and as the table form (m_erf_tab2); 14 exp(-x/2) (m_exp_tab_nh);
+ * 15 .. 18 the raw seeds the root helpers refine (v_rcp_f64, v_rsq_f64, the f32 paths of x**(-1/3) and x**(-1/5)); 19 .. 27 the
+ * forms with two quadratic Newton steps of m_rcp, m_rsqrt, m_sqrtp, m_sqrt_rsqrt (22 the root, 23 its reciprocal), m_rcbrt,
+ * m_pow08, m_cuberoot_parts (26, 27 as 5, 6) and 31 of m_divf(3, x); 28, 29 the two results of m_sqrt_rsqrt and 30 m_divf(3, x)
+ * as the kernels call them.  No reference counterpart; used by the parity tests to bound
  * the helpers against libm.  Returns 0 or a negative fpx_status. */
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n);
 /* Diagnostics: the turbulence profiles of one Langevin pass (hanna.f90) for n points in[5i..5i+4] = h, ol, ust, wst, z: ten values
