@@ -25,6 +25,7 @@
 #include "fpx_calcpar.hpp"
 #include "fpx_getvdep.hpp"
 #include "fpx_calcpv.hpp"
+#include "fpx_calcfluxes.hpp"
 #include "fpx_convect.hpp"
 #include "fpx_rng_host.hpp"
 
@@ -2105,6 +2106,9 @@ struct EngineBase {
   virtual int set_output_times(int loutnext, int loutstep) = 0;
   virtual int conccalc(int itime, double weight) = 0;
   virtual int get_grids(void *gridunc, void *drygridunc, int allreduce, int clear) = 0;
+  virtual int get_flux(void *flux, int allreduce, int clear) = 0;
+  virtual int fluxoutput(int itime, const fpx_fluxout *f, const char *prefix, int reduced) = 0;
+  virtual int calcfluxes_time(double *ms, long long *launches, int reset) = 0;
   virtual int count_particles(int64_t *local, int64_t *total, int allreduce) = 0;
   virtual int lane_stats(uint64_t *out, int n, int reset) = 0;
   virtual int set_option(const char *name, const char *value) = 0;
@@ -2325,7 +2329,9 @@ struct Engine : EngineBase {
     if (cfg.ifine < 1) return fail(FPX_ERR_ARG, "ifine must be >= 1");
     if (cfg.lsynctime == 0 || std::abs((long long)cfg.lsynctime) > 65535) return fail(FPX_ERR_ARG, "lsynctime must be non-zero and at most 65535 s in magnitude (the hand-over record of the Langevin kernel keeps |itimec - itime| in 16 bits)");
     if (cfg.ipout == 3) return fail(FPX_ERR_UNSUPPORTED, "ipout = 3: the particle loop's partpos_average (timemanager.f90:617) is not computed by this engine");
-    if (cfg.iflux == 1) return fail(FPX_ERR_UNSUPPORTED, "iflux = 1: the particle loop's calcfluxes (timemanager.f90:623) is not computed by this engine");
+    if (cfg.device_flux != 0 && cfg.device_flux != 1) return fail(FPX_ERR_ARG, "device_flux must be 0 or 1");
+    if (cfg.device_flux == 1 && cfg.iflux != 1) return fail(FPX_ERR_ARG, "device_flux = 1 without iflux = 1: there is no flux to compute");
+    if (cfg.iflux == 1 && !cfg.device_flux) return fail(FPX_ERR_UNSUPPORTED, "iflux = 1: the particle loop's calcfluxes (timemanager.f90:623) is not computed by this engine");
     if (cfg.linit_cond >= 1) return fail(FPX_ERR_UNSUPPORTED, "linit_cond >= 1: the particle loop's initial_cond_calc (timemanager.f90:631,702) is not computed by this engine");
     if (cfg.lsettling && cfg.compute_real_bytes == 4 && (long long)cfg.nx * cfg.ny > (1ll << 24)) return fail(FPX_ERR_ARG, "lsettling with the f32 engine: nx*ny must not exceed 2^24 (the Langevin kernel keeps the column index of get_settling in an f32 stash slot)");
     if (cfg.blend_mode < 0 || cfg.blend_mode > 2) return fail(FPX_ERR_ARG, "blend_mode must be 0 (automatic), 1 (on) or 2 (off)");
@@ -2462,6 +2468,7 @@ struct Engine : EngineBase {
     if (stream) (void)hipStreamSynchronize(stream);
     for (auto &e : pinned_host) (void)hipHostUnregister(const_cast<void *>(e.first));
     for (auto &e : ev_pool) for (int i = 0; i < 5; i++) (void)hipEventDestroy(e.e[i]);
+    for (auto &e : fx_ev_pool) for (int i = 0; i < 4; i++) (void)hipEventDestroy(e.e[i]);
     for (void *q : owned) (void)hipFree(q);
     if (staging) (void)hipFree(staging);
     if (d_sort_tmp) (void)hipFree(d_sort_tmp);
@@ -3005,7 +3012,7 @@ struct Engine : EngineBase {
 
   // caldate.f90:42-65 (the date part), its default-real literals in the host's real kind H
   template <typename H>
-  static int gv_caldate(double juldate) {
+  static int gv_caldate(double juldate, int *hhmiss = nullptr) {
 #pragma clang fp contract(off)
     int julday = (int)juldate;
     if ((juldate - julday) * 86400. >= 86399.5) {
@@ -3027,6 +3034,14 @@ struct Engine : EngineBase {
     int yyyy = jc - 4715;
     if (mm > 2) yyyy = yyyy - 1;
     if (yyyy <= 0) yyyy = yyyy - 1;
+    if (hhmiss) {   // caldate.f90:66-78
+      int hh = (int)(24. * (juldate - (double)julday));
+      int mi = (int)(1440. * (juldate - (double)julday) - 60. * (double)hh);
+      int ss = (int)std::lround(86400. * (juldate - (double)julday) - 3600. * (double)hh - 60. * (double)mi);
+      if (ss == 60) { ss = 0; mi = mi + 1; }
+      if (mi == 60) { mi = 0; hh = hh + 1; }
+      *hhmiss = 10000 * hh + 100 * mi + ss;
+    }
     return 10000 * yyyy + 100 * mm + dd;
   }
   // getvdep.f90:51-77: the seasonal category of every grid row at wind-field time wftime
@@ -4187,6 +4202,7 @@ struct Engine : EngineBase {
     if (c->nuvz < 4 || c->nconvlev < 2 || c->nconvlev > c->nuvz - 2) return fail(FPX_ERR_ARG, "conv_init: need 2 <= nconvlev <= nuvz - 2");
     if (!c->akz || !c->bkz || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "conv_init: akz, bkz, akm, bkm are required");
     if (conv_on) return fail(FPX_ERR_STATE, "conv_init: already initialised");
+    if (cfg.device_flux) return fail(FPX_ERR_UNSUPPORTED, "conv_init: device_flux = 1: the calcfluxes calls of the convective displacement (convmix.f90:208-220,284-296) are not computed by this engine");
     const size_t hb = (size_t)cfg.host_real_bytes;
     int rc;
     const void *tabs[4] = {c->akz, c->bkz, c->akm, c->bkm};
@@ -4603,6 +4619,10 @@ struct Engine : EngineBase {
     }
     return 0;
   }
+  // header.reserved, bit 0: the file ends with the flux grid of a run with device_flux (uint64 count, then the values in the
+  // host's real kind); a file without fluxes has reserved = 0 and is what it always was
+  static constexpr int32_t kCkptFlux = 1;
+  uint64_t ckpt_flux_bytes(const CkptHeader &h) const { return (h.reserved & kCkptFlux) ? 8 + (uint64_t)n_flux * cfg.host_real_bytes : 0; }
   struct CkptRng { HostRng<float> r4; HostRng<double> r8; Ran1 rel; };
   uint64_t conv_cbase_bytes() const {      // cbaseflux of the mother grid and of every nest that has convection fields
     if (!conv_on) return 0;
@@ -4630,7 +4650,8 @@ struct Engine : EngineBase {
     h.cbase_bytes = conv_cbase_bytes();
     h.rel_global_count = rel_global_count;
     ckpt_describe_grid(h);
-    h.total_bytes = ckpt_total_bytes(h);
+    h.reserved = cfg.device_flux && fx_flux ? kCkptFlux : 0;      // the flux section follows cbaseflux: a count and the values
+    h.total_bytes = ckpt_total_bytes(h) + ckpt_flux_bytes(h);
     if (fwrite(&h, sizeof(h), 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
     CkptRng rs{rng4, rng8, rel_ran1};
     if (fwrite(&rs, sizeof(rs), 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
@@ -4651,6 +4672,11 @@ struct Engine : EngineBase {
     if (h.cbase_bytes)
       for (int g = 0; g <= V.numbnests; g++)
         if (conv_cb[g] && (rc = ckpt_put_plain(fh, (const unsigned char *)conv_cb[g], conv_cb_bytes(g), buf))) return rc;
+    if (h.reserved & kCkptFlux) {
+      const uint64_t cnt = n_flux;
+      if (fwrite(&cnt, 8, 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
+      if ((rc = ckpt_put_plain(fh, (const unsigned char *)fx_flux, n_flux * cfg.host_real_bytes, buf))) return rc;
+    }
     closer.f = nullptr;
     if (fclose(fh) != 0) return fail(FPX_ERR_ARG, std::string("checkpoint_write: write error on ") + path);
     return 0;
@@ -4681,11 +4707,19 @@ struct Engine : EngineBase {
         return fail(FPX_ERR_ARG, "checkpoint_read: written on another grid (nx, ny, nz, maxspec or the nest extents differ)");
       if (mine.pad != h.pad) return fail(FPX_ERR_ARG, "checkpoint_read: written with (without) DRYBKDEP / WETBKDEP");
       // the whole file must be there before a single array is touched
-      if (h.total_bytes != ckpt_total_bytes(h)) return fail(FPX_ERR_ARG, "checkpoint_read: inconsistent header");
+      if ((h.reserved & ~kCkptFlux) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: unknown sections in the file");
+      if (((h.reserved & kCkptFlux) != 0) != (cfg.device_flux && fx_flux))
+        return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_flux; create the engine alike and call fpx_outgrid_init first");
+      if (h.total_bytes != ckpt_total_bytes(h) + ckpt_flux_bytes(h)) return fail(FPX_ERR_ARG, "checkpoint_read: inconsistent header");
       if (fseek(fh, 0, SEEK_END) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: cannot seek");
       const long long len = (long long)ftell(fh);
       if (len < 0 || (uint64_t)len != h.total_bytes)
         return fail(FPX_ERR_ARG, "checkpoint_read: the file is truncated or has trailing bytes (" + std::to_string(len) + " bytes, header says " + std::to_string(h.total_bytes) + "); nothing was restored");
+      if (h.reserved & kCkptFlux) {
+        uint64_t cnt = 0;
+        if (fseek(fh, (long)ckpt_total_bytes(h), SEEK_SET) != 0 || fread(&cnt, 8, 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_read: cannot read the flux section");
+        if (cnt != (uint64_t)n_flux) return fail(FPX_ERR_STATE, "checkpoint_read: the flux grid of the checkpoint is not the one configured");
+      }
       if (fseek(fh, (long)sizeof(h), SEEK_SET) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: cannot seek");
     }
     CkptRng rs;
@@ -4717,6 +4751,12 @@ struct Engine : EngineBase {
     if (h.cbase_bytes)
       for (int g = 0; g <= V.numbnests; g++)
         if (conv_cb[g] && (rc = ckpt_get_plain(fh, (unsigned char *)conv_cb[g], conv_cb_bytes(g), buf))) return ckpt_invalidate(rc);
+    if (h.reserved & kCkptFlux) {
+      uint64_t cnt = 0;
+      if (fread(&cnt, 8, 1, fh) != 1) return ckpt_invalidate(fail(FPX_ERR_ARG, "checkpoint_read: file too short"));
+      if ((rc = ckpt_get_plain(fh, (unsigned char *)fx_flux, n_flux * cfg.host_real_bytes, buf))) return ckpt_invalidate(rc);
+      fx_red_valid = false;
+    }
     for (bool &v : red_valid) v = false;
     rng4 = rs.r4; rng8 = rs.r8; rel_ran1 = rs.rel;
     step_counter = h.step_counter;
@@ -4857,8 +4897,10 @@ struct Engine : EngineBase {
       return fail(FPX_ERR_STATE, "step: the release-point tables xmass, npart are needed for the mass-fraction test (fpx_set_release_points)");
     for (int l = 0; l < V.numbnests; l++)
       if (!nest_loaded[l][0] || !nest_loaded[l][1]) return fail(FPX_ERR_STATE, "step: nest fields missing (fpx_upload_nest_fields, both slots)");
+    if (cfg.device_flux && !Gp.on) return fail(FPX_ERR_STATE, "step: device_flux = 1 needs the output grid the fluxes are counted on (fpx_outgrid_init)");
     if (out) memset(out, 0, sizeof(*out));
     if (numpart == 0) return 0;
+    if (cfg.device_flux) { const int rc = flux_prepare(); if (rc) return rc; }
     if (cfg.drydep) red_valid[RG_DRY] = red_valid[RG_DRYN] = false;
     if (cfg.sort_interval > 0 && step_counter > 0 && step_counter % (unsigned)cfg.sort_interval == 0) {
       int rc = sort_particles();
@@ -4926,10 +4968,17 @@ struct Engine : EngineBase {
     // longer share cache lines).
     V.pbl_cost_buckets = opt.pbl_cost_buckets >= 0 ? opt.pbl_cost_buckets : (numpart < 50000000ll ? 3 : 0);
     { const int rc = blend_winds(itime); if (rc) return rc; }      // its own kernel (k_blend_w3), ahead of the per-kernel events
-    HIPCHK(hipEventRecord(ev.e[0], stream));
+    // device_flux: k_flux_save must follow the receptor block, and fpx_kernel_times' first interval must not hold it -- the
+    // interval then opens behind both (without device_flux the order is what it always was)
+    if (!cfg.device_flux) HIPCHK(hipEventRecord(ev.e[0], stream));
     if (P.xscav) {   // timemanager.f90:564-598, before the particle is moved
       k_bkdep<R><<<nb, kBlock, 0, stream>>>(V, Wp, P, numpart, itime, cfg.drybkdep, cfg.wetbkdep, d_zspan);
       HIPCHK(hipGetLastError());
+    }
+    if (cfg.device_flux) {   // timemanager.f90:560-562 -- after the receptor block, which may zero xmass1 (:578,593)
+      const int rc = cfg.host_real_bytes == 4 ? flux_launch<float>(false, itime) : flux_launch<double>(false, itime);
+      if (rc) return rc;
+      HIPCHK(hipEventRecord(ev.e[0], stream));
     }
     {
       // specialised variants: dry deposition (aerosols), initialize() only when new particles can
@@ -4975,6 +5024,10 @@ struct Engine : EngineBase {
     }
     HIPCHK(hipEventRecord(ev.e[3], stream));
     HIPCHK(hipGetLastError());
+    if (cfg.device_flux) {   // timemanager.f90:623
+      const int rc = cfg.host_real_bytes == 4 ? flux_launch<float>(true, itime) : flux_launch<double>(true, itime);
+      if (rc) return rc;
+    }
     V.w3t0 = nullptr; V.w3t1 = nullptr; V.r2t0 = nullptr;      // the blended packs belong to this step's itime only
     if (opt.verbose > 1) {   // the lists of the launches (a synchronisation per step: diagnostics only)
       unsigned int hc[kCtrWords];
@@ -5305,6 +5358,10 @@ struct Engine : EngineBase {
     HIPCHK(hipMemsetAsync(Gp.drygridunc, 0, n_grid2 * sizeof(float), stream));
     HIPCHK(hipStreamSynchronize(stream));
     Gp.nested = 0; Gp.numreceptor = 0;
+    if (cfg.device_flux) {
+      rc = cfg.host_real_bytes == 4 ? flux_init_t<float>(g, outheight) : flux_init_t<double>(g, outheight);
+      if (rc) return rc;
+    }
     Gp.on = 1;
     return 0;
   }
@@ -5525,6 +5582,214 @@ struct Engine : EngineBase {
     // cumulative over the run (zeroed once, outgrid_init.f90:317-318)
     if (clear) HIPCHK(hipMemsetAsync(Gp.gridunc, 0, n_grid3 * sizeof(R), stream));
     HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+
+  // ---- gross mass fluxes (fpx_calcfluxes.hpp; fpx_config.device_flux) ------------------------------------------
+  // flux and everything the kernels compare a position with are kept in the host's real kind H, whatever the engine
+  // computes in: calcfluxes.f90 declares them default real.
+  void *fx_flux = nullptr, *fx_flux0 = nullptr;        // flux_mod's flux; the receive buffer of its reduction
+  void *fx_outh = nullptr, *fx_outhh = nullptr;        // outheight, outheighthalf in H
+  void *fx_xold = nullptr, *fx_yold = nullptr, *fx_zold = nullptr, *fx_mass = nullptr;
+  unsigned char *fx_due = nullptr;
+  size_t n_flux = 0;
+  double fx_geo[4] = {};                               // dxout, dyout, xoutshift, youtshift as the host passed them
+  bool fx_red_valid = false;
+  struct FluxEvents { hipEvent_t e[4]; };
+  std::vector<FluxEvents> fx_ev_pool;
+  size_t fx_ev_used = 0;
+  double fx_acc_ms = 0;
+  long long fx_acc_launches = 0;
+  template <typename H>
+  int flux_init_t(const fpx_outgrid *g, const void *outheight) {
+    n_flux = (size_t)6 * g->numxgrid * g->numygrid * g->numzgrid * cfg.nspec * g->maxpointspec_act * g->nageclass;
+    fx_geo[0] = g->dxout; fx_geo[1] = g->dyout; fx_geo[2] = g->xoutshift; fx_geo[3] = g->youtshift;
+    std::vector<H> oh((const H *)outheight, (const H *)outheight + g->numzgrid), ohh(g->numzgrid);
+    {
+#pragma clang fp contract(off)
+      ohh[0] = oh[0] / (H)2.;                          // readoutgrid.f90:194-196
+      for (int j = 1; j < g->numzgrid; j++) ohh[j] = (oh[j - 1] + oh[j]) / (H)2.;
+    }
+    int rc;
+    H *a, *b, *f;
+    if ((rc = dalloc(&a, (size_t)g->numzgrid)) || (rc = dalloc(&b, (size_t)g->numzgrid)) || (rc = dalloc(&f, n_flux))) return rc;
+    HIPCHK(hipMemcpyAsync(a, oh.data(), g->numzgrid * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(b, ohh.data(), g->numzgrid * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(f, 0, n_flux * sizeof(H), stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    fx_outh = a; fx_outhh = b; fx_flux = f;
+    return 0;
+  }
+  // the scratch of k_flux_save (allocated at the first step that needs it) and an event set for this step
+  int flux_prepare() {
+    if (!fx_due) {
+      const size_t cap = (size_t)P.cap, hb = (size_t)cfg.host_real_bytes;
+      unsigned char *q;
+      int rc;
+      if ((rc = dalloc(&q, cap * hb))) return rc; fx_xold = q;
+      if ((rc = dalloc(&q, cap * hb))) return rc; fx_yold = q;
+      if ((rc = dalloc(&q, cap * hb))) return rc; fx_zold = q;
+      if ((rc = dalloc(&q, cap * hb * cfg.nspec))) return rc; fx_mass = q;
+      if ((rc = dalloc(&fx_due, cap))) return rc;
+    }
+    if (fx_ev_used >= 64) { const int rc = flux_harvest(); if (rc) return rc; }
+    if (fx_ev_used == fx_ev_pool.size()) {
+      FluxEvents fe;
+      for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&fe.e[i]));
+      fx_ev_pool.push_back(fe);
+    }
+    return 0;      // set fx_ev_used is this step's; it counts once both kernels are in the stream (flux_launch)
+  }
+  template <typename H>
+  cf::Args<H> flux_args() const {
+    cf::Args<H> A;
+    A.numxgrid = Gp.numxgrid; A.numygrid = Gp.numygrid; A.numzgrid = Gp.numzgrid; A.nspec = cfg.nspec;
+    A.maxpointspec_act = Gp.maxpointspec_act; A.nageclass = Gp.nageclass;
+    A.use_npoint = Gp.ioutputforeachrelease == 1 && cfg.mdomainfill == 0;
+    A.nx = cfg.nx; A.nxmin1 = cfg.nx - 1;
+    for (int i = 0; i < cf::kMaxAgeCf; i++) A.lage[i] = Gp.lage[i];
+    A.dx = (H)cfg.dx; A.dy = (H)cfg.dy; A.dxout = (H)fx_geo[0]; A.dyout = (H)fx_geo[1]; A.xoutshift = (H)fx_geo[2]; A.youtshift = (H)fx_geo[3];
+    A.outheight = (const H *)fx_outh; A.outheighthalf = (const H *)fx_outhh; A.flux = (H *)fx_flux;
+    A.xold = (H *)fx_xold; A.yold = (H *)fx_yold; A.zold = (H *)fx_zold; A.mass = (H *)fx_mass; A.due = fx_due; A.cap = P.cap;
+    return A;
+  }
+  template <typename H>
+  int flux_launch(bool after, int itime) {
+    static_assert(cf::kMaxAgeCf == kMaxAge, "age-class limit");
+    const cf::Args<H> A = flux_args<H>();
+    FluxEvents &fe = fx_ev_pool[fx_ev_used];
+    const int nb = (int)((numpart + 255) / 256);
+    HIPCHK(hipEventRecord(fe.e[after ? 2 : 0], stream));
+    if (!after) cf::k_flux_save<H, R><<<nb, 256, 0, stream>>>(A, P.xt, P.yt, P.zt, P.xmass1, P.itra1, P.cap, numpart, itime);
+    else cf::k_calcfluxes<H, R><<<nb, 256, 0, stream>>>(A, P.xt, P.yt, P.zt, P.npoint, P.itramem, numpart, itime);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(fe.e[after ? 3 : 1], stream));
+    if (after) { fx_ev_used++; fx_red_valid = false; }   // the partial sums move on
+    return 0;
+  }
+  int flux_harvest() {
+    HIPCHK(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < fx_ev_used; i++) {
+      float t = 0;
+      HIPCHK(hipEventElapsedTime(&t, fx_ev_pool[i].e[0], fx_ev_pool[i].e[1])); fx_acc_ms += t;
+      HIPCHK(hipEventElapsedTime(&t, fx_ev_pool[i].e[2], fx_ev_pool[i].e[3])); fx_acc_ms += t;
+      fx_acc_launches++;
+    }
+    fx_ev_used = 0;
+    return 0;
+  }
+  int calcfluxes_time(double *ms, long long *launches, int reset) override {
+    const int rc = flux_harvest();
+    if (rc) return rc;
+    if (ms) *ms = fx_acc_ms;
+    if (launches) *launches = fx_acc_launches;
+    if (reset) { fx_acc_ms = 0; fx_acc_launches = 0; }
+    return 0;
+  }
+  template <typename H>
+  int flux_reduce_t() {
+    H *recv = (H *)fx_flux0;
+    const int rc = reduce_into((const H *)fx_flux, &recv, n_flux, "get_flux");
+    fx_flux0 = recv;
+    if (!rc) fx_red_valid = true;
+    return rc;
+  }
+  int get_flux(void *flux, int allreduce, int clear) override {
+    if (!cfg.device_flux) return fail(FPX_ERR_STATE, "get_flux: the engine was created without device_flux");
+    if (!Gp.on || !fx_flux) return fail(FPX_ERR_STATE, "get_flux: fpx_outgrid_init first");
+    const void *src = fx_flux;
+    if (allreduce && comm_ranks > 1) {
+      const int rc = cfg.host_real_bytes == 4 ? flux_reduce_t<float>() : flux_reduce_t<double>();
+      if (rc) return rc;
+      src = fx_flux0;
+    }
+    if (flux) HIPCHK(hipMemcpyAsync(flux, src, n_flux * cfg.host_real_bytes, hipMemcpyDeviceToHost, stream));
+    if (clear) HIPCHK(hipMemsetAsync(fx_flux, 0, n_flux * cfg.host_real_bytes, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  // fluxoutput.f90:46-283 on the host from the downloaded grid (the grid is small next to the particles, and the file is
+  // written record by record anyway), in the host's real kind
+  template <typename H>
+  int fluxoutput_t(int itime, const fpx_fluxout *f, const char *prefix, const void *src) {
+#pragma clang fp contract(off)
+    std::vector<H> fl(n_flux);
+    HIPCHK(hipMemcpyAsync(fl.data(), src, n_flux * sizeof(H), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const int nxg = Gp.numxgrid, nyg = Gp.numygrid, nzg = Gp.numzgrid, ns = cfg.nspec, nkp = Gp.maxpointspec_act, na = Gp.nageclass;
+    const H *area = (const H *)f->area, *areaeast = (const H *)f->areaeast, *areanorth = (const H *)f->areanorth;
+    const H outstep = (H)f->outstep;
+    auto at = [&](int i, int ix, int jy, int kz, int k, int kp, int nage) -> H {   // i, kz 1-based; the others 0-based
+      return fl[(size_t)(i - 1) + 6 * ((size_t)ix + (size_t)nxg * ((size_t)jy + (size_t)nyg * ((size_t)(kz - 1) + (size_t)nzg * ((size_t)k + (size_t)ns * ((size_t)kp + (size_t)nkp * (size_t)nage)))))];
+    };
+    int hhmiss = 0;
+    const int yyyymmdd = gv_caldate<H>(f->bdate + (double)itime / 86400., &hhmiss);
+    char name[1200];
+    snprintf(name, sizeof name, "%sgrid_flux_%08d%06d", prefix, yyyymmdd, hhmiss);
+    FILE *fh = fopen(name, "wb");
+    if (!fh) return fail(FPX_ERR_ARG, std::string("fluxoutput: cannot open ") + name);
+    std::vector<unsigned char> rec;                    // one unformatted sequential record: length, payload, length
+    bool ok = true;
+    auto put = [&](const void *q, size_t n) { const unsigned char *c = (const unsigned char *)q; rec.insert(rec.end(), c, c + n); };
+    auto flush = [&]() {
+      const int32_t len = (int32_t)rec.size();
+      ok = ok && fwrite(&len, 4, 1, fh) == 1 && (rec.empty() || fwrite(rec.data(), 1, rec.size(), fh) == rec.size()) && fwrite(&len, 4, 1, fh) == 1;
+      rec.clear();
+    };
+    auto put_int = [&](int32_t v) { put(&v, 4); flush(); };
+    // :61-134: cells per (species, age class) over all kp, and the sparse test
+    std::vector<int> ncells((size_t)6 * ns * na, 0);
+    for (int k = 0; k < ns; k++) for (int kp = 0; kp < nkp; kp++) for (int nage = 0; nage < na; nage++)
+      for (int jy = 0; jy < nyg; jy++) for (int ix = 0; ix < nxg; ix++) for (int kz = 1; kz <= nzg; kz++)
+        for (int i = 1; i <= 6; i++) if (at(i, ix, jy, kz, k, kp, nage) > (H)0) ncells[(size_t)(i - 1) + 6 * ((size_t)k + (size_t)ns * nage)]++;
+    put_int(itime);
+    const int order[6] = {2, 1, 3, 4, 5, 6};           // eastward, westward, south, north, up, down (:146-276)
+    for (int k = 0; k < ns && ok; k++) for (int kp = 0; kp < nkp && ok; kp++) for (int nage = 0; nage < na && ok; nage++)
+      for (int d = 0; d < 6; d++) {
+        const int i = order[d];
+        auto value = [&](int ix, int jy, int kz) -> H {
+          const H a = i <= 2 ? areaeast[(size_t)ix + (size_t)nxg * ((size_t)jy + (size_t)nyg * (size_t)(kz - 1))]
+                    : i <= 4 ? areanorth[(size_t)ix + (size_t)nxg * ((size_t)jy + (size_t)nyg * (size_t)(kz - 1))] : area[(size_t)ix + (size_t)nxg * (size_t)jy];
+          return (H)1.e12 * at(i, ix, jy, kz, k, kp, nage) / a / outstep;
+        };
+        if (4 * ncells[(size_t)(i - 1) + 6 * ((size_t)k + (size_t)ns * nage)] < nxg * nyg * nzg) {
+          put_int(1);
+          for (int kz = 1; kz <= nzg; kz++) for (int jy = 0; jy < nyg; jy++) for (int ix = 0; ix < nxg; ix++)
+            if (at(i, ix, jy, kz, k, kp, nage) > (H)0) {
+              const int32_t idx = ix + jy * nxg + kz * nxg * nyg;
+              const H v = value(ix, jy, kz);
+              put(&idx, 4); put(&v, sizeof(H)); flush();
+            }
+          const int32_t m = -999; const H e = (H)999.;
+          put(&m, 4); put(&e, sizeof(H)); flush();
+        } else {
+          put_int(2);
+          for (int kz = 1; kz <= nzg; kz++) for (int ix = 0; ix < nxg; ix++) {
+            for (int jy = 0; jy < nyg; jy++) { const H v = value(ix, jy, kz); put(&v, sizeof(H)); }
+            flush();
+          }
+        }
+      }
+    ok = (fclose(fh) == 0) && ok;
+    if (!ok) return fail(FPX_ERR_ARG, std::string("fluxoutput: write error on ") + name);
+    return 0;
+  }
+  int fluxoutput(int itime, const fpx_fluxout *f, const char *prefix, int reduced) override {
+    if (!cfg.device_flux) return fail(FPX_ERR_STATE, "fluxoutput: the engine was created without device_flux");
+    if (!Gp.on || !fx_flux) return fail(FPX_ERR_STATE, "fluxoutput: fpx_outgrid_init first");
+    if (!f || f->struct_bytes != (int32_t)sizeof(fpx_fluxout)) return fail(FPX_ERR_ARG, "fluxoutput: null or fpx_fluxout size mismatch (ABI)");
+    if (!f->area || !f->areaeast || !f->areanorth || !prefix) return fail(FPX_ERR_ARG, "fluxoutput: area, areaeast, areanorth and the path prefix are required");
+    if (strlen(prefix) > 1000) return fail(FPX_ERR_ARG, "fluxoutput: prefix too long");
+    const void *src = fx_flux;
+    if (reduced && comm_ranks > 1) {
+      if (!fx_red_valid) return fail(FPX_ERR_STATE, "fluxoutput: reduced = 1 needs fpx_get_flux with allreduce = 1 first");
+      src = fx_flux0;
+    }
+    const int rc = cfg.host_real_bytes == 4 ? fluxoutput_t<float>(itime, f, prefix, src) : fluxoutput_t<double>(itime, f, prefix, src);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(fx_flux, 0, n_flux * cfg.host_real_bytes, stream));     // :289-303
+    HIPCHK(hipStreamSynchronize(stream));
+    fx_red_valid = false;
     return 0;
   }
 
@@ -5937,6 +6202,15 @@ int fpx_outgrid_init(fpx_handle h, const fpx_outgrid *g, const void *outheight) 
 int fpx_set_output_times(fpx_handle h, int32_t loutnext, int32_t loutstep) { FPX_GUARD(h); return h->impl->set_output_times(loutnext, loutstep); }
 int fpx_conccalc(fpx_handle h, int32_t itime, double weight) { FPX_GUARD(h); return h->impl->conccalc(itime, weight); }
 int fpx_get_grids(fpx_handle h, void *gridunc, void *drygridunc, int32_t allreduce, int32_t clear) { FPX_GUARD(h); return h->impl->get_grids(gridunc, drygridunc, allreduce, clear); }
+int fpx_get_flux(fpx_handle h, void *flux, int32_t allreduce, int32_t clear) { FPX_GUARD(h); return h->impl->get_flux(flux, allreduce, clear); }
+int fpx_fluxoutput(fpx_handle h, int32_t itime, const fpx_fluxout *f, const char *prefix, int32_t reduced) { FPX_GUARD(h); return h->impl->fluxoutput(itime, f, prefix, reduced); }
+int fpx_calcfluxes_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset) {
+  FPX_GUARD(h);
+  long long l = 0;
+  const int rc = h->impl->calcfluxes_time(ms, &l, reset);
+  if (launches) *launches = l;
+  return rc;
+}
 int fpx_comm_unique_id(void *id, int32_t nbytes) {
   if (!id || nbytes != (int32_t)sizeof(ncclUniqueId)) return fpx::fail(FPX_ERR_ARG, "fpx_comm_unique_id: the id is 128 bytes");
   ncclUniqueId uid;

@@ -106,6 +106,7 @@ class Engine:
         self.bkdep = bool(cfg.drybkdep or cfg.wetbkdep)
         cfg.turboff, cfg.interpolhmix = int(sc.get("turboff", 0)), int(sc.get("interpolhmix", 0))   # com_mod.f90:777-778
         cfg.ipout, cfg.iflux, cfg.linit_cond = int(sc.get("ipout", 0)), int(sc.get("iflux", 0)), int(sc.get("linit_cond", 0))   # refused when set
+        cfg.device_flux = int(sc.get("device_flux", 0))   # iflux = 1 is accepted with it: the fluxes are computed here (get_flux, fluxoutput)
         cfg.blend_mode = int(blend_mode)                # 0: from global_particles, 1 on, 2 off
         cfg.global_particles = int(global_particles)    # the run's particle count over all ranks
         cfg.pbl_slice_passes = int(pbl_slice_passes)    # 0: the engine's schedule, -1: one launch, k: k passes per launch
@@ -521,6 +522,37 @@ class Engine:
         self.numparticlecount = int(npc.value)
         return self.itime, self.n, self.numparticlecount
 
+    def get_flux(self, allreduce=False, clear=False):
+        """fpx_get_flux: the gross mass fluxes accumulated since the last clear (device_flux = 1), in the host's real
+        kind, shape (nageclass, maxpointspec_act, nspec, numzgrid, numygrid, numxgrid, 6)."""
+        out = np.zeros(self.fshape, self.hreal)
+        check(self.lib.fpx_get_flux(self.h, _vp(out), int(allreduce), int(clear)), "fpx_get_flux")
+        return out
+
+    def fluxoutput(self, itime, prefix, area, areaeast, areanorth, outstep, bdate, reduced=False):
+        """fpx_fluxoutput: writes <prefix>grid_flux_<date><time> (fluxoutput.f90) and zeroes the device's flux;
+        returns the file name."""
+        from ._lib import FpxFluxout
+        rt = self.hreal
+        a = np.ascontiguousarray(np.asarray(area, dtype=rt))
+        ae = np.ascontiguousarray(np.asarray(areaeast, dtype=rt))
+        an = np.ascontiguousarray(np.asarray(areanorth, dtype=rt))
+        nzg, nyg, nxg = self.fshape[3:6]
+        if a.shape != (nyg, nxg) or ae.shape != (nzg, nyg, nxg) or an.shape != (nzg, nyg, nxg):
+            raise ValueError("fluxoutput: area [numygrid][numxgrid], areaeast and areanorth [numzgrid][numygrid][numxgrid]")
+        f = FpxFluxout(C.sizeof(FpxFluxout), 0, float(bdate), float(rt(outstep)), a.ctypes.data, ae.ctypes.data, an.ctypes.data)
+        import glob
+        before = set(glob.glob(str(prefix) + "grid_flux_*"))
+        check(self.lib.fpx_fluxoutput(self.h, int(itime), C.byref(f), str(prefix).encode(), int(reduced)), "fpx_fluxoutput")
+        new = sorted(set(glob.glob(str(prefix) + "grid_flux_*")) - before)
+        return new[0] if new else None
+
+    def calcfluxes_time(self, reset=False):
+        """fpx_calcfluxes_time: (device ms of k_flux_save + k_calcfluxes since the last reset, steps that ran them)."""
+        ms = C.c_double(0); n = C.c_int64(0)
+        check(self.lib.fpx_calcfluxes_time(self.h, C.byref(ms), C.byref(n), int(reset)), "fpx_calcfluxes_time")
+        return ms.value, int(n.value)
+
     def concoutput(self, itime, prefix, area, volume, outnum, wetdep=False, drydep=False, clear=False, nest=False,
                    iout=1, prefix_pptv=None, outheight=None, outlon0=0.0, outlat0=0.0, weightmolar=(), reduced=False):
         """fpx_concoutput: writes <prefix><nnn> (the reference's grid_conc_* files) for every species."""
@@ -739,6 +771,7 @@ class Engine:
             check(self.lib.fpx_set_output_times(self.h, int(sc["outtimes"][0]), int(sc["outtimes"][1])),
                   "fpx_set_output_times")
         self.gshape = (len(lage), ncu, mps, self.nspec, nzg, nyg, nxg)
+        self.fshape = (len(lage), mps, self.nspec, nzg, nyg, nxg, 6)      # flux_mod's flux, first index fastest
         if "outgridn" in sc:          # OUTGRID_NEST (readoutgrid_nest.f90)
             nxn, nyn = (int(v) for v in sc["outgridn"])
             dxn, dyn, lon0n, lat0n = (float(v) for v in sc["outgeomn"])

@@ -21,7 +21,10 @@ module flexgpu_mod
   use com_mod
   use point_mod, only: xmass, npart, ireleasestart, ireleaseend, kindz, xpoint1, xpoint2, ypoint1, ypoint2, zpoint1, zpoint2, rho_rel
   use xmass_mod, only: xmasssave
-  use outg_mod, only: outheight, area, volume
+  use outg_mod, only: outheight, area, volume, areaeast, areanorth
+#ifdef FLEXGPU_FLUX
+  use flux_mod, only: flux
+#endif
   use unc_mod, only: gridunc, drygridunc, wetgridunc, griduncn, drygriduncn, wetgriduncn
   use conv_mod, only: nconvlev, cbaseflux, cbasefluxn
   implicit none
@@ -37,7 +40,10 @@ module flexgpu_mod
             flexgpu_getvdep_init, flexgpu_getvdep, &
             flexgpu_redist_plan, flexgpu_redist_bytes, flexgpu_redist_pack, flexgpu_redist_unpack, &
             flexgpu_checkpoint_write, flexgpu_checkpoint_read, &
-            flexgpu_conv_init, flexgpu_upload_conv_fields, flexgpu_convmix, flexgpu_cbaseflux
+            flexgpu_conv_init, flexgpu_upload_conv_fields, flexgpu_convmix, flexgpu_cbaseflux, flexgpu_fluxoutput
+#ifdef FLEXGPU_FLUX
+  public :: flexgpu_get_flux
+#endif
 #ifdef FLEXGPU_NESTS
   public :: flexgpu_upload_nests, flexgpu_upload_wet_nest_fields, flexgpu_nests_init, flexgpu_verttransform_nests, &
             flexgpu_upload_conv_nest_fields, flexgpu_cbaseflux_nests, flexgpu_upload_diag_nest_fields
@@ -74,7 +80,8 @@ module flexgpu_mod
     integer(c_int32_t) :: pbl_slice_passes
     integer(c_int64_t) :: global_particles
     integer(c_int32_t) :: ipout, iflux, linit_cond
-    integer(c_int32_t) :: reserved(3)
+    integer(c_int32_t) :: device_flux
+    integer(c_int32_t) :: reserved(2)
   end type fpx_config
 
   type, bind(C) :: fpx_fields
@@ -113,6 +120,12 @@ module flexgpu_mod
     real(c_double) :: weightmolar(FPX_MAXSPEC)
     integer(c_int32_t) :: reduced, reserved
   end type fpx_concout
+
+  type, bind(C) :: fpx_fluxout
+    integer(c_int32_t) :: struct_bytes, reserved
+    real(c_double) :: bdate, outstep
+    type(c_ptr) :: area, areaeast, areanorth
+  end type fpx_fluxout
 
   integer, parameter :: FPX_MAXNESTS = 4
   type, bind(C) :: fpx_nests
@@ -392,6 +405,18 @@ module flexgpu_mod
       type(fpx_fields), intent(in) :: sfc
       type(fpx_fields_out), intent(in) :: o
     end function fpx_verttransform_nest
+    integer(c_int) function fpx_get_flux(h, f, allreduce, clear) bind(C, name='fpx_get_flux')
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: h, f
+      integer(c_int32_t), value :: allreduce, clear
+    end function fpx_get_flux
+    integer(c_int) function fpx_fluxoutput(h, itime, f, prefix, reduced) bind(C, name='fpx_fluxoutput')
+      import :: c_ptr, c_int, c_int32_t, c_char, fpx_fluxout
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: itime, reduced
+      type(fpx_fluxout), intent(in) :: f
+      character(kind=c_char), intent(in) :: prefix(*)
+    end function fpx_fluxoutput
     integer(c_int) function fpx_concoutput(h, itime, c, prefix, clear) bind(C, name='fpx_concoutput')
       import :: c_ptr, c_int, c_int32_t, c_char, fpx_concout
       type(c_ptr), value :: h
@@ -638,11 +663,13 @@ contains
   ! The run's ipout / iflux / linit_cond travel along: the engine refuses (ierr = -5) a run whose particle loop would also
   ! call partpos_average, calcfluxes or initial_cond_calc (timemanager.f90:617,623,631,702), which it does not compute.
   ! turboff / interpolhmix: the host's compile-time parameters (com_mod.f90:777-778) become the engine's run-time switches.
+  ! device_flux = .true.: with iflux = 1 the engine computes the gross fluxes itself (calcfluxes.f90 in flexgpu_step) and the
+  ! host fetches them with flexgpu_get_flux or lets flexgpu_fluxoutput write the file; without it iflux = 1 is refused.
   subroutine flexgpu_init(ierr, device, nmaxpart, compute_real_bytes, rng_mode, seed, defer_height, particle_base, &
-                          global_particles, blend_mode)
+                          global_particles, blend_mode, device_flux)
     integer, intent(out) :: ierr
     integer, intent(in), optional :: device, nmaxpart, compute_real_bytes, rng_mode, blend_mode
-    logical, intent(in), optional :: defer_height
+    logical, intent(in), optional :: defer_height, device_flux
     integer(c_int64_t), intent(in), optional :: seed, particle_base, global_particles
     type(fpx_config) :: cfg
     integer :: ks
@@ -684,6 +711,7 @@ contains
     cfg%pbl_slice_passes = 0
     cfg%global_particles = cfg%max_particles; if (present(global_particles)) cfg%global_particles = global_particles
     cfg%ipout = ipout; cfg%iflux = iflux; cfg%linit_cond = linit_cond
+    cfg%device_flux = 0; if (present(device_flux)) cfg%device_flux = merge(1, 0, device_flux)
     cfg%reserved = 0
     ierr = fpx_create(flexgpu_handle, cfg)
     if (ierr /= 0) return
@@ -936,6 +964,39 @@ contains
     if (present(reduced)) c%reduced = merge(1, 0, reduced)
     ierr = fpx_concoutput(flexgpu_handle, int(itime, c_int32_t), c, trim(prefix) // c_null_char, 1_c_int32_t)
   end subroutine flexgpu_concoutput
+
+#ifdef FLEXGPU_FLUX
+  ! (-DFLEXGPU_FLUX: a host that links flux_mod; like FLEXGPU_NESTS the switch keeps the module usable by hosts that do not.)
+  ! The device's gross fluxes overwrite flux_mod's flux (allocated by the host's outgrid_init.f90:186), so that the host may
+  ! keep calling its own fluxoutput (timemanager.f90:439).  clear = 1 zeroes the device's grid, as fluxoutput.f90:289-303
+  ! zeroes the host's after writing; allreduce = .true.: the sums over all ranks, the ranks' partial sums stay.
+  subroutine flexgpu_get_flux(clear, ierr, allreduce)
+    integer, intent(in) :: clear
+    integer, intent(out) :: ierr
+    logical, intent(in), optional :: allreduce
+    integer(c_int32_t) :: ar
+    ar = 0
+    if (present(allreduce)) ar = merge(1, 0, allreduce)
+    ierr = fpx_get_flux(flexgpu_handle, loc_r(flux), ar, int(clear, c_int32_t))
+  end subroutine flexgpu_get_flux
+#endif
+
+  ! Replaces `if (iflux.eq.1) call fluxoutput(itime)` (timemanager.f90:439): writes path(2)//'grid_flux_'//date//time from the
+  ! device's grid with the host's area, areaeast, areanorth, bdate and outstep, and zeroes the device's grid.
+  ! reduced = .true. (MPI host, after flexgpu_get_flux(0, ierr, allreduce=.true.)): the file holds the sums over all ranks.
+  subroutine flexgpu_fluxoutput(itime, ierr, reduced)
+    integer, intent(in) :: itime
+    integer, intent(out) :: ierr
+    logical, intent(in), optional :: reduced
+    type(fpx_fluxout) :: f
+    integer(c_int32_t) :: red
+    f%struct_bytes = int(c_sizeof(f), c_int32_t); f%reserved = 0
+    f%bdate = bdate; f%outstep = outstep
+    f%area = loc_r(area); f%areaeast = loc_r(areaeast); f%areanorth = loc_r(areanorth)
+    red = 0
+    if (present(reduced)) red = merge(1, 0, reduced)
+    ierr = fpx_fluxoutput(flexgpu_handle, int(itime, c_int32_t), f, path(2)(1:length(2)) // c_null_char, red)
+  end subroutine flexgpu_fluxoutput
 
   ! one time slot of the com_mod fields (slot = the value found in memind(k))
   subroutine flexgpu_upload_fields(slot, ierr)

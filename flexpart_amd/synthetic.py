@@ -981,3 +981,70 @@ def calcpv_case(name):
     out["geom"] = np.array(PV_GEOM[name], np.float64)
     out["globalflags"] = np.array([int(glob)] * 3, np.int32)
     return out
+
+
+# --------------------------------------------------------------------------
+# calcfluxes / fluxoutput (tests/golden/cf_r*.npz)
+# --------------------------------------------------------------------------
+CF_VARIANTS = ("release", "domainfill")
+
+
+def calcfluxes_case(variant="release"):
+    """Prepared particles for the reference's calcfluxes and fluxoutput, from integer hashes and IEEE-exact operations
+    only, so that the tests regenerate the fixture's inputs bit for bit.  Met grid 20 x 12 (dx 1, dy 0.5), output grid
+    6 x 4 x 3 with cells of 0.3 x 0.2 degrees whose origin lies inside the met grid (particles lie west and south of
+    it), 2 species, 3 release points with ioutputforeachrelease = 1, 2 age classes.  `ncalls` batches of particles, each
+    with a position before (xold.. as the double / real the particle arrays held) and after the move; masses are small
+    integers times 2**-10, so every sum is exact in either real kind and in any order.  The last eight particles of a
+    batch move by more than nx/2 (the cyclic branch, both directions).  'domainfill' is a small second case with
+    mdomainfill = 1 and npoint = the particle number, as a domain-filling run has it: kp = 1 for every particle."""
+    if variant not in CF_VARIANTS:
+        raise ValueError(variant)
+    fill = variant == "domainfill"
+    n, ncalls = (60, 1) if fill else (300, 2)
+    nspec, numpoint = 2, 3
+    c = dict(grid=np.array([20, 12], np.int32), geom=np.array([1.0, 0.5, -10.0, 40.0], np.float64),
+             outgrid=np.array([6, 4, 3], np.int32), outgeom=np.array([0.3, 0.2, -3.7, 42.1], np.float64),
+             outheight=np.array([100.0, 500.0, 1500.0], np.float64), nspec=nspec, numpoint=numpoint,
+             ioutputforeachrelease=1, mdomainfill=int(fill), maxpointspec_act=numpoint, lage=np.array([3600, 86400], np.int32),
+             itime=10800, bdate=2458864.0, outstep=3600.0, ncalls=ncalls, npart=n)
+    nxg, nyg, nzg = (int(v) for v in c["outgrid"])
+    # wall areas: any positive numbers do (fluxoutput only divides by them); dyadic fractions of 1e8, exact in both kinds
+    c["area"] = 1.0e8 * (1.0 + np.floor(_hash01((nyg, nxg), 8100) * 64.0) / 64.0)
+    c["areaeast"] = 1.0e6 * (1.0 + np.floor(_hash01((nzg, nyg, nxg), 8200) * 64.0) / 64.0)
+    c["areanorth"] = 1.0e6 * (1.0 + np.floor(_hash01((nzg, nyg, nxg), 8300) * 64.0) / 64.0)
+    for b in range(ncalls):
+        s = 9000 + 100 * b + (50 if fill else 0)
+        xo = 5.3 + 3.8 * _uniform01(n, s + 1)
+        yo = 3.6 + 2.8 * _uniform01(n, s + 2)
+        zo = 2000.0 * _uniform01(n, s + 3)
+        xn = xo + 2.4 * (_uniform01(n, s + 4) - 0.5)
+        yn = yo + 1.6 * (_uniform01(n, s + 5) - 0.5)
+        zn = 2000.0 * _uniform01(n, s + 6)
+        still = np.arange(n) % 7 == 3                        # some stay on their level, some in their column
+        zn[still] = zo[still] + 20.0 * (_uniform01(n, s + 7)[still] - 0.5)
+        zn = np.abs(zn)
+        cyc = np.arange(n) >= n - 8
+        east = cyc & (np.arange(n) % 2 == 0)
+        xo[cyc] = np.where(east[cyc], 0.4, 18.7) + 0.5 * _uniform01(n, s + 8)[cyc]
+        xn[cyc] = np.where(east[cyc], 18.6, 0.3) + 0.5 * _uniform01(n, s + 9)[cyc]
+        yo[cyc] = 4.4 + 1.2 * _uniform01(n, s + 10)[cyc]
+        yn[cyc] = yo[cyc] + 0.2
+        zo[cyc] = zn[cyc] = 200.0
+        h = _splitmix64(n, s + 11)
+        m = np.zeros((nspec, n), np.float64)
+        m[0] = (1 + (h % np.uint64(8)).astype(np.int64)).astype(np.float64) / 1024.0
+        second = (h >> np.uint64(8)) % np.uint64(6) == np.uint64(0)
+        age = ((h >> np.uint64(24)) % np.uint64(5000)).astype(np.int64)          # most in the first age class
+        second = second | (age >= 3600)                                          # the second species: one in six, and every old particle
+        m[1] = np.where(second, (1 + ((h >> np.uint64(16)) % np.uint64(4)).astype(np.int64)).astype(np.float64) / 1024.0, 0.0)
+        old = (h >> np.uint64(40)) % np.uint64(16) == np.uint64(0)                # the few of the second class sit in one corner
+        age[old] += 3600
+        xo[old & ~cyc] = 6.4 + 0.25 * _uniform01(n, s + 12)[old & ~cyc]
+        xn[old & ~cyc] = xo[old & ~cyc] + 0.35
+        c[f"xold{b}"], c[f"yold{b}"], c[f"zold{b}"] = xo, yo, zo
+        c[f"xnew{b}"], c[f"ynew{b}"], c[f"znew{b}"] = xn, yn, zn
+        c[f"xmass1_{b}"] = m
+        c[f"npoint{b}"] = (np.arange(n) + 1).astype(np.int32) if fill else (1 + ((h >> np.uint64(48)) % np.uint64(numpoint)).astype(np.int64)).astype(np.int32)
+        c[f"itramem{b}"] = (int(c["itime"]) - age).astype(np.int32)
+    return c

@@ -123,10 +123,16 @@ typedef struct {
   int64_t global_particles;
   /* Diagnostics inside the particle loop that the engine does NOT compute (out of scope): the host passes
    * its COMMAND switches and fpx_create refuses (FPX_ERR_UNSUPPORTED) a run that would need them, instead of dropping their
-   * output silently: ipout = 3 (partpos_average, timemanager.f90:617), iflux = 1 (calcfluxes, :623), linit_cond >= 1
-   * (initial_cond_calc, :631,702).  Zero-initialised fields mean "not requested". */
+   * output silently: ipout = 3 (partpos_average, timemanager.f90:617), iflux = 1 (calcfluxes, :623; unless device_flux = 1,
+   * below), linit_cond >= 1 (initial_cond_calc, :631,702).  Zero-initialised fields mean "not requested". */
   int32_t ipout, iflux, linit_cond;
-  int32_t reserved[3];
+  /* Gross mass fluxes on the device (calcfluxes.f90, timemanager.f90:623): iflux = 1 is accepted only together with
+   * device_flux = 1, by which the host declares that it fetches the flux grid from the engine (fpx_get_flux, fpx_fluxoutput);
+   * iflux = 1 alone is refused as above, and device_flux = 1 with iflux != 1 is FPX_ERR_ARG.  With it fpx_outgrid_init
+   * allocates flux, and fpx_step runs two more kernels (one before, one after the particle is moved); without it nothing
+   * is allocated and the step launches what it always did. */
+  int32_t device_flux;
+  int32_t reserved[2];
 } fpx_config;
 
 /* One time slot of the met fields the path gathers from (com_mod.f90:355-371,
@@ -370,7 +376,8 @@ int fpx_readpartpositions(fpx_handle h, const char *path, const fpx_restart *r,
  * Nested wind fields (convmix.f90:100-119,198-250; after fpx_nests_init): a particle inside a nest takes the nest's columns,
  *   soundings and mass-flux field cbasefluxn(:,:,l); fpx_upload_conv_nest_fields(nest, slot, ...) with the strides nxmaxn,
  *   nymaxn of fpx_nests_init is then required for every nest, fpx_get/set_cbaseflux_nest move [nyn][nxn].
- * Not covered: the flux diagnostics of calcfluxes (iflux = 1). */
+ * Not covered: the flux diagnostics of calcfluxes (iflux = 1) for the convective displacement (convmix.f90:208-220,284-296).
+ *   fpx_conv_init on an engine with device_flux = 1 is therefore refused (FPX_ERR_UNSUPPORTED) rather than dropping them. */
 typedef struct {
   int32_t struct_bytes;
   int32_t nuvz;              /* com_mod nuvz                                              */
@@ -617,6 +624,39 @@ int fpx_conccalc(fpx_handle h, int32_t itime, double weight);
  * clear != 0: zero the rank's gridunc afterwards, as concoutput does after writing (concoutput.f90:719-720: gridunc
  * and creceptor only -- the deposition grids are zeroed once, outgrid_init.f90:317-318, and never again). */
 int fpx_get_grids(fpx_handle h, void *gridunc, void *drygridunc, int32_t allreduce, int32_t clear);
+/* ---- gross mass fluxes (fpx_config.device_flux = 1) -----------------------------------------------------------
+ * fpx_step then does what `if (iflux.eq.1) call calcfluxes(nage,j,xold,yold,zold)` (timemanager.f90:623, with :560-562 and
+ * the age class of :545-548; the routine: calcfluxes.f90:43-166) does for every particle it moves: it accumulates the
+ * particle's masses -- as they are before the deposition/decay epilogue of :637-660, after the receptor block :564-598 --
+ * on the cell faces crossed, into the device's flux(6,0:numxgrid-1,0:numygrid-1,numzgrid,nspec,maxpointspec_act,nageclass)
+ * of flux_mod (allocated as outgrid_init.f90:186 does, host_real_bytes per value).  outheighthalf is derived from the
+ * outheight of fpx_outgrid_init as readoutgrid.f90:194-196 does; mdomainfill of fpx_config and ioutputforeachrelease of
+ * fpx_outgrid decide kp (calcfluxes.f90:43).  There is no nested flux grid (the reference has none).  A step without
+ * fpx_outgrid_init returns FPX_ERR_STATE.
+ * fpx_get_flux copies the grid to the host (flux may be NULL), with the semantics of fpx_get_grids: allreduce != 0 sums
+ * over the communicator into a receive buffer of the engine's and copies out from that (the rank's partial sums stay);
+ * clear != 0 zeroes the rank's grid afterwards (fluxoutput.f90:289-303). */
+int fpx_get_flux(fpx_handle h, void *flux, int32_t allreduce, int32_t clear);
+/* Replaces `if (iflux.eq.1) call fluxoutput(itime)` (timemanager.f90:439; the routine: fluxoutput.f90:46-283): writes
+ * "<prefix>grid_flux_<yyyymmdd><hhmmss>" (prefix = path(2)(1:length(2))) from the device's grid, byte-identical to the
+ * reference's file for the same grid -- per species, kp and age class the six directions in the reference's order (eastward
+ * = index 2, westward = 1, south = 3, north = 4, up = 5, down = 6), each sparse (records of index and value, closed by
+ * -999, 999.) when 4*ncells < numxgrid*numygrid*numzgrid with ncells counted per (species, age class) over all kp, else as
+ * full rows; values 1.e12*flux/area/outstep in the host's real kind -- and zeroes flux afterwards (:289-303).
+ * reduced = 1: write the sums over all ranks that a preceding fpx_get_flux(h, NULL, 1, 0) left in the receive buffer. */
+typedef struct {
+  int32_t struct_bytes;
+  int32_t reserved;
+  double bdate;          /* com_mod bdate: julian date of the run's start (fluxoutput.f90:46)            */
+  double outstep;        /* com_mod outstep (real)                                                       */
+  const void *area;      /* area(0:numxgrid-1,0:numygrid-1), outg_mod                                    */
+  const void *areaeast;  /* areaeast(0:numxgrid-1,0:numygrid-1,numzgrid), outg_mod (outgrid_init.f90:88) */
+  const void *areanorth; /* areanorth, same shape                                                        */
+} fpx_fluxout;
+int fpx_fluxoutput(fpx_handle h, int32_t itime, const fpx_fluxout *f, const char *prefix, int32_t reduced);
+/* cumulative device time (ms) of k_flux_save + k_calcfluxes, by events of their own, and the number of steps that ran
+ * them since the last reset.  fpx_kernel_times keeps its meaning: the two kernels lie outside its intervals. */
+int fpx_calcfluxes_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset);
 /* Communicator for the grid reduction, one of:
  * (a) RCCL: rank 0 obtains an id (128 bytes), the host distributes it (MPI_Bcast / torch.distributed / a file), every
  *     rank calls fpx_comm_init; the reduction then runs device to device on the handle's stream. */
