@@ -26,6 +26,7 @@
 #include "fpx_getvdep.hpp"
 #include "fpx_calcpv.hpp"
 #include "fpx_calcfluxes.hpp"
+#include "fpx_partavg.hpp"
 #include "fpx_convect.hpp"
 #include "fpx_rng_host.hpp"
 
@@ -737,13 +738,7 @@ __global__ void __launch_bounds__(kBlock, FPX_PREP_TWO_WAVES(INIT, POLAR, NEST, 
 // the host only streams the bytes to disk.  Arithmetic in H with FMA contraction off: the file
 // is byte-identical to the reference's.
 // ---------------------------------------------------------------------------
-template <typename H>
-struct DiagP {
-  const H *oro, *tropo[2];   // host layout (ix,jy), stride nxmax
-  const H *d3;               // [jy][ix][iz][slot][3] = (pv, qv, tt): z fastest like the wind pack, one 96-byte run per corner column
-  int nxmax, nymax;
-  H dx, dy, xlon0, ylat0;
-};
+// (DiagP and the interpolation itself, po_gather: fpx_partavg.hpp -- shared with the interval averages)
 
 // Both kernels run over the device slots (cell-sorted after a locality sort: coalesced state reads, gathers with
 // the locality of the particle step); the file order is the particle number, so the selection flag and the
@@ -769,74 +764,12 @@ __global__ void __launch_bounds__(kBlock) k_partoutput(View<R> V, Parts<R> P, Di
   const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n || P.itra1[s] != itime) return;
   const unsigned int pid = P.pid[s];
-  const int nx = V.nx, ny = V.ny, nz = V.nz, nspec = V.nspec;
+  const int nspec = V.nspec;
   const int reclen = 8 + (10 + nspec) * (int)sizeof(H);
-  const H dt1 = (H)(itime - V.memtime0), dt2 = (H)(V.memtime1 - itime);   // partoutput.f90:69-71
-  const H dtt = (H)1. / (dt1 + dt2);
-  const double xt = P.xt[s], yt = P.yt[s];
   const H zt = (H)P.zt[s];
-  const H xlon = (H)((double)D.xlon0 + xt * (double)D.dx);
-  const H ylat = (H)((double)D.ylat0 + yt * (double)D.dy);
-  const int ix = (int)xt, jy = (int)yt;
-  int ixp = ix + 1, jyp = jy + 1;
-  const H ddx = (H)(xt - (double)(H)ix), ddy = (H)(yt - (double)(H)jy);
-  const H rddx = (H)1. - ddx, rddy = (H)1. - ddy;
-  const H p1 = rddx * rddy, p2 = ddx * rddy, p3 = rddx * ddy, p4 = ddx * ddy;
-  if (jyp >= D.nymax) jyp = jyp - 1;                                      // :119-121
-  if (ixp >= D.nxmax) ixp = D.nxmax - 1;                                  // guard (weight 0 there)
-  auto h2 = [&](const H *f, int i, int j) { return f[(size_t)i + (size_t)D.nxmax * (size_t)j]; };
-  // component c of (pv, qv, tt) at level k, slot h; elements of the host's padding read as 0 like rho below
-  auto d3 = [&](int c, int i, int j, int k, int h) -> H {
-    if (i >= nx || j >= ny) return (H)0;
-    return D.d3[((((size_t)j * nx + i) * nz + (k - 1)) * 2 + h) * 3 + c];
-  };
-  // rho and hmix live in the gather packs (compact nx, ny; elements of the host's padding read as 0)
-  auto rho_at = [&](int i, int j, int k, int slot) -> H {
-    if (i >= nx || j >= ny) return (H)0;
-    return (H)V.r2[(((size_t)j * nx + i) * nz + (k - 1)) * 4 + slot * 2];
-  };
-  auto hmix_at = [&](int i, int j, int slot) -> H {
-    if (i >= nx || j >= ny) return (H)0;
-    return (H)V.sfc[((size_t)j * nx + i) * 8 + slot * 4 + 3];
-  };
-  const H topo = p1 * h2(D.oro, ix, jy) + p2 * h2(D.oro, ixp, jy) + p3 * h2(D.oro, ix, jyp) + p4 * h2(D.oro, ixp, jyp);
-  int indz = nz - 1, indzp = nz;   // the reference keeps the previous particle's indices when zt >= height(nz); cannot happen after advance()
-  for (int il = 2; il <= nz; il++)
-    if ((H)V.height[il - 1] > zt) { indz = il - 1; indzp = il; break; }
-  const H dz1 = zt - (H)V.height[indz - 1], dz2 = (H)V.height[indzp - 1] - zt;
-  const H dz = (H)1. / (dz1 + dz2);
-  const int slot[2] = {V.m1, V.m2};
-  H pvprof[2], qvprof[2], ttprof[2], rhoprof[2];
-#pragma unroll
-  for (int l = 0; l < 2; l++) {
-    const int ind = indz + l;
-    H pv1[2], qv1[2], tt1[2], rho1[2];
-#pragma unroll
-    for (int m = 0; m < 2; m++) {
-      const int h = slot[m];
-      pv1[m] = p1 * d3(0, ix, jy, ind, h) + p2 * d3(0, ixp, jy, ind, h) + p3 * d3(0, ix, jyp, ind, h) + p4 * d3(0, ixp, jyp, ind, h);
-      qv1[m] = p1 * d3(1, ix, jy, ind, h) + p2 * d3(1, ixp, jy, ind, h) + p3 * d3(1, ix, jyp, ind, h) + p4 * d3(1, ixp, jyp, ind, h);
-      tt1[m] = p1 * d3(2, ix, jy, ind, h) + p2 * d3(2, ixp, jy, ind, h) + p3 * d3(2, ix, jyp, ind, h) + p4 * d3(2, ixp, jyp, ind, h);
-      rho1[m] = p1 * rho_at(ix, jy, ind, h) + p2 * rho_at(ixp, jy, ind, h) + p3 * rho_at(ix, jyp, ind, h) + p4 * rho_at(ixp, jyp, ind, h);
-    }
-    pvprof[l] = (pv1[0] * dt2 + pv1[1] * dt1) * dtt;
-    qvprof[l] = (qv1[0] * dt2 + qv1[1] * dt1) * dtt;
-    ttprof[l] = (tt1[0] * dt2 + tt1[1] * dt1) * dtt;
-    rhoprof[l] = (rho1[0] * dt2 + rho1[1] * dt1) * dtt;
-  }
-  const H pvi = (dz1 * pvprof[1] + dz2 * pvprof[0]) * dz;
-  const H qvi = (dz1 * qvprof[1] + dz2 * qvprof[0]) * dz;
-  const H tti = (dz1 * ttprof[1] + dz2 * ttprof[0]) * dz;
-  const H rhoi = (dz1 * rhoprof[1] + dz2 * rhoprof[0]) * dz;
-  H tr[2], hm[2];
-#pragma unroll
-  for (int m = 0; m < 2; m++) {
-    const int h = slot[m];
-    tr[m] = p1 * h2(D.tropo[h], ix, jy) + p2 * h2(D.tropo[h], ixp, jy) + p3 * h2(D.tropo[h], ix, jyp) + p4 * h2(D.tropo[h], ixp, jyp);
-    hm[m] = p1 * hmix_at(ix, jy, h) + p2 * hmix_at(ixp, jy, h) + p3 * hmix_at(ix, jyp, h) + p4 * hmix_at(ixp, jyp, h);
-  }
-  const H hmixi = (hm[0] * dt2 + hm[1] * dt1) * dtt;
-  const H tri = (tr[0] * dt2 + tr[1] * dt1) * dtt;
+  PoVals<H> o;
+  po_gather<R, H, false>(V, D, itime, P.xt[s], P.yt[s], zt, o);
+  const H xlon = o.xlon, ylat = o.ylat, topo = o.topo, pvi = o.pvi, qvi = o.qvi, tti = o.tti, rhoi = o.rhoi, hmixi = o.hmixi, tri = o.tri;
   // the record, :177-179 (32-bit words: the payload of an 8-byte build is only 4-byte aligned in the file)
   unsigned int *w = out + (size_t)recidx[pid] * (size_t)(reclen / 4 + 2);
   *w++ = (unsigned int)reclen;
@@ -2109,6 +2042,9 @@ struct EngineBase {
   virtual int get_flux(void *flux, int allreduce, int clear) = 0;
   virtual int fluxoutput(int itime, const fpx_fluxout *f, const char *prefix, int reduced) = 0;
   virtual int calcfluxes_time(double *ms, long long *launches, int reset) = 0;
+  virtual int get_partavg(long long first, long long count, int32_t *npart_av, void *const *sums) = 0;
+  virtual int partoutput_average(int itime, const char *prefix, int64_t *nrecords) = 0;
+  virtual int partavg_time(double *ms, long long *launches, int reset) = 0;
   virtual int count_particles(int64_t *local, int64_t *total, int allreduce) = 0;
   virtual int lane_stats(uint64_t *out, int n, int reset) = 0;
   virtual int set_option(const char *name, const char *value) = 0;
@@ -2328,7 +2264,9 @@ struct Engine : EngineBase {
     if (cfg.max_particles < 1 || cfg.max_particles > 0xFFFFFFF0ll) return fail(FPX_ERR_ARG, "bad max_particles");
     if (cfg.ifine < 1) return fail(FPX_ERR_ARG, "ifine must be >= 1");
     if (cfg.lsynctime == 0 || std::abs((long long)cfg.lsynctime) > 65535) return fail(FPX_ERR_ARG, "lsynctime must be non-zero and at most 65535 s in magnitude (the hand-over record of the Langevin kernel keeps |itimec - itime| in 16 bits)");
-    if (cfg.ipout == 3) return fail(FPX_ERR_UNSUPPORTED, "ipout = 3: the particle loop's partpos_average (timemanager.f90:617) is not computed by this engine");
+    if (cfg.device_partavg != 0 && cfg.device_partavg != 1) return fail(FPX_ERR_ARG, "device_partavg must be 0 or 1");
+    if (cfg.device_partavg == 1 && cfg.ipout != 3) return fail(FPX_ERR_ARG, "device_partavg = 1 without ipout = 3: there are no averages to compute");
+    if (cfg.ipout == 3 && !cfg.device_partavg) return fail(FPX_ERR_UNSUPPORTED, "ipout = 3: the particle loop's partpos_average (timemanager.f90:617) is not computed by this engine");
     if (cfg.device_flux != 0 && cfg.device_flux != 1) return fail(FPX_ERR_ARG, "device_flux must be 0 or 1");
     if (cfg.device_flux == 1 && cfg.iflux != 1) return fail(FPX_ERR_ARG, "device_flux = 1 without iflux = 1: there is no flux to compute");
     if (cfg.iflux == 1 && !cfg.device_flux) return fail(FPX_ERR_UNSUPPORTED, "iflux = 1: the particle loop's calcfluxes (timemanager.f90:623) is not computed by this engine");
@@ -2430,6 +2368,7 @@ struct Engine : EngineBase {
       k_fill<R><<<(int)((cap * cfg.nspec + kBlock - 1) / kBlock), kBlock, 0, stream>>>(P.xscav, (R)-1, 0, (long long)(cap * cfg.nspec), nullptr);
     }
     if ((rc = dalloc(&P.pid, cap))) return rc;
+    if (cfg.device_partavg && (rc = partavg_alloc(0))) return rc;
     if ((rc = dalloc(&d_pbl_list, cap))) return rc;
     if ((rc = dalloc(&d_pbl_ctr, kCtrWords))) return rc;
     if ((rc = dalloc(&d_pbl_flag, cap))) return rc;
@@ -2469,6 +2408,7 @@ struct Engine : EngineBase {
     for (auto &e : pinned_host) (void)hipHostUnregister(const_cast<void *>(e.first));
     for (auto &e : ev_pool) for (int i = 0; i < 5; i++) (void)hipEventDestroy(e.e[i]);
     for (auto &e : fx_ev_pool) for (int i = 0; i < 4; i++) (void)hipEventDestroy(e.e[i]);
+    for (auto &e : pa_ev_pool) for (int i = 0; i < 2; i++) (void)hipEventDestroy(e.e[i]);
     for (void *q : owned) (void)hipFree(q);
     if (staging) (void)hipFree(staging);
     if (d_sort_tmp) (void)hipFree(d_sort_tmp);
@@ -3280,12 +3220,7 @@ struct Engine : EngineBase {
       if (count > 0) {
         const size_t words = (size_t)count * recwords;
         if ((e = hipMalloc(&out, words * 4)) != hipSuccess) { cleanup(); return fail(FPX_ERR_NOMEM, std::string("partoutput: record buffer: ") + hipGetErrorString(e)); }
-        DiagP<H> D;
-        D.oro = (const H *)diag_oro;
-        D.tropo[0] = (const H *)diag_tropo[0]; D.tropo[1] = (const H *)diag_tropo[1];
-        D.d3 = (const H *)diag_d3;
-        D.nxmax = cfg.nxmax; D.nymax = cfg.nymax;
-        D.dx = (H)cfg.dx; D.dy = (H)cfg.dy; D.xlon0 = (H)cfg.xlon0; D.ylat0 = (H)cfg.ylat0;
+        const DiagP<H> D = diag_args<H>();
         k_partoutput<R, H><<<nb, kBlock, 0, stream>>>(V, P, D, idx, n, itime, out);
         e = hipGetLastError();
         (void)hipEventRecord(e1, stream);
@@ -4622,6 +4557,28 @@ struct Engine : EngineBase {
   // header.reserved, bit 0: the file ends with the flux grid of a run with device_flux (uint64 count, then the values in the
   // host's real kind); a file without fluxes has reserved = 0 and is what it always was
   static constexpr int32_t kCkptFlux = 1;
+  // bit 1: after that (or after cbaseflux) follow the interval averages of a run with device_partavg: uint64 numpart, then
+  // npart_av (int32) and the fourteen sums in the host's real kind, each [numpart] in particle-number order
+  static constexpr int32_t kCkptPartavg = 2;
+  uint64_t ckpt_partavg_bytes(const CkptHeader &h) const { return (h.reserved & kCkptPartavg) ? 8 + (uint64_t)h.numpart * (4 + (uint64_t)pa::kSums * cfg.host_real_bytes) : 0; }
+  template <typename H>
+  int ckpt_put_partavg(FILE *fh, long long n, std::vector<unsigned char> &buf) {
+    const pa::State<H> S = partavg_state<H>(pa_cur);
+    int rc;
+    if ((rc = ckpt_put_array(fh, S.npart_av, n, buf))) return rc;
+    for (int k = 0; k < pa::kSums; k++) if ((rc = ckpt_put_array(fh, S.sum + (size_t)k * S.cap, n, buf))) return rc;
+    return 0;
+  }
+  template <typename H>
+  int ckpt_get_partavg(FILE *fh, long long n, std::vector<unsigned char> &buf) {
+    const pa::State<H> S = partavg_state<H>(pa_cur);
+    HIPCHK(hipMemsetAsync(S.npart_av, 0, (size_t)S.cap * sizeof(int), stream));
+    HIPCHK(hipMemsetAsync(S.sum, 0, (size_t)S.cap * pa::kSums * sizeof(H), stream));
+    int rc;
+    if ((rc = ckpt_get_array(fh, S.npart_av, n, buf))) return rc;
+    for (int k = 0; k < pa::kSums; k++) if ((rc = ckpt_get_array(fh, S.sum + (size_t)k * S.cap, n, buf))) return rc;
+    return 0;
+  }
   uint64_t ckpt_flux_bytes(const CkptHeader &h) const { return (h.reserved & kCkptFlux) ? 8 + (uint64_t)n_flux * cfg.host_real_bytes : 0; }
   struct CkptRng { HostRng<float> r4; HostRng<double> r8; Ran1 rel; };
   uint64_t conv_cbase_bytes() const {      // cbaseflux of the mother grid and of every nest that has convection fields
@@ -4651,7 +4608,8 @@ struct Engine : EngineBase {
     h.rel_global_count = rel_global_count;
     ckpt_describe_grid(h);
     h.reserved = cfg.device_flux && fx_flux ? kCkptFlux : 0;      // the flux section follows cbaseflux: a count and the values
-    h.total_bytes = ckpt_total_bytes(h) + ckpt_flux_bytes(h);
+    if (cfg.device_partavg) h.reserved |= kCkptPartavg;
+    h.total_bytes = ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h);
     if (fwrite(&h, sizeof(h), 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
     CkptRng rs{rng4, rng8, rel_ran1};
     if (fwrite(&rs, sizeof(rs), 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
@@ -4676,6 +4634,11 @@ struct Engine : EngineBase {
       const uint64_t cnt = n_flux;
       if (fwrite(&cnt, 8, 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
       if ((rc = ckpt_put_plain(fh, (const unsigned char *)fx_flux, n_flux * cfg.host_real_bytes, buf))) return rc;
+    }
+    if (h.reserved & kCkptPartavg) {
+      const uint64_t cnt = (uint64_t)n;
+      if (fwrite(&cnt, 8, 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
+      if ((rc = cfg.host_real_bytes == 4 ? ckpt_put_partavg<float>(fh, n, buf) : ckpt_put_partavg<double>(fh, n, buf))) return rc;
     }
     closer.f = nullptr;
     if (fclose(fh) != 0) return fail(FPX_ERR_ARG, std::string("checkpoint_write: write error on ") + path);
@@ -4707,10 +4670,12 @@ struct Engine : EngineBase {
         return fail(FPX_ERR_ARG, "checkpoint_read: written on another grid (nx, ny, nz, maxspec or the nest extents differ)");
       if (mine.pad != h.pad) return fail(FPX_ERR_ARG, "checkpoint_read: written with (without) DRYBKDEP / WETBKDEP");
       // the whole file must be there before a single array is touched
-      if ((h.reserved & ~kCkptFlux) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: unknown sections in the file");
+      if ((h.reserved & ~(kCkptFlux | kCkptPartavg)) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: unknown sections in the file");
+      if (((h.reserved & kCkptPartavg) != 0) != (cfg.device_partavg != 0))
+        return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_partavg; create the engine alike");
       if (((h.reserved & kCkptFlux) != 0) != (cfg.device_flux && fx_flux))
         return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_flux; create the engine alike and call fpx_outgrid_init first");
-      if (h.total_bytes != ckpt_total_bytes(h) + ckpt_flux_bytes(h)) return fail(FPX_ERR_ARG, "checkpoint_read: inconsistent header");
+      if (h.total_bytes != ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h)) return fail(FPX_ERR_ARG, "checkpoint_read: inconsistent header");
       if (fseek(fh, 0, SEEK_END) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: cannot seek");
       const long long len = (long long)ftell(fh);
       if (len < 0 || (uint64_t)len != h.total_bytes)
@@ -4756,6 +4721,11 @@ struct Engine : EngineBase {
       if (fread(&cnt, 8, 1, fh) != 1) return ckpt_invalidate(fail(FPX_ERR_ARG, "checkpoint_read: file too short"));
       if ((rc = ckpt_get_plain(fh, (unsigned char *)fx_flux, n_flux * cfg.host_real_bytes, buf))) return ckpt_invalidate(rc);
       fx_red_valid = false;
+    }
+    if (h.reserved & kCkptPartavg) {
+      uint64_t cnt = 0;
+      if (fread(&cnt, 8, 1, fh) != 1 || cnt != (uint64_t)n) return ckpt_invalidate(fail(FPX_ERR_ARG, "checkpoint_read: the section of the interval averages does not match the particle count"));
+      if ((rc = cfg.host_real_bytes == 4 ? ckpt_get_partavg<float>(fh, n, buf) : ckpt_get_partavg<double>(fh, n, buf))) return ckpt_invalidate(rc);
     }
     for (bool &v : red_valid) v = false;
     rng4 = rs.r4; rng8 = rs.r8; rel_ran1 = rs.rel;
@@ -4898,9 +4868,13 @@ struct Engine : EngineBase {
     for (int l = 0; l < V.numbnests; l++)
       if (!nest_loaded[l][0] || !nest_loaded[l][1]) return fail(FPX_ERR_STATE, "step: nest fields missing (fpx_upload_nest_fields, both slots)");
     if (cfg.device_flux && !Gp.on) return fail(FPX_ERR_STATE, "step: device_flux = 1 needs the output grid the fluxes are counted on (fpx_outgrid_init)");
+    if (cfg.device_partavg)
+      for (int i = 0; i < 9; i++)
+        if (!diag_have[i]) return fail(FPX_ERR_STATE, "step: device_partavg = 1 needs oro, pv, qv, tt of both slots on the device (fpx_upload_diag_fields or fpx_verttransform_ecmwf)");
     if (out) memset(out, 0, sizeof(*out));
     if (numpart == 0) return 0;
     if (cfg.device_flux) { const int rc = flux_prepare(); if (rc) return rc; }
+    if (cfg.device_partavg) { const int rc = partavg_prepare(); if (rc) return rc; }
     if (cfg.drydep) red_valid[RG_DRY] = red_valid[RG_DRYN] = false;
     if (cfg.sort_interval > 0 && step_counter > 0 && step_counter % (unsigned)cfg.sort_interval == 0) {
       int rc = sort_particles();
@@ -5029,6 +5003,10 @@ struct Engine : EngineBase {
       if (rc) return rc;
     }
     V.w3t0 = nullptr; V.w3t1 = nullptr; V.r2t0 = nullptr;      // the blended packs belong to this step's itime only
+    if (cfg.device_partavg) {   // timemanager.f90:617 -- the position after advance, the particles k_prep found due (its keys outlive the step)
+      const int rc = cfg.host_real_bytes == 4 ? partavg_launch<float>(itime) : partavg_launch<double>(itime);
+      if (rc) return rc;
+    }
     if (opt.verbose > 1) {   // the lists of the launches (a synchronisation per step: diagnostics only)
       unsigned int hc[kCtrWords];
       HIPCHK(hipMemcpyAsync(hc, d_pbl_ctr, sizeof(hc), hipMemcpyDeviceToHost, stream));
@@ -5090,6 +5068,13 @@ struct Engine : EngineBase {
     if (n == "pbl_cost_buckets") { if (!is_int || iv < -1 || iv > 3) goto bad; opt.pbl_cost_buckets = (int)iv; return 0; }   // -1 automatic, 0 none, 1: four buckets, 2: two, 3: eight
     if (n == "prep_init_always") { if (!need_int(0)) goto bad; opt.prep_init_always = iv != 0; return 0; }
     if (n == "pbl_drain_lanes") { if (!is_int || iv < -1 || iv > 64) goto bad; opt.pbl_drain_lanes = (int)iv; return 0; }
+    if (n == "bdate") {   // com_mod bdate (julian date of the run's start): fpx_partoutput_average names its file by it
+      char *e2 = nullptr;
+      const double b = strtod(value, &e2);
+      if (e2 == value || *e2 != 0 || !(b > 0.)) goto bad;
+      pa_bdate = b; pa_bdate_set = true;
+      return 0;
+    }
     if (n == "permute") {
       if (v == "auto") opt.permute = 0; else if (v == "direct") opt.permute = 1; else if (v == "staged") opt.permute = 2; else goto bad;
       return 0;
@@ -5312,6 +5297,13 @@ struct Engine : EngineBase {
       k_permute<R, 3><<<8 * tiles_per_xcd, kBlock, 0, stream>>>(P, P2, d_vals2, n, cfg.nspec, tiles_per_xcd);
     }
     HIPCHK(hipGetLastError());
+    if (cfg.device_partavg) {   // the sums move with their particle (perm = d_vals2, the same for both gathers)
+      if (!pa_n[1] && (rc = partavg_alloc(1))) return rc;
+      if (cfg.host_real_bytes == 4) pa::k_partavg_permute<float><<<(int)((P.cap + 255) / 256), 256, 0, stream>>>(partavg_state<float>(pa_cur), partavg_state<float>(pa_cur ^ 1), d_vals2, n);
+      else pa::k_partavg_permute<double><<<(int)((P.cap + 255) / 256), 256, 0, stream>>>(partavg_state<double>(pa_cur), partavg_state<double>(pa_cur ^ 1), d_vals2, n);
+      HIPCHK(hipGetLastError());
+      pa_cur ^= 1;
+    }
     // slots >= n keep their (dead) contents in both sets; swap roles
     std::swap(P, P2);
     if (n < P.cap) {
@@ -5793,6 +5785,161 @@ struct Engine : EngineBase {
     return 0;
   }
 
+  // ---- per-particle averages over the output interval (fpx_partavg.hpp; fpx_config.device_partavg) -------------
+  // npart_av and the fourteen sums of com_mod.f90:688-691 per storage space, in the host's real kind; a second set only once
+  // a locality sort has to move them.  Zero at creation; nothing but fpx_partoutput_average resets them -- release and
+  // splitting leave a space's sums as they find them, as the reference does.
+  int *pa_n[2] = {nullptr, nullptr};
+  void *pa_sum[2] = {nullptr, nullptr};
+  int pa_cur = 0;
+  struct PaEvents { hipEvent_t e[2]; };
+  std::vector<PaEvents> pa_ev_pool;
+  size_t pa_ev_used = 0;
+  double pa_acc_ms = 0;
+  long long pa_acc_launches = 0;
+  int partavg_alloc(int k) {
+    const size_t cap = (size_t)P.cap, hb = (size_t)cfg.host_real_bytes;
+    unsigned char *q;
+    int rc;
+    if ((rc = dalloc(&pa_n[k], cap))) return rc;
+    if ((rc = dalloc(&q, cap * hb * pa::kSums))) return rc;
+    pa_sum[k] = q;
+    HIPCHK(hipMemsetAsync(pa_n[k], 0, cap * sizeof(int), stream));
+    HIPCHK(hipMemsetAsync(q, 0, cap * hb * pa::kSums, stream));
+    return 0;
+  }
+  template <typename H>
+  pa::State<H> partavg_state(int k) const {
+    pa::State<H> S;
+    S.npart_av = pa_n[k]; S.sum = (H *)pa_sum[k]; S.cap = P.cap;
+    return S;
+  }
+  template <typename H>
+  DiagP<H> diag_args() const {
+    DiagP<H> D;
+    D.oro = (const H *)diag_oro;
+    D.tropo[0] = (const H *)diag_tropo[0]; D.tropo[1] = (const H *)diag_tropo[1];
+    D.d3 = (const H *)diag_d3;
+    D.nxmax = cfg.nxmax; D.nymax = cfg.nymax;
+    D.dx = (H)cfg.dx; D.dy = (H)cfg.dy; D.xlon0 = (H)cfg.xlon0; D.ylat0 = (H)cfg.ylat0;
+    return D;
+  }
+  int partavg_prepare() {
+    if (pa_ev_used >= 64) { const int rc = partavg_harvest(); if (rc) return rc; }
+    if (pa_ev_used == pa_ev_pool.size()) {
+      PaEvents pe;
+      for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&pe.e[i]));
+      pa_ev_pool.push_back(pe);
+    }
+    return 0;
+  }
+  template <typename H>
+  int partavg_launch(int itime) {
+    PaEvents &pe = pa_ev_pool[pa_ev_used];
+    HIPCHK(hipEventRecord(pe.e[0], stream));
+    pa::k_partavg<R, H><<<(int)((numpart + 255) / 256), 256, 0, stream>>>(V, P, diag_args<H>(), partavg_state<H>(pa_cur), d_pbl_flag, kKeyNotDue, numpart, itime);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(pe.e[1], stream));
+    pa_ev_used++;
+    return 0;
+  }
+  int partavg_harvest() {
+    HIPCHK(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < pa_ev_used; i++) {
+      float t = 0;
+      HIPCHK(hipEventElapsedTime(&t, pa_ev_pool[i].e[0], pa_ev_pool[i].e[1])); pa_acc_ms += t;
+      pa_acc_launches++;
+    }
+    pa_ev_used = 0;
+    return 0;
+  }
+  int partavg_time(double *ms, long long *launches, int reset) override {
+    const int rc = partavg_harvest();
+    if (rc) return rc;
+    if (ms) *ms = pa_acc_ms;
+    if (launches) *launches = pa_acc_launches;
+    if (reset) { pa_acc_ms = 0; pa_acc_launches = 0; }
+    return 0;
+  }
+  template <typename H>
+  int get_partavg_t(long long first, long long count, int32_t *npart_av, void *const *sums) {
+    const pa::State<H> S = partavg_state<H>(pa_cur);
+    int rc;
+    if (npart_av && (rc = get<int32_t, int>(npart_av, S.npart_av, first, count))) return rc;
+    for (int k = 0; sums && k < pa::kSums; k++)
+      if (sums[k] && (rc = get<H, H>((H *)sums[k], S.sum + (size_t)k * S.cap, first, count))) return rc;
+    return 0;
+  }
+  int get_partavg(long long first, long long count, int32_t *npart_av, void *const *sums) override {
+    if (!cfg.device_partavg) return fail(FPX_ERR_STATE, "get_partavg: the engine was created without device_partavg");
+    if (first < 0 || count < 0 || first + count > P.cap) return fail(FPX_ERR_ARG, "get_partavg: range outside the storage spaces");
+    if (count == 0) return 0;
+    return cfg.host_real_bytes == 4 ? get_partavg_t<float>(first, count, npart_av, sums) : get_partavg_t<double>(first, count, npart_av, sums);
+  }
+  // partoutput_average.f90:54-201: the records are formed on the device, the host streams them.  Direct access, recl = 24,
+  // no record markers; the file ends with the record of the last valid particle, the records of the others in between are
+  // zero bytes (what the reference's runtime leaves in a hole).
+  template <typename H>
+  int partoutput_average_t(int itime, const char *name, int64_t *nrecords) {
+    const long long n = numpart;
+    FILE *fh = fopen(name, "wb");
+    if (!fh) return fail(FPX_ERR_ARG, std::string("partoutput_average: cannot open ") + name);
+    unsigned int *out = nullptr, *stat = nullptr;
+    void *pin = nullptr;
+    auto cleanup = [&]() {
+      if (out) (void)hipFree(out);
+      if (stat) (void)hipFree(stat);
+      if (pin) (void)hipHostFree(pin);
+      if (fh) fclose(fh);
+    };
+    unsigned int hs[2] = {0, 0};
+    bool io_ok = true;
+    if (n > 0) {
+      hipError_t e = hipMalloc(&out, (size_t)n * 24);
+      if (e == hipSuccess) e = hipMalloc(&stat, 2 * sizeof(unsigned int));
+      if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_NOMEM, std::string("partoutput_average: record buffer: ") + hipGetErrorString(e)); }
+      e = hipMemsetAsync(out, 0, (size_t)n * 24, stream);
+      if (e == hipSuccess) e = hipMemsetAsync(stat, 0, 2 * sizeof(unsigned int), stream);
+      if (e == hipSuccess) {
+        pa::k_partavg_out<R, H><<<(int)((n + 255) / 256), 256, 0, stream>>>(P, partavg_state<H>(pa_cur), n, itime, out, stat);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync(hs, stat, sizeof hs, hipMemcpyDeviceToHost, stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(stream);
+      const size_t total = (size_t)hs[1] * 24, chunk = (size_t)64 << 20;
+      if (e == hipSuccess && total) e = hipHostMalloc(&pin, std::min(chunk, total));
+      for (size_t off = 0; e == hipSuccess && io_ok && off < total; off += chunk) {
+        const size_t nbytes = std::min(chunk, total - off);
+        e = hipMemcpyAsync(pin, (const char *)out + off, nbytes, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e == hipSuccess) io_ok = fwrite(pin, 1, nbytes, fh) == nbytes;
+      }
+      if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_DEVICE, std::string("partoutput_average: ") + hipGetErrorString(e)); }
+    }
+    io_ok = (fclose(fh) == 0) && io_ok;
+    fh = nullptr;
+    cleanup();
+    if (!io_ok) return fail(FPX_ERR_ARG, std::string("partoutput_average: write error on ") + name);
+    if (nrecords) *nrecords = hs[0];
+    return 0;
+  }
+  double pa_bdate = 0;
+  bool pa_bdate_set = false;
+  int partoutput_average(int itime, const char *prefix, int64_t *nrecords) override {
+    if (!cfg.device_partavg) return fail(FPX_ERR_STATE, "partoutput_average: the engine was created without device_partavg");
+    if (!prefix) return fail(FPX_ERR_ARG, "partoutput_average: null path");
+    if (strlen(prefix) > 1000) return fail(FPX_ERR_ARG, "partoutput_average: prefix too long");
+    // with the run's start date known (fpx_set_option "bdate") the argument is path(2)(1:length(2)) and the name is formed as
+    // partoutput_average.f90:45-62 does; without it the argument is the complete path of the file
+    char name[1200];
+    if (pa_bdate_set) {
+      int hhmiss = 0;
+      const int yyyymmdd = cfg.host_real_bytes == 4 ? gv_caldate<float>(pa_bdate + (double)itime / 86400., &hhmiss) : gv_caldate<double>(pa_bdate + (double)itime / 86400., &hhmiss);
+      snprintf(name, sizeof name, "%spartposit_average_%08d%06d", prefix, yyyymmdd, hhmiss);
+    } else snprintf(name, sizeof name, "%s", prefix);
+    return cfg.host_real_bytes == 4 ? partoutput_average_t<float>(itime, name, nrecords) : partoutput_average_t<double>(itime, name, nrecords);
+  }
+
   // ---- nested grids --------------------------------------------------------------
   int nest_nxmaxn = 0, nest_nymaxn = 0;
   bool nest_loaded[kMaxNests][2] = {};
@@ -6208,6 +6355,15 @@ int fpx_calcfluxes_time(fpx_handle h, double *ms, int64_t *launches, int32_t res
   FPX_GUARD(h);
   long long l = 0;
   const int rc = h->impl->calcfluxes_time(ms, &l, reset);
+  if (launches) *launches = l;
+  return rc;
+}
+int fpx_get_partavg(fpx_handle h, int64_t first, int64_t count, int32_t *npart_av, void *const *sums) { FPX_GUARD(h); return h->impl->get_partavg(first, count, npart_av, sums); }
+int fpx_partoutput_average(fpx_handle h, int32_t itime, const char *path_or_prefix, int64_t *nrecords) { FPX_GUARD(h); return h->impl->partoutput_average(itime, path_or_prefix, nrecords); }
+int fpx_partavg_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset) {
+  FPX_GUARD(h);
+  long long l = 0;
+  const int rc = h->impl->partavg_time(ms, &l, reset);
   if (launches) *launches = l;
   return rc;
 }

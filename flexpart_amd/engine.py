@@ -10,6 +10,7 @@ in the HIP library; nothing here computes trajectories.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -107,6 +108,7 @@ class Engine:
         cfg.turboff, cfg.interpolhmix = int(sc.get("turboff", 0)), int(sc.get("interpolhmix", 0))   # com_mod.f90:777-778
         cfg.ipout, cfg.iflux, cfg.linit_cond = int(sc.get("ipout", 0)), int(sc.get("iflux", 0)), int(sc.get("linit_cond", 0))   # refused when set
         cfg.device_flux = int(sc.get("device_flux", 0))   # iflux = 1 is accepted with it: the fluxes are computed here (get_flux, fluxoutput)
+        cfg.device_partavg = int(sc.get("device_partavg", 0))   # ipout = 3 is accepted with it: the interval averages are kept here (get_partavg, partoutput_average)
         cfg.blend_mode = int(blend_mode)                # 0: from global_particles, 1 on, 2 off
         cfg.global_particles = int(global_particles)    # the run's particle count over all ranks
         cfg.pbl_slice_passes = int(pbl_slice_passes)    # 0: the engine's schedule, -1: one launch, k: k passes per launch
@@ -134,6 +136,8 @@ class Engine:
             self.upload_nests_from_scenario(sc)
         if n:
             self.upload_particles_from_scenario(sc)
+        if cfg.device_partavg and "pv" in sc and "oro" in sc:
+            self.upload_diag_fields_from_scenario(sc)
         self.gshape = None
         if "outgrid" in sc:
             self.outgrid_from_scenario(sc)
@@ -551,6 +555,40 @@ class Engine:
         """fpx_calcfluxes_time: (device ms of k_flux_save + k_calcfluxes since the last reset, steps that ran them)."""
         ms = C.c_double(0); n = C.c_int64(0)
         check(self.lib.fpx_calcfluxes_time(self.h, C.byref(ms), C.byref(n), int(reset)), "fpx_calcfluxes_time")
+        return ms.value, int(n.value)
+
+    PARTAVG_SUMS = ("cartx", "carty", "cartz", "z", "topo", "pv", "qv", "tt", "uu", "vv", "rho", "tro", "hmix", "energy")
+
+    def get_partavg(self, first=0, count=None):
+        """fpx_get_partavg: dict of npart_av (int32) and the fourteen running sums of partpos_average.f90 (PARTAVG_SUMS, the
+        host's real kind) of the particles first .. first+count-1, in particle-number order (device_partavg = 1)."""
+        n = self.n - first if count is None else count
+        out = dict(npart_av=np.zeros(n, np.int32))
+        for k in self.PARTAVG_SUMS:
+            out[k] = np.zeros(n, self.hreal)
+        ptrs = (C.c_void_p * 14)(*[out[k].ctypes.data for k in self.PARTAVG_SUMS])
+        check(self.lib.fpx_get_partavg(self.h, int(first), int(n), _vp(out["npart_av"]), ptrs), "fpx_get_partavg")
+        return out
+
+    def partoutput_average(self, itime, prefix, bdate=None):
+        """fpx_partoutput_average: writes <prefix>partposit_average_<date><time> (partoutput_average.f90) when bdate (julian
+        date of the run's start) is given, else the file `prefix` itself, and zeroes the device's sums;
+        returns (file name, number of valid particles)."""
+        n = C.c_int64(0)
+        if bdate is None:
+            check(self.lib.fpx_partoutput_average(self.h, int(itime), str(prefix).encode(), C.byref(n)), "fpx_partoutput_average")
+            return str(prefix), int(n.value)
+        import glob
+        self.set_option("bdate", repr(float(bdate)))
+        before = {f: os.path.getmtime(f) for f in glob.glob(str(prefix) + "partposit_average_*")}
+        check(self.lib.fpx_partoutput_average(self.h, int(itime), str(prefix).encode(), C.byref(n)), "fpx_partoutput_average")
+        new = sorted(f for f in glob.glob(str(prefix) + "partposit_average_*") if f not in before)
+        return (new[0] if new else None), int(n.value)
+
+    def partavg_time(self, reset=False):
+        """fpx_partavg_time: (device ms of k_partavg since the last reset, steps that ran it)."""
+        ms = C.c_double(0); n = C.c_int64(0)
+        check(self.lib.fpx_partavg_time(self.h, C.byref(ms), C.byref(n), int(reset)), "fpx_partavg_time")
         return ms.value, int(n.value)
 
     def concoutput(self, itime, prefix, area, volume, outnum, wetdep=False, drydep=False, clear=False, nest=False,

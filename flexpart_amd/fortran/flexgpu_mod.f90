@@ -35,6 +35,7 @@ module flexgpu_mod
             flexgpu_outgrid_init, flexgpu_conccalc, flexgpu_get_grids, &
             flexgpu_wet_init, flexgpu_upload_wet_fields, flexgpu_wetdepo, flexgpu_verttransform, &
             flexgpu_upload_diag_fields, flexgpu_partoutput, flexgpu_readpartpositions, &
+            flexgpu_partoutput_average, flexgpu_get_partavg, &
             flexgpu_concoutput, flexgpu_abi_sizes, flexgpu_comm_init_host, flexgpu_count_particles, flexgpu_set_option, flexgpu_get_info, &
             flexgpu_release_init, flexgpu_releaseparticles, flexgpu_split_particles, flexgpu_calcpar, &
             flexgpu_getvdep_init, flexgpu_getvdep, &
@@ -81,7 +82,8 @@ module flexgpu_mod
     integer(c_int64_t) :: global_particles
     integer(c_int32_t) :: ipout, iflux, linit_cond
     integer(c_int32_t) :: device_flux
-    integer(c_int32_t) :: reserved(2)
+    integer(c_int32_t) :: device_partavg
+    integer(c_int32_t) :: reserved(1)
   end type fpx_config
 
   type, bind(C) :: fpx_fields
@@ -329,6 +331,27 @@ module flexgpu_mod
       character(kind=c_char), intent(in) :: path(*)
       integer(c_int64_t), intent(out) :: nrec
     end function fpx_partoutput
+    integer(c_int) function fpx_partoutput_average(h, itime, path, nrec) bind(C, name='fpx_partoutput_average')
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_char
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: itime
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int64_t), intent(out) :: nrec
+    end function fpx_partoutput_average
+    integer(c_int) function fpx_get_partavg(h, first, count, npart_av, sums) bind(C, name='fpx_get_partavg')
+      import :: c_ptr, c_int, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int64_t), value :: first, count
+      type(c_ptr), value :: npart_av
+      type(c_ptr), intent(in) :: sums(14)
+    end function fpx_get_partavg
+    integer(c_int) function fpx_partavg_time(h, ms, launches, reset) bind(C, name='fpx_partavg_time')
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: ms
+      integer(c_int64_t), intent(out) :: launches
+      integer(c_int32_t), value :: reset
+    end function fpx_partavg_time
     integer(c_int) function fpx_conv_init(h, c) bind(C, name='fpx_conv_init')
       import :: c_ptr, c_int, fpx_conv_config
       type(c_ptr), value :: h
@@ -665,11 +688,13 @@ contains
   ! turboff / interpolhmix: the host's compile-time parameters (com_mod.f90:777-778) become the engine's run-time switches.
   ! device_flux = .true.: with iflux = 1 the engine computes the gross fluxes itself (calcfluxes.f90 in flexgpu_step) and the
   ! host fetches them with flexgpu_get_flux or lets flexgpu_fluxoutput write the file; without it iflux = 1 is refused.
+  ! device_partavg = .true.: with ipout = 3 the engine keeps the interval averages of partpos_average.f90 itself (in
+  ! flexgpu_step) and flexgpu_partoutput_average writes their file; without it ipout = 3 is refused.
   subroutine flexgpu_init(ierr, device, nmaxpart, compute_real_bytes, rng_mode, seed, defer_height, particle_base, &
-                          global_particles, blend_mode, device_flux)
+                          global_particles, blend_mode, device_flux, device_partavg)
     integer, intent(out) :: ierr
     integer, intent(in), optional :: device, nmaxpart, compute_real_bytes, rng_mode, blend_mode
-    logical, intent(in), optional :: defer_height, device_flux
+    logical, intent(in), optional :: defer_height, device_flux, device_partavg
     integer(c_int64_t), intent(in), optional :: seed, particle_base, global_particles
     type(fpx_config) :: cfg
     integer :: ks
@@ -712,6 +737,7 @@ contains
     cfg%global_particles = cfg%max_particles; if (present(global_particles)) cfg%global_particles = global_particles
     cfg%ipout = ipout; cfg%iflux = iflux; cfg%linit_cond = linit_cond
     cfg%device_flux = 0; if (present(device_flux)) cfg%device_flux = merge(1, 0, device_flux)
+    cfg%device_partavg = 0; if (present(device_partavg)) cfg%device_partavg = merge(1, 0, device_partavg)
     cfg%reserved = 0
     ierr = fpx_create(flexgpu_handle, cfg)
     if (ierr /= 0) return
@@ -847,6 +873,38 @@ contains
     ierr = fpx_partoutput(flexgpu_handle, int(itime, c_int32_t), trim(fname) // c_null_char, nrec)
     if (present(nrecords)) nrecords = nrec
   end subroutine flexgpu_partoutput
+
+  ! Replaces `call partoutput_average(itime)` (timemanager.f90:455; engine created with device_partavg = .true.): same file
+  ! name (partoutput_average.f90:45-62), the records formed from the sums the device kept; all sums are zero afterwards.
+  subroutine flexgpu_partoutput_average(itime, ierr, nrecords)
+    integer, intent(in) :: itime
+    integer, intent(out) :: ierr
+    integer(c_int64_t), intent(out), optional :: nrecords
+    real(kind=dp) :: jul
+    integer :: jjjjmmdd, ihmmss
+    character :: adate*8, atime*6
+    character(len=200) :: fname
+    integer(c_int64_t) :: nrec
+    jul = bdate + real(itime, kind=dp) / 86400._dp
+    call caldate(jul, jjjjmmdd, ihmmss)
+    write(adate, '(i8.8)') jjjjmmdd
+    write(atime, '(i6.6)') ihmmss
+    fname = path(2)(1:length(2)) // 'partposit_average_' // adate // atime
+    ierr = fpx_partoutput_average(flexgpu_handle, int(itime, c_int32_t), trim(fname) // c_null_char, nrec)
+    if (present(nrecords)) nrecords = nrec
+  end subroutine flexgpu_partoutput_average
+
+  ! The device's npart_av and part_av_* of the particles 1..n into com_mod's arrays (diagnostics; the run does not need it).
+  subroutine flexgpu_get_partavg(n, ierr)
+    integer, intent(in) :: n
+    integer, intent(out) :: ierr
+    type(c_ptr) :: sums(14)
+    sums(1) = loc_r(part_av_cartx); sums(2) = loc_r(part_av_carty); sums(3) = loc_r(part_av_cartz); sums(4) = loc_r(part_av_z)
+    sums(5) = loc_r(part_av_topo); sums(6) = loc_r(part_av_pv); sums(7) = loc_r(part_av_qv); sums(8) = loc_r(part_av_tt)
+    sums(9) = loc_r(part_av_uu); sums(10) = loc_r(part_av_vv); sums(11) = loc_r(part_av_rho); sums(12) = loc_r(part_av_tro)
+    sums(13) = loc_r(part_av_hmix); sums(14) = loc_r(part_av_energy)
+    ierr = fpx_get_partavg(flexgpu_handle, 0_c_int64_t, int(n, c_int64_t), loc_i(npart_av), sums)
+  end subroutine flexgpu_get_partavg
 
   ! Replaces the second half of `call readpartpositions` (readpartpositions.f90:115-148): the host has read
   ! the `header` file (:59-113) and passes its date and time; the dump path(2)//'partposit_end' is parsed

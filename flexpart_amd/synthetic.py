@@ -1048,3 +1048,88 @@ def calcfluxes_case(variant="release"):
         c[f"npoint{b}"] = (np.arange(n) + 1).astype(np.int32) if fill else (1 + ((h >> np.uint64(48)) % np.uint64(numpoint)).astype(np.int64)).astype(np.int32)
         c[f"itramem{b}"] = (int(c["itime"]) - age).astype(np.int32)
     return c
+
+
+# --------------------------------------------------------------------------
+# partpos_average / partoutput_average (tests/golden/pa_r*.npz)
+# --------------------------------------------------------------------------
+PA_SUMS = ("cartx", "carty", "cartz", "z", "topo", "pv", "qv", "tt", "uu", "vv", "rho", "tro", "hmix", "energy")
+
+
+def partavg_case():
+    """Prepared particles for the reference's partpos_average and partoutput_average, from integer hashes and IEEE-exact
+    operations only, so that the tests regenerate the fixture's inputs bit for bit.  Met grid 20 x 12 x 10 with dx = 10,
+    dy = 4 degrees from (-9.9999998, -4) -- longitudes -10 .. 180, latitudes -4 .. 40 -- and nymax = ny; the wind-field window is
+    0 .. 10800 s with memind = (2, 1).  Two output intervals: six calls (itime 900 .. 5400) and the output at 6300, three
+    more calls (6300 .. 8100) and the output at 9000.  Per call every particle has a position and a flag whether the
+    particle loop reaches it (itra1 = itime); per output an itra1.  240 particles, by j % 8:
+      5     moved in the first three calls only and terminated afterwards: a hole in both files (so are the last three
+            particles: the files end before them);
+      6     released before the fourth call: npart_av = 3 at the first output;
+      3     (the first ten of them) inside two columns with extreme values -- qv 0.07, pv +-400, uu 180, vv -170 and, on the
+            two top levels, tt 150 K in the south and 330 K in the north -- half of them above 70 km: the clamps of z, qv,
+            pv, tt, uu, vv and energy;
+      else  a cloud over lon -8 .. 10, lat -3 .. 38, drifting from call to call.
+    Particles 1 and 9 sit on the northern boundary row (yt = ny - 1: the jyp >= nymax fix-up), particles 2 and 10 at
+    longitude 180.0000001 in an 8-byte build: the angle goes to radians and back with the same pi180, so the result exceeds
+    180 -- the wrap of partoutput_average.f90:103 -- only for a longitude in the sliver between 180 and pi / pi180 =
+    180.0000002 (the pi of par_mod is a little short).  A 4-byte real cannot reach the wrap at all: xlon0 and the longitude
+    round to -10 and 180, and the largest atan2(..) / pi180, 180.000006, rounds to 180.0."""
+    nx, ny, nz, n = 20, 12, 10, 240
+    height = make_height(nz)
+    f = make_fields(nx, ny, nz, height)
+    c = dict(grid=np.array([nx, ny, nz], np.int32), geom=np.array([10.0, 4.0, -9.9999998, -4.0], np.float64), nymax=ny, height=height,
+             memtime=np.array([0, 10800], np.int32), memind=np.array([2, 1], np.int32), bdate=GV_BDATE, npart=n,
+             calls=((900, 1800, 2700, 3600, 4500, 5400), (6300, 7200, 8100)), outputs=(6300, 9000))
+    per = nx - 1
+    i = np.arange(nx, dtype=np.int64)[None, None, :]
+    j = np.arange(ny, dtype=np.int64)[None, :, None]
+    k = np.arange(nz, dtype=np.int64)[:, None, None]
+    z = height[:, None, None]
+    oro = 400.0 * (1.0 + _wave(2 * i[0] + 3 * j[0], per)) + 0.0 * j[0]
+    pv = np.empty((2, nz, ny, nx)); qv = np.empty((2, nz, ny, nx))
+    for m in range(2):
+        sh = 10 * m
+        pv[m] = 2.0 * (1.0 + 0.5 * _wave(i + sh + k, per)) * (1.0 + z / 6000.0) * (2.0 * j / float(ny - 1) - 1.0)
+        qv[m] = 0.012 / (1.0 + z / 2500.0) ** 2 * (0.6 + 0.4 * _wave(2 * (i + sh) + j, per)) + 0.0 * k
+    uu, vv, tt = f["uu"].copy(), f["vv"].copy(), f["tt"].copy()
+    hot = slice(3, 5)                                    # columns 3 and 4: longitudes 20 and 30
+    qv[..., hot] = 0.07
+    pv[:, :, :6, hot] = 400.0
+    pv[:, :, 6:, hot] = -400.0
+    uu[..., hot] = 180.0
+    vv[..., hot] = -170.0
+    tt[:, nz - 2:, :6, hot] = 150.0
+    tt[:, nz - 2:, 6:, hot] = 330.0
+    for key, a in (("oro", oro), ("pv", pv), ("qv", qv), ("tt", tt), ("uu", uu), ("vv", vv), ("rho", f["rho"]),
+                   ("tropopause", f["tropopause"]), ("hmix", f["hmix"])):
+        c[key] = a
+    idx = np.arange(n)
+    cls = idx % 8
+    cls[n - 3:] = 5
+    extreme = (cls == 3) & (idx < 80)
+    x0 = 0.2 + 1.8 * _uniform01(n, 9501)
+    y0 = 0.3 + 10.0 * _uniform01(n, 9502)
+    z0 = 30.0 + 11000.0 * _uniform01(n, 9503) ** 2
+    x0[extreme] = 3.05 + 0.9 * _uniform01(n, 9504)[extreme]
+    z0[extreme & (idx % 16 == 3)] = 70000.0 + 9000.0 * _uniform01(n, 9505)[extreme & (idx % 16 == 3)]
+    ncall = 0
+    for iv, times in enumerate(c["calls"]):
+        for itime in times:
+            s = 9600 + 20 * ncall
+            xt = x0 + 0.02 * ncall + 0.03 * (_uniform01(n, s + 1) - 0.5)
+            yt = y0 + 0.015 * ncall + 0.03 * (_uniform01(n, s + 2) - 0.5)
+            zt = np.abs(z0 + 40.0 * (_uniform01(n, s + 3) - 0.5))
+            xt[extreme] = np.minimum(xt[extreme], 3.98)
+            yt[[1, 9]] = float(ny - 1)
+            xt[[2, 10]] = 18.99999999
+            due = np.ones(n, bool)
+            due[cls == 5] = ncall < 3
+            due[cls == 6] = ncall >= 3
+            c[f"xt{ncall}"], c[f"yt{ncall}"], c[f"zt{ncall}"], c[f"due{ncall}"] = xt, yt, zt, due.astype(np.int32)
+            ncall += 1
+        itra1 = np.full(n, c["outputs"][iv], np.int32)
+        itra1[cls == 5] = DEAD
+        c[f"itra1_{iv}"] = itra1
+    c["ncalls"] = ncall
+    return c

@@ -123,7 +123,7 @@ typedef struct {
   int64_t global_particles;
   /* Diagnostics inside the particle loop that the engine does NOT compute (out of scope): the host passes
    * its COMMAND switches and fpx_create refuses (FPX_ERR_UNSUPPORTED) a run that would need them, instead of dropping their
-   * output silently: ipout = 3 (partpos_average, timemanager.f90:617), iflux = 1 (calcfluxes, :623; unless device_flux = 1,
+   * output silently: ipout = 3 (partpos_average, timemanager.f90:617; unless device_partavg = 1, below), iflux = 1 (calcfluxes, :623; unless device_flux = 1,
    * below), linit_cond >= 1 (initial_cond_calc, :631,702).  Zero-initialised fields mean "not requested". */
   int32_t ipout, iflux, linit_cond;
   /* Gross mass fluxes on the device (calcfluxes.f90, timemanager.f90:623): iflux = 1 is accepted only together with
@@ -132,7 +132,13 @@ typedef struct {
    * allocates flux, and fpx_step runs two more kernels (one before, one after the particle is moved); without it nothing
    * is allocated and the step launches what it always did. */
   int32_t device_flux;
-  int32_t reserved[2];
+  /* Per-particle averages over the output interval on the device (partpos_average.f90:31-184, timemanager.f90:617): ipout = 3
+   * is accepted only together with device_partavg = 1, by which the host declares that it lets the engine write the
+   * partposit_average_* files (fpx_partoutput_average); ipout = 3 alone is refused as above, device_partavg = 1 with
+   * ipout != 3 is FPX_ERR_ARG.  With it fpx_create allocates fifteen values per storage space and fpx_step runs one more
+   * kernel after the particle is moved; without it nothing is allocated and the step launches what it always did. */
+  int32_t device_partavg;
+  int32_t reserved[1];
 } fpx_config;
 
 /* One time slot of the met fields the path gathers from (com_mod.f90:355-371,
@@ -657,6 +663,36 @@ int fpx_fluxoutput(fpx_handle h, int32_t itime, const fpx_fluxout *f, const char
 /* cumulative device time (ms) of k_flux_save + k_calcfluxes, by events of their own, and the number of steps that ran
  * them since the last reset.  fpx_kernel_times keeps its meaning: the two kernels lie outside its intervals. */
 int fpx_calcfluxes_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset);
+/* ---- per-particle averages over the output interval (fpx_config.device_partavg = 1, ipout = 3) --------------------
+ * fpx_step then does what `if (ipout.eq.3) call partpos_average(itime,j)` (timemanager.f90:617; the routine:
+ * partpos_average.f90:31-184) does for every particle it moves: with the position advance left and the step's itime it
+ * interpolates oro, pv, qv, tt, uu, vv, rho, tropopause and hmix to the particle, forms the energy (:155) and the
+ * Cartesian unit vector of the position (:165-169), adds them to fourteen running sums of the particle's storage space and
+ * counts the call in npart_av -- all in the host's real kind, in the reference's order of operations.  uu and vv are read
+ * from the two unblended time slots whatever blend_mode says.  The diag fields (fpx_upload_diag_fields or
+ * fpx_verttransform_ecmwf: oro, pv, qv, tt of both slots) must be on the device at the first step, else FPX_ERR_STATE.
+ * The sums are zero at creation and only fpx_partoutput_average resets them: like the reference, release and splitting
+ * leave the sums of the storage space they take as they find them.  One deviation: a particle whose advance ended
+ * outside the grid or with a non-finite position (nstop > 1; it is terminated in the same step) is not averaged in that
+ * step -- the reference would index the fields out of bounds there.
+ * fpx_get_partavg copies npart_av and the sums of the particles first .. first+count-1 (0-based particle numbers) to the
+ * host: sums[14] = cartx, carty, cartz, z, topo, pv, qv, tt, uu, vv, rho, tro, hmix, energy (com_mod.f90:688-691), each
+ * host_real_bytes per value; a NULL pointer skips that array. */
+int fpx_get_partavg(fpx_handle h, int64_t first, int64_t count, int32_t *npart_av, void *const *sums);
+/* Replaces `if (ipout.eq.3) call partoutput_average(itime)` (timemanager.f90:455; the routine:
+ * partoutput_average.f90:54-201): for every particle with itra1 = itime the sums are divided by npart_av, the mean
+ * position is projected back to longitude and latitude, the twelve values are scaled, clamped to +-32766 and rounded to
+ * int16 (:103-156) and written as record number = particle number of a direct-access file with recl = 24 (no record
+ * markers; ishort_energy is computed by the reference but not written).  The file ends with the last valid particle's
+ * record; records of particles that are not valid hold zero bytes.  Afterwards the fifteen values of EVERY storage space
+ * are zero (:172-186).  The records are this rank's particles; nothing is reduced over ranks.
+ * path_or_prefix: once the run's start date is known -- fpx_set_option(h, "bdate", "<julian date>") -- it is
+ * path(2)(1:length(2)) and the file is "<prefix>partposit_average_<yyyymmdd><hhmmss>" of bdate + itime/86400 (caldate);
+ * without it, it is the complete path of the file.  *nrecords (may be NULL): the number of valid particles written. */
+int fpx_partoutput_average(fpx_handle h, int32_t itime, const char *path_or_prefix, int64_t *nrecords);
+/* cumulative device time (ms) of k_partavg, by events of its own, and the number of steps that ran it since the last
+ * reset.  fpx_kernel_times keeps its meaning: the kernel lies outside its intervals. */
+int fpx_partavg_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset);
 /* Communicator for the grid reduction, one of:
  * (a) RCCL: rank 0 obtains an id (128 bytes), the host distributes it (MPI_Bcast / torch.distributed / a file), every
  *     rank calls fpx_comm_init; the reduction then runs device to device on the handle's stream. */
