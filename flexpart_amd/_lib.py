@@ -198,7 +198,7 @@ SYMBOLS = [
     "fpx_step", "fpx_step_async", "fpx_sync", "fpx_counters", "fpx_kernel_time", "fpx_kernel_times", "fpx_sort_particles",
     "fpx_seed_particles", "fpx_stream", "fpx_outgrid_init", "fpx_set_output_times", "fpx_conccalc",
     "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
-    "fpx_wetdepo", "fpx_get_wetgrid", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_find_level_probe",
+    "fpx_wetdepo", "fpx_get_wetgrid", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_cbl_probe", "fpx_find_level_probe",
     "fpx_outgrid_nest_init", "fpx_get_grids_nest", "fpx_receptors_init", "fpx_get_receptors", "fpx_upload_wet_nest_fields",
     "fpx_verttransform_ecmwf", "fpx_verttransform_nest", "fpx_verttransform_time", "fpx_calcpar", "fpx_calcpar_time", "fpx_getvdep_init", "fpx_getvdep", "fpx_getvdep_time", "fpx_calcpv_init", "fpx_get_pvh", "fpx_calcpv_time", "fpx_upload_diag_fields", "fpx_partoutput", "fpx_partoutput_time", "fpx_readpartpositions", "fpx_concoutput",
     "fpx_checkpoint_write", "fpx_checkpoint_read",
@@ -226,6 +226,7 @@ def load():
     lib.fpx_stream.argtypes = [vp]
     lib.fpx_math_probe.argtypes = [C.c_int32, vp, vp, C.c_int64]
     lib.fpx_hanna_probe.argtypes = [vp, vp, C.c_int64]
+    lib.fpx_cbl_probe.argtypes = [C.c_int32, vp, vp, C.c_int64]
     lib.fpx_find_level_probe.argtypes = [C.c_int32, vp, C.c_int32, vp, vp, C.c_int64, vp, vp]
     lib.fpx_upload_wet_nest_fields.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(FpxWetFields), C.c_int32]
     lib.fpx_outgrid_nest_init.argtypes = [vp, C.POINTER(FpxOutgridNest)]
@@ -316,6 +317,18 @@ def load():
     lib.fpx_get_info.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
     _lib = lib
     return lib
+
+
+def cbl_probe(form, points):
+    """fpx_cbl_probe on an (n, 10) array of wp, zp/h, wst^3 * transition, 1/h, rhograd/rhoa, sigmaw, 1/sigmaw, dsigmawdz, tlw,
+    ldirect: -> (n, 3) array of ath, bth, flagrein.  form 0: cbl() in the reference's dimensional variables, 1: the normalised body."""
+    import numpy as np
+    x = np.ascontiguousarray(points, np.float64)
+    if x.ndim != 2 or x.shape[1] != 10:
+        raise ValueError("cbl_probe: points must be an (n, 10) array")
+    out = np.empty((x.shape[0], 3))
+    check(load().fpx_cbl_probe(int(form), x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), x.shape[0]), "fpx_cbl_probe")
+    return out
 
 
 class FpxError(RuntimeError):

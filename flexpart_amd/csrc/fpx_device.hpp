@@ -1371,17 +1371,35 @@ FPX_DEV R cbl_transition(R h, R ol) {   // cbl.f90:79-81
 //   the two cube roots of cbl.f90:115-121 from one x**(-1/3) (m_cuberoot_parts).
 // What is left is 2 reciprocals, 1 sqrt, 2 coupled sqrt+rsqrt, 1 rsqrt, 2 exp and 2 erf per call
 // (the straightforward form has 20 divisions, 7 square roots, 1 log and 4 exp).
+// The normalised form (FORM = FPX_CBL_NORMALISED = 1, fp64 only; 0 and every float instance keep the body described so far, in
+// the reference's dimensional variables).  With g = sw*rs and iv = a1^0.5 (4+r)^0.5 / sw, so that g*iv = 4+r = 1/(al*bl):
+//   sigmawa = g*bl, sigmawb = g*al, 1/sigmawa = iv*al, 1/sigmawb = iv*bl, wa = f*g*bl, wb = f*g*al;
+//   wa/sigmawa = f exactly, so da = wold*iv*al - f and db = wold*iv*bl + f: one fma each from ua = wold/sigmawa, ub = wold/sigmawb;
+//   dsigmawa = g*bl*ca, dsigmawb = g*al*cb with ca = ds - mh*(dal*a1 + al*bl*ffd), cb = ds + mh*(dal*a1 - al*bl*ffd),
+//     ds = dsigmawdz/sw, mh = rs^2/2;  dwa = g*bl*(df + f*ca), dwb = g*al*(df + f*cb);
+//   Ta = g*bl*ta, ta = al*(df + f*(ca + rx)) + f*dal;   Tb = g*al*tb, tb = bl*(df + f*(cb + rx)) - f*dal;
+//   wold = ua*g*bl = ub*g*al, so Ua = (g*bl)^2 * ka, ka = al*(ca*ua^2 + (ca + rx) + ua*df) + dal, and
+//     Ub = (g*al)^2 * kb, kb = bl*(cb*ub^2 + (cb + rx) - ub*df) - dal;  pa = iv*al*ea, pb = iv*bl*eb, hence
+//     Ua*pa = g*bl*ea*ka and Ub*pb = g*al*eb*kb (g*iv*al*bl = 1);
+//   Phi = g*phin, phin = (0.5 sqrt(2 pi))*(al*tb*erfb - bl*ta*erfa) + bl*ea*ka + al*eb*kb;
+//   ptot = iv*pn, pn = al^2 ea + bl^2 eb;   Q = iv^2*qn, qn = da al^3 ea + db bl^3 eb;
+//   ath = (g*phin - w2tl*iv^2*qn)/(iv*pn) = (w2/pn) * (phin/a1 - (iv/tlw)*qn), since g/iv = w2/a1.
+// No sigmawa/b, wa/b, dwa/b, dsigmawa/b, pa/b, Ta/b, Ua/b is formed: by a hand count of the source about 76 fp64 operations behind
+// the two roots of 4+r where the dimensional body has about 92; the compiler's listing of the probe kernel has 15 fewer
+// (profiles/r10/README.md).
 // `wt` = wst^3 * transition (cbl.f90:79-81,103-104): depends on h, ol, wst only and is passed in.
 // `z` = zp/h as zp*ih: the caller has it already (the zeta of the sub-step before, or its own product in a pass's first).
 // ST: the source of the lookup tables of exp and of the error-function pair (the loop kernel's stash)
-template <typename R, typename ST>
+#ifndef FPX_CBL_NORMALISED
+#define FPX_CBL_NORMALISED 1
+#endif
+template <int FORM = FPX_CBL_NORMALISED, typename R, typename ST>
 FPX_DEV void cbl(const ST &S, int ldirect, R wp, R z /* zp * ih */, R wt /* wst^3 * transition */, R ih /* 1/h */, R rhoaux /* rhograd/rhoa */, R sigmaw, R irw /* 1/sigmaw */, R dsigmawdz, R tlw,
                  R &ath, R &bth, int &flagrein) {
   const R usurad2 = K(0.7071067812), usurad2p = K(0.3989422804), costluar4 = K(0.66667), eps = K(0.000001);
   const unsigned int tdir = ldirect < 0 ? 0x80000000u : 0u;   // timedir = ldirect = +-1 as a sign mask: x * timedir = m_flip(x, tdir), exactly
   const R w2 = sigmaw * sigmaw;
   const R rtl = m_rsqrt(tlw);                        // tlw >= 30 (hanna_short.f90:91)
-  const R w2tl = w2 * (rtl * rtl);                   // (C0/2)*alfa
   const R wold = m_flip(wp, tdir);
   const R omz = K(1.) - z;
   const R omz05 = m_sqrtp(omz), omz15 = omz * omz05;
@@ -1415,6 +1433,43 @@ FPX_DEV void cbl(const ST &S, int ldirect, R wp, R z /* zp * ih */, R wt /* wst^
   const R bluarw = K(1.) - aluarw;
   const R ir4 = ir405 * ir405;                       // = aluarw*bluarw
   const R daluarw = K(-2.) * dxluarw * (ir405 * ir4);
+  if constexpr (FORM != 0 && sizeof(R) == 8) {
+    // the normalised form (derivation above): everything in units of g = sigmaw*rs, which leaves ath as one factor at the end
+    const R rx = rhoaux;
+    const R rs = r405 * ia105;
+    const R mh = (K(0.5) * rs) * rs;
+    const R ds = dsigmawdz * irw;
+    const R da1 = daluarw * a1, abf = ir4 * ffd;
+    const R ce = m_fma(-mh, abf, ds);
+    const R ca = m_fma(-mh, da1, ce), cb = m_fma(mh, da1, ce);
+    const R car = ca + rx, cbr = cb + rx;
+    const R fdal = fluarw * daluarw;
+    const R ta = m_fma(aluarw, m_fma(fluarw, car, dfluarw), fdal);
+    const R tb = m_fma(bluarw, m_fma(fluarw, cbr, dfluarw), -fdal);
+    const R iv = irw * (a105 * r405);
+    const R isa = iv * aluarw, isb = iv * bluarw;
+    const R ua = wold * isa, ub = wold * isb;
+    const R da = m_fma(wold, isa, -fluarw), db = m_fma(wold, isb, fluarw);
+    if (m_abs(da) > K(6.) && m_abs(db) > K(6.)) flagrein = 1;
+    const R da2 = da * da, db2 = db * db;
+    const R ea = S.exp_nh(da2), eb = S.exp_nh(db2);
+    const R ka = m_fma(aluarw, m_fma(ua, dfluarw, m_fma(ca, ua * ua, car)), daluarw);
+    const R kb = m_fma(bluarw, m_fma(-ub, dfluarw, m_fma(cb, ub * ub, cbr)), -daluarw);
+    const R aea = aluarw * ea, beb = bluarw * eb;          // al*ea, bl*eb feed pn and qn; the cross products bl*ea, al*eb below feed phin
+    const R a2ea = aluarw * aea, b2eb = bluarw * beb;
+    const R pn = a2ea + b2eb;
+    const R qn = m_fma(da * aluarw, a2ea, (db * bluarw) * b2eb);
+    const R cu = usurad2 * usurad2 - K(0.5);
+    R erfa, erfb;
+    S.erf_pair(da * usurad2, ea - ea * (da2 * cu), db * usurad2, eb - eb * (db2 * cu), erfa, erfb);
+    const R gs = m_fma(bluarw * ea, ka, (aluarw * eb) * kb);
+    const R er = m_fma(aluarw * tb, erfb, -((bluarw * ta) * erfa));
+    const R phin = m_fma(K(0.5) / usurad2p, er, gs);
+    ath = (w2 * m_rcp(pn)) * m_fma(ia105 * ia105, phin, -m_flip(((rtl * rtl) * iv) * qn, tdir));
+    bth = (sigmaw * K(1.4142135623730951)) * rtl;
+    return;
+  }
+  const R w2tl = w2 * (rtl * rtl);                   // (C0/2)*alfa
   const R dbluarw = -daluarw;
   const R rs = r405 * ia105, rs3 = rs * (rs * rs);
   const R qa05 = bluarw * rs, qb05 = aluarw * rs;

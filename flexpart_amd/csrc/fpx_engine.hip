@@ -1644,6 +1644,27 @@ __global__ void __launch_bounds__(kBlock) k_hanna_probe(int which, const double 
   }
 }
 
+// diagnostics (fpx_cbl_probe): cbl() of a fine sub-step on plain arrays, called as the fp64 gas kernels of k_pbl_loop call it -- a
+// StashErfTab over the block's LDS copies of the exp table and the error-function table.  in[10i .. 10i+9] = wp, z (= zp/h), wt
+// (= wst^3 * transition), 1/h, rhograd/rhoa, sigmaw, 1/sigmaw, dsigmawdz, tlw, ldirect; out[3i .. 3i+2] = ath, bth, flagrein.
+// FORM 0: the body in the reference's dimensional variables, 1: the normalised one; an instance each, whatever FPX_CBL_NORMALISED is.
+template <int FORM>
+__global__ void __launch_bounds__(kBlock) k_cbl_probe(const double *__restrict__ in, double *__restrict__ out, long long n) {
+  __shared__ double lds_tab[kLdsTabDoubles];
+  __shared__ __align__(16) double lds_erft[kErfcxIntervals * kErfcxRow];
+  for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
+  for (int k = threadIdx.x; k < kErfcxIntervals * kErfcxRow; k += blockDim.x) lds_erft[k] = kErfcxTab[k];
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double *x = in + 10 * i;
+  const StashErfTab S = make_stash<double, true>(nullptr, (lds_tab_ptr)lds_tab, (lds_erft_ptr)lds_erft);
+  double ath = 0., bth = 0.;
+  int flagrein = 0;
+  cbl<FORM>(S, x[9] < 0. ? -1 : 1, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], ath, bth, flagrein);
+  out[3 * i] = ath; out[3 * i + 1] = bth; out[3 * i + 2] = (double)flagrein;
+}
+
 // diagnostics (fpx_find_level_probe): the level search of a Langevin pass on plain arrays, the height column in LDS as in k_pbl_loop.
 // which = 0: find_level_from with the point's guess (0: none); which = 1: find_level and the two heights the pass read after it.
 // One launch per form.  idx[i] = the level, zz[2i], zz[2i+1] = height(indz), height(indz+1).
@@ -6425,6 +6446,24 @@ int fpx_hanna_probe(const double *in, double *out, int64_t n) {
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out + 10 * n * which, dy, 10 * n * sizeof(double), hipMemcpyDeviceToHost);
   }
+  (void)hipFree(dx); (void)hipFree(dy);
+  return e == hipSuccess ? FPX_OK : FPX_ERR_DEVICE;
+}
+
+int fpx_cbl_probe(int32_t form, const double *in, double *out, int64_t n) {
+  if ((form != 0 && form != 1) || !in || !out || n < 0) return FPX_ERR_ARG;
+  if (n == 0) return FPX_OK;
+  double *dx = nullptr, *dy = nullptr;
+  if (hipMalloc(&dx, 10 * n * sizeof(double)) != hipSuccess) return FPX_ERR_NOMEM;
+  if (hipMalloc(&dy, 3 * n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); return FPX_ERR_NOMEM; }
+  hipError_t e = hipMemcpy(dx, in, 10 * n * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const unsigned blocks = (unsigned)((n + fpx::kBlock - 1) / fpx::kBlock);
+    if (form == 0) fpx::k_cbl_probe<0><<<blocks, fpx::kBlock>>>(dx, dy, n);
+    else fpx::k_cbl_probe<1><<<blocks, fpx::kBlock>>>(dx, dy, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dy, 3 * n * sizeof(double), hipMemcpyDeviceToHost);
   (void)hipFree(dx); (void)hipFree(dy);
   return e == hipSuccess ? FPX_OK : FPX_ERR_DEVICE;
 }

@@ -794,6 +794,12 @@ int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n);
  * -h/ol > 5 (0/1) -- computed the way the engine does, from the step's invariants as k_prep takes them and the Langevin kernel's
  * stash holds them (out[10i..10i+9]), and by the plain form (out[10n + 10i ..]).  The two halves must agree in every bit. */
 int fpx_hanna_probe(const double *in, double *out, int64_t n);
+/* Diagnostics: cbl() of one fine sub-step of the Langevin kernel (cbl.f90:70-210) for n points in[10i..10i+9] = wp, zp/h,
+ * wst^3 * transition (cbl.f90:79-81), 1/h, rhograd/rhoa, sigmaw, 1/sigmaw, dsigmawdz, tlw, ldirect (+-1), evaluated as the fp64 gas
+ * kernels do, with the exponential and error-function tables in LDS: out[3i..3i+2] = ath, bth, flagrein (0/1).  form 0: the body
+ * in the reference's dimensional variables, 1: the normalised one (fpx_device.hpp, FPX_CBL_NORMALISED chooses which of them the
+ * kernels run; the probe has both). */
+int fpx_cbl_probe(int32_t form, const double *in, double *out, int64_t n);
 /* Diagnostics: the level search of a Langevin pass for n heights z[i] in the column height[0..nz-1] (2 <= nz, strictly increasing;
  * real_bytes 4 or 8 is the type of height, z and zz), started from guess[i] -- the level of the lane's previous pass, 1..nz-1, or
  * 0 for none (any other value counts as none) -- and the plain bisection.  idx[i], zz[2i], zz[2i+1] = the level indz and
