@@ -29,6 +29,7 @@
 #include "fpx_partavg.hpp"
 #include "fpx_convect.hpp"
 #include "fpx_rng_host.hpp"
+#include "fpx_host_res.hpp"
 
 namespace fpx {
 
@@ -2142,8 +2143,7 @@ struct Engine : EngineBase {
   long long numpart = 0;
   // owned device memory
   std::vector<void *> owned;
-  void *staging = nullptr;
-  size_t staging_bytes = 0;
+  Scratch staging;
   unsigned int *slot_of_pid = nullptr;   // only after a locality sort; read it through slot_map()
   bool slot_map_dirty = false;
   // Time-blended wind packs of the step in flight (View::w3t0 / w3t1).  Worth their 0.65 GB of extra traffic per step only
@@ -2191,8 +2191,7 @@ struct Engine : EngineBase {
   Parts<R> P2;                           // second particle buffer set (sort ping-pong), allocated lazily
   bool have_p2 = false;
   unsigned int *d_keys = nullptr, *d_keys2 = nullptr, *d_vals = nullptr, *d_vals2 = nullptr;
-  void *d_sort_tmp = nullptr;
-  size_t sort_tmp_bytes = 0;
+  Scratch d_sort_tmp;
   Stats *d_stats = nullptr;
   unsigned int *d_pbl_list = nullptr, *d_pbl_ctr = nullptr;   // the counters of the work list and of the launches that go through it (layout: k_list_counts)
   unsigned int *d_surv[2] = {nullptr, nullptr};               // lists of the suspended particles (ping-pong between launches), allocated with the first sliced step
@@ -2224,8 +2223,7 @@ struct Engine : EngineBase {
   // host-supplied all-reduce (fpx_comm_init_host): the transport of an MPI host, or gloo in the tests
   fpx_allreduce_fn host_allreduce = nullptr;
   void *host_allreduce_user = nullptr;
-  void *red_pin = nullptr;               // pinned bounce buffer of the host transport: [send | recv]
-  size_t red_pin_bytes = 0;
+  Scratch red_pin{true};                 // pinned bounce buffer of the host transport: [send | recv]
   // Receive buffers of the grid reduction (the reference's gridunc0, drygridunc0, wetgridunc0, griduncn0, ... and
   // creceptor0: mpi_mod.f90:2451-2492,2543-2569; allocated in outgrid_init.f90:220-225).  The per-rank partial sums
   // stay untouched in Gp.*: drygridunc / wetgridunc accumulate over the whole run and are reduced again at every
@@ -2234,8 +2232,7 @@ struct Engine : EngineBase {
   float *drygridunc0 = nullptr, *wetgridunc0 = nullptr, *drygriduncn0 = nullptr, *wetgriduncn0 = nullptr;
   bool red_valid[7] = {};                // which receive buffers hold the sums of the last reduction
   enum { RG_GRID = 0, RG_DRY, RG_WET, RG_GRIDN, RG_DRYN, RG_WETN, RG_REC };
-  void *d_sel_tmp = nullptr;
-  size_t sel_tmp_bytes = 0;
+  Scratch d_sel_tmp;
   int pbl_grid = 0, pbl_per_cu = 0;
   // TABLE_SEQ state
   HostRng<float> rng4;
@@ -2251,11 +2248,9 @@ struct Engine : EngineBase {
   std::vector<float> h_dcas4, h_dcas14;
   std::vector<double> h_dcas8, h_dcas18;
   // timing
-  struct StepEvents { hipEvent_t e[5]; };   // before k_prep | before k_pbl_loop | after it | after k_pbl_finish | after k_prep (before the work-list sort)
-  std::vector<StepEvents> ev_pool;
-  size_t ev_used = 0;
-  double acc_ms = 0, acc_part_ms[4] = {0, 0, 0, 0};   // k_prep + work list | k_pbl_loop | k_pbl_finish | k_prep alone
-  long long acc_launches = 0;
+  // events: before k_prep | before k_pbl_loop | after it | after k_pbl_finish | after k_prep (before the work-list sort)
+  // intervals: the step | k_prep + work list | k_pbl_loop | k_pbl_finish | k_prep alone
+  IntervalTimer<5> step_timer{{0, 3}, {0, 1}, {1, 2}, {2, 3}, {0, 4}};
   unsigned int step_counter = 0;
 
   template <typename T>
@@ -2265,13 +2260,6 @@ struct Engine : EngineBase {
     if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
     owned.push_back(q);
     *p = (T *)q;
-    return 0;
-  }
-  int ensure_staging(size_t bytes) {
-    if (bytes <= staging_bytes) return 0;
-    if (staging) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(staging)); staging = nullptr; staging_bytes = 0; }
-    HIPCHK(hipMalloc(&staging, bytes));
-    staging_bytes = bytes;
     return 0;
   }
 
@@ -2427,22 +2415,7 @@ struct Engine : EngineBase {
   ~Engine() override {
     if (stream) (void)hipStreamSynchronize(stream);
     for (auto &e : pinned_host) (void)hipHostUnregister(const_cast<void *>(e.first));
-    for (auto &e : ev_pool) for (int i = 0; i < 5; i++) (void)hipEventDestroy(e.e[i]);
-    for (auto &e : fx_ev_pool) for (int i = 0; i < 4; i++) (void)hipEventDestroy(e.e[i]);
-    for (auto &e : pa_ev_pool) for (int i = 0; i < 2; i++) (void)hipEventDestroy(e.e[i]);
-    for (void *q : owned) (void)hipFree(q);
-    if (staging) (void)hipFree(staging);
-    if (d_sort_tmp) (void)hipFree(d_sort_tmp);
-    if (d_sel_tmp) (void)hipFree(d_sel_tmp);
-    if (conv_scr) (void)hipFree(conv_scr);
-    if (conv_scan_tmp) (void)hipFree(conv_scan_tmp);
-    if (conv_alive) (void)hipFree(conv_alive);
-    if (rel_flags_buf) (void)hipFree(rel_flags_buf);
-    if (rel_rank_buf) (void)hipFree(rel_rank_buf);
-    if (rel_tmp_buf) (void)hipFree(rel_tmp_buf);
-    if (redist_dev) (void)hipFree(redist_dev);      // (d_w3t: dalloc'ed, freed with the engine's other owned buffers)
-    if (d_sort_rec) (void)hipFree(d_sort_rec);
-    if (red_pin) (void)hipHostFree(red_pin);
+    for (void *q : owned) (void)hipFree(q);         // (the scratch buffers and the timers' events free themselves: fpx_host_res.hpp)
     if (comm) (void)ncclCommDestroy(comm);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -2473,10 +2446,9 @@ struct Engine : EngineBase {
   template <typename T, typename Launch>
   int staged_launch(const void *src, size_t n, bool on_device, Launch launch) {
     if (!on_device) {
-      int rc = ensure_staging(n * sizeof(T));
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(staging, src, n * sizeof(T), hipMemcpyHostToDevice, stream));
-      src = staging;
+      HIPCHK(staging.reserve(n * sizeof(T), stream));
+      HIPCHK(hipMemcpyAsync(staging.as(), src, n * sizeof(T), hipMemcpyHostToDevice, stream));
+      src = staging.as();
     }
     launch((const T *)src);
     HIPCHK(hipGetLastError());
@@ -2704,7 +2676,7 @@ struct Engine : EngineBase {
     vt::Out<H> O{D(UU), D(VV), D(WW), D(TT), D(QV), D(PV), D(RHO), D(DRHO), D(UPOL), D(VPOL), D(UVZ), D(WZ), D(RHOH), D(PINM)};
     // pvh = NULL: calcpv.f90 / calcpv_nests.f90 on the arrays just uploaded, into D(PVH), under an event pair of its own.
     // ppml and theta go to UVZ and WZ, which the transform below overwrites anyway.
-    hipEvent_t p0 = nullptr, p1 = nullptr;
+    Events<2> pev, ev;
     if (!m->pvh) {
       pv::Args<H> P;
       P.nx = gnx; P.ny = gny; P.nuvz = m->nuvz; P.nxmax = gnxmax; P.nymax = gnymax;
@@ -2712,18 +2684,17 @@ struct Engine : EngineBase {
       P.dx = nest ? (H)pv_dxn[nest - 1] : (H)cfg.dx; P.dy = G.dy; P.ylat0 = G.ylat0;
       P.uuh = D(UUH); P.vvh = D(VVH); P.tth = D(TTH); P.ps = D(PS); P.akz = D(AKZ); P.bkz = D(BKZ);
       P.ppml = D(UVZ); P.theta = D(WZ); P.pvh = D(PVH);
-      HIPCHK(hipEventCreate(&p0)); HIPCHK(hipEventCreate(&p1));
-      HIPCHK(hipEventRecord(p0, stream));
+      HIPCHK(pev.create());
+      HIPCHK(hipEventRecord(pev[0], stream));
       const dim3 gp((gnx * gny + 255) / 256, m->nuvz);
       pv::k_theta<H><<<gp, 256, 0, stream>>>(P);
       pv::k_pv<H><<<gp, 256, 0, stream>>>(P);
       if (P.nglobal || P.sglobal) pv::k_pole<H><<<dim3((m->nuvz + 63) / 64, 2), 64, 0, stream>>>(P);
       HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(p1, stream));
+      HIPCHK(hipEventRecord(pev[1], stream));
     }
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, stream));
+    HIPCHK(ev.create());
+    HIPCHK(hipEventRecord(ev[0], stream));
     const int ncol = gnx * gny, nb = (ncol + 255) / 256;
     const size_t sm = (size_t)nz * sizeof(H);
     const dim3 g3(nb, nz);
@@ -2764,7 +2735,7 @@ struct Engine : EngineBase {
       vt::k_vt_polerow<H><<<nz, 64, smrow, stream>>>(G, O, 1);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
+    HIPCHK(hipEventRecord(ev[1], stream));
     // repack into the gather layout, as upload_fields / upload_nest_fields do from the staged host arrays
     const int s = slot - 1;
     auto pk = [&](const H *in, const R *outp, int stride, int off) -> int {
@@ -2797,14 +2768,12 @@ struct Engine : EngineBase {
     }
     HIPCHK(hipStreamSynchronize(stream));
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
     vt_last_ms = ms;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     pv_last_ms = 0;
-    if (p0) {
-      HIPCHK(hipEventElapsedTime(&ms, p0, p1));
+    if (!m->pvh) {
+      HIPCHK(hipEventElapsedTime(&ms, pev[0], pev[1]));
       pv_last_ms = ms;
-      (void)hipEventDestroy(p0); (void)hipEventDestroy(p1);
     }
     pvh_on_device[nest] = true;
     // without sfc the slot's 2-D fields are still those of the previous wind field until fpx_calcpar has run: not loaded
@@ -2870,12 +2839,12 @@ struct Engine : EngineBase {
     A.surfstr = d_str; A.sshf = d_shf; A.excessoro = d_exc; A.akm = d_akm; A.bkm = d_bkm; A.lsubgrid = c->lsubgrid;
     A.zlev = D(RHOH);                          // scratch of the transform, free between calls
     A.ustar = d_ust; A.wstar = d_wst; A.oli = d_oli; A.hmix = d_hmix; A.tropopause = d_trop;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, stream));
+    Events<2> ev;
+    HIPCHK(ev.create());
+    HIPCHK(hipEventRecord(ev[0], stream));
     cp::k_calcpar<H><<<(cfg.nx * cfg.ny + 255) / 256, 256, 0, stream>>>(A);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
+    HIPCHK(hipEventRecord(ev[1], stream));
     // into the gather packs, as upload_fields does from the host's arrays
     auto pk2 = [&](const H *in, const R *outp, int stride, int off) -> int {
       const int tot = cfg.nx * cfg.ny;
@@ -2901,9 +2870,8 @@ struct Engine : EngineBase {
     }
     HIPCHK(hipStreamSynchronize(stream));
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
     cp_last_ms = ms;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     cp_slot_on_device = slot;                  // whose ustar, oli the buffer holds (fpx_getvdep)
     // device_vdep with DRYDEP: the slot's vdep is still the previous wind field's until fpx_getvdep has run: not loaded
     vdep_pending[s] = V.vdep && !c->vdep;
@@ -3061,12 +3029,12 @@ struct Engine : EngineBase {
     A.lseason = gv_season;
     H *d_vdep = B + 9 * n2;
     A.vdep = d_vdep;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, stream));
+    Events<2> ev;
+    HIPCHK(ev.create());
+    HIPCHK(hipEventRecord(ev[0], stream));
     gv::k_getvdep<H><<<(cfg.nx * cfg.ny + 255) / 256, 256, (size_t)gv_lay.total() * sizeof(H), stream>>>(A);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream));
+    HIPCHK(hipEventRecord(ev[1], stream));
     // into the gather pack, as upload_fields does from the host's vdep(0,0,1,n) planes
     const int tot = cfg.nx * cfg.ny;
     for (int ks = 0; ks < nspec; ks++) {
@@ -3076,9 +3044,8 @@ struct Engine : EngineBase {
     if (vdep_out) HIPCHK(hipMemcpyAsync(vdep_out, d_vdep, n2 * nspec * sizeof(H), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
     gv_last_ms = ms;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (vdep_pending[s]) { vdep_pending[s] = false; slot_loaded[s] = true; }   // fpx_calcpar(device_vdep = 1) was waiting for this
     return 0;
   }
@@ -3199,17 +3166,10 @@ struct Engine : EngineBase {
     const long long n = numpart;
     const int reclen = 8 + (10 + cfg.nspec) * (int)sizeof(H);
     const size_t recwords = (size_t)reclen / 4 + 2;
-    unsigned int *flags = nullptr, *idx = nullptr, *out = nullptr;
-    void *tmp = nullptr;
+    Scratch b_flags, b_idx, b_out, b_tmp;
     FILE *fh = fopen(path, "wb");
     if (!fh) return fail(FPX_ERR_ARG, std::string("partoutput: cannot open ") + path);
-    auto cleanup = [&]() {
-      if (flags) (void)hipFree(flags);
-      if (idx) (void)hipFree(idx);
-      if (out) (void)hipFree(out);
-      if (tmp) (void)hipFree(tmp);
-      if (fh) fclose(fh);
-    };
+    FileCloser closer(fh);
     unsigned int count = 0;
     bool io_ok = true;
     {
@@ -3218,49 +3178,47 @@ struct Engine : EngineBase {
     }
     if (n > 0) {
       hipError_t e;
-      if ((e = hipMalloc(&flags, n * sizeof(unsigned int))) != hipSuccess || (e = hipMalloc(&idx, n * sizeof(unsigned int))) != hipSuccess) {
-        cleanup();
+      if ((e = b_flags.reserve(n * sizeof(unsigned int), stream)) != hipSuccess || (e = b_idx.reserve(n * sizeof(unsigned int), stream)) != hipSuccess)
         return fail(FPX_ERR_NOMEM, std::string("partoutput: ") + hipGetErrorString(e));
-      }
+      unsigned int *flags = b_flags.as<unsigned int>(), *idx = b_idx.as<unsigned int>();
       const int nb = (int)((n + kBlock - 1) / kBlock);
-      hipEvent_t e0, e1;
-      (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-      (void)hipEventRecord(e0, stream);
+      Events<2> ev;
+      (void)ev.create();
+      (void)hipEventRecord(ev[0], stream);
       k_po_flags<R><<<nb, kBlock, 0, stream>>>(P, n, itime, flags);
       size_t tb = 0;
       (void)rocprim::exclusive_scan(nullptr, tb, flags, idx, 0u, (size_t)n, rocprim::plus<unsigned int>(), stream);
-      if ((e = hipMalloc(&tmp, std::max<size_t>(tb, 16))) != hipSuccess) { cleanup(); return fail(FPX_ERR_NOMEM, "partoutput: scan storage"); }
-      e = rocprim::exclusive_scan(tmp, tb, flags, idx, 0u, (size_t)n, rocprim::plus<unsigned int>(), stream);
+      if ((e = b_tmp.reserve(tb, stream)) != hipSuccess) return fail(FPX_ERR_NOMEM, "partoutput: scan storage");
+      e = rocprim::exclusive_scan(b_tmp.as(), tb, flags, idx, 0u, (size_t)n, rocprim::plus<unsigned int>(), stream);
       unsigned int last_idx = 0, last_flag = 0;
       if (e == hipSuccess) e = hipMemcpyAsync(&last_idx, idx + (n - 1), 4, hipMemcpyDeviceToHost, stream);
       if (e == hipSuccess) e = hipMemcpyAsync(&last_flag, flags + (n - 1), 4, hipMemcpyDeviceToHost, stream);
       if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_DEVICE, std::string("partoutput: ") + hipGetErrorString(e)); }
+      if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("partoutput: ") + hipGetErrorString(e));
       count = last_idx + last_flag;
-      struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
       if (count > 0) {
         const size_t words = (size_t)count * recwords;
-        if ((e = hipMalloc(&out, words * 4)) != hipSuccess) { cleanup(); return fail(FPX_ERR_NOMEM, std::string("partoutput: record buffer: ") + hipGetErrorString(e)); }
+        if ((e = b_out.reserve(words * 4, stream)) != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("partoutput: record buffer: ") + hipGetErrorString(e));
+        unsigned int *out = b_out.as<unsigned int>();
         const DiagP<H> D = diag_args<H>();
         k_partoutput<R, H><<<nb, kBlock, 0, stream>>>(V, P, D, idx, n, itime, out);
         e = hipGetLastError();
-        (void)hipEventRecord(e1, stream);
-        if (e == hipSuccess && hipEventSynchronize(e1) == hipSuccess) {
+        (void)hipEventRecord(ev[1], stream);
+        if (e == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess) {
           float ms = 0;
-          if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) po_last_ms = ms;
+          if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) po_last_ms = ms;
         }
         // stream the record bytes to the file through two pinned bounce buffers: the copy of chunk k+1 runs while
         // chunk k is written (the call is bound by the host's write, about 4 GB/s into tmpfs)
         const size_t chunk = (size_t)64 << 20, total = words * 4;
-        void *pin = nullptr;
-        hipEvent_t done[2] = {nullptr, nullptr};
-        if (e == hipSuccess) e = hipHostMalloc(&pin, 2 * std::min(chunk, total));
-        if (e == hipSuccess) e = hipEventCreate(&done[0]);
-        if (e == hipSuccess) e = hipEventCreate(&done[1]);
+        Scratch pin(true);
+        Events<2> done;
+        if (e == hipSuccess) e = pin.reserve(2 * std::min(chunk, total), stream);
+        if (e == hipSuccess) e = done.create();
         const size_t bufsz = std::min(chunk, total);
         auto issue = [&](size_t k) -> hipError_t {
           const size_t off = k * chunk, nbytes = std::min(chunk, total - off);
-          hipError_t r = hipMemcpyAsync((char *)pin + (k & 1) * bufsz, (const char *)out + off, nbytes, hipMemcpyDeviceToHost, stream);
+          hipError_t r = hipMemcpyAsync(pin.as<char>() + (k & 1) * bufsz, (const char *)out + off, nbytes, hipMemcpyDeviceToHost, stream);
           return r == hipSuccess ? hipEventRecord(done[k & 1], stream) : r;
         };
         const size_t nchunks = (total + chunk - 1) / chunk;
@@ -3269,12 +3227,10 @@ struct Engine : EngineBase {
           e = hipEventSynchronize(done[k & 1]);
           if (e == hipSuccess && k + 1 < nchunks) e = issue(k + 1);
           const size_t nbytes = std::min(chunk, total - k * chunk);
-          if (e == hipSuccess) io_ok = fwrite((const char *)pin + (k & 1) * bufsz, 1, nbytes, fh) == nbytes;
+          if (e == hipSuccess) io_ok = fwrite(pin.as<char>() + (k & 1) * bufsz, 1, nbytes, fh) == nbytes;
         }
         if (e == hipSuccess) e = hipStreamSynchronize(stream); else (void)hipStreamSynchronize(stream);
-        for (int i = 0; i < 2; i++) if (done[i]) (void)hipEventDestroy(done[i]);
-        if (pin) (void)hipHostFree(pin);
-        if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_DEVICE, std::string("partoutput: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("partoutput: ") + hipGetErrorString(e));
       }
     }
     {   // the closing record, partoutput.f90:182-184
@@ -3290,9 +3246,7 @@ struct Engine : EngineBase {
       memcpy(p, &rl, 4);
       io_ok = io_ok && fwrite(rec.data(), 1, rec.size(), fh) == rec.size();
     }
-    io_ok = (fclose(fh) == 0) && io_ok;
-    fh = nullptr;
-    cleanup();
+    io_ok = (closer.close() == 0) && io_ok;
     if (!io_ok) return fail(FPX_ERR_ARG, std::string("partoutput: write error on ") + path);
     if (nrec) *nrec = count;
     return 0;
@@ -3339,7 +3293,7 @@ struct Engine : EngineBase {
   int readpart_t(const char *path, const fpx_restart *r, int64_t *numpart_out, int32_t *numparticlecount, int32_t *itimein_out) {
     FILE *fh = fopen(path, "rb");
     if (!fh) return fail(FPX_ERR_ARG, std::string("readpartpositions: cannot open ") + path);
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fh};
+    FileCloser closer(fh);
     if (fseek(fh, 0, SEEK_END) != 0) return fail(FPX_ERR_ARG, "readpartpositions: seek");
     const long long size = ftell(fh);
     rewind(fh);
@@ -3363,46 +3317,39 @@ struct Engine : EngineBase {
     // readpartpositions.f90:133-134: the previous run must end where this one starts
     if (std::abs(r->jul_header + (double)itimein / 86400. - r->bdate) > 1.e-5)
       return fail(FPX_ERR_ARG, "readpartpositions: ending time of the previous run does not agree with the start of this run");
-    int *d_status = nullptr, *d_nclass = nullptr;
-    unsigned int *raw = nullptr;
-    void *pin = nullptr;
-    auto cleanup = [&]() {
-      if (d_status) (void)hipFree(d_status);
-      if (d_nclass) (void)hipFree(d_nclass);
-      if (raw) (void)hipFree(raw);
-      if (pin) (void)hipHostFree(pin);
-    };
-    hipError_t e = hipMalloc(&d_status, 2 * sizeof(int));
+    Scratch b_status, b_nclass, b_raw, pin(true);
+    hipError_t e = b_status.reserve(2 * sizeof(int), stream);
+    int *d_status = b_status.as<int>();
     if (e == hipSuccess) e = hipMemsetAsync(d_status, 0, 2 * sizeof(int), stream);
     int status[2] = {0, 0};
     if (n > 0 && e == hipSuccess) {
       const size_t bytes = (size_t)(n + 1) * recbytes;
-      e = hipMalloc(&raw, bytes);
+      e = b_raw.reserve(bytes, stream);
+      unsigned int *raw = b_raw.as<unsigned int>();
       const size_t chunk = (size_t)64 << 20;
-      if (e == hipSuccess) e = hipHostMalloc(&pin, std::min(chunk, bytes));
+      if (e == hipSuccess) e = pin.reserve(std::min(chunk, bytes), stream);
       for (size_t off = 0; e == hipSuccess && off < bytes; off += chunk) {
         const size_t nb = std::min(chunk, bytes - off);
-        if (fread(pin, 1, nb, fh) != nb) { cleanup(); return fail(FPX_ERR_ARG, "readpartpositions: short read"); }
-        e = hipMemcpyAsync((char *)raw + off, pin, nb, hipMemcpyHostToDevice, stream);
+        if (fread(pin.as(), 1, nb, fh) != nb) return fail(FPX_ERR_ARG, "readpartpositions: short read");
+        e = hipMemcpyAsync((char *)raw + off, pin.as(), nb, hipMemcpyHostToDevice, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
       }
       if (e == hipSuccess && r->nclassunc > 1) {      // nclass(i)=min(int(ran1(idummy)*real(nclassunc))+1,nclassunc), :142-143
         std::vector<int> nc((size_t)n);
         Ran1 g;
         for (long long i = 0; i < n; i++) nc[i] = std::min((int)(g.template next<H>() * (H)r->nclassunc) + 1, r->nclassunc);
-        e = hipMalloc(&d_nclass, (size_t)n * sizeof(int));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_nclass, nc.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream);
+        e = b_nclass.reserve((size_t)n * sizeof(int), stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(b_nclass.as(), nc.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
       }
       if (e == hipSuccess) {
         k_readpart<R, H><<<(int)((n + kBlock - 1) / kBlock), kBlock, 0, stream>>>(P, raw, n, cfg.nspec, (H)cfg.dx, (H)cfg.dy, (H)cfg.xlon0, (H)cfg.ylat0,
-                                                                                r->jul_header, r->bdate, r->mintime, r->itrasplit, d_nclass, d_status);
+                                                                                r->jul_header, r->bdate, r->mintime, r->itrasplit, b_nclass.as<int>(), d_status);
         e = hipGetLastError();
       }
       if (e == hipSuccess) e = hipMemcpyAsync(status, d_status, sizeof status, hipMemcpyDeviceToHost, stream);
       if (e == hipSuccess) e = hipStreamSynchronize(stream);
     }
-    cleanup();
     if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("readpartpositions: ") + hipGetErrorString(e));
     if (status[0] != 0) return fail(FPX_ERR_ARG, status[0] == 1 ? "readpartpositions: record markers do not match this build's record length"
                                                   : "readpartpositions: the file does not hold exactly one dump (header, records, closing record)");
@@ -3578,9 +3525,8 @@ struct Engine : EngineBase {
     numpart = *numpart_io;
     // ---- the k-th particle takes the k-th vacant storage space in particle-number order (:133-137) --------
     const long long cap = P.cap;
-    std::vector<void *> mine;
-    auto cleanup = [&]() { for (void *q : mine) (void)hipFree(q); };
-    auto mal = [&](auto **q, size_t n) -> hipError_t { hipError_t e = hipMalloc((void **)q, std::max<size_t>(n, 1) * sizeof(**q)); if (e == hipSuccess) mine.push_back(*q); return e; };
+    std::vector<Scratch> mine;       // this call's buffers
+    auto mal = [&](auto **q, size_t n) -> hipError_t { mine.emplace_back(); const hipError_t e = mine.back().reserve(n * sizeof(**q), stream); *q = (decltype(*q + 0))mine.back().as(); return e; };
     unsigned int *flags = nullptr, *rank = nullptr, *target = nullptr, *d_max = nullptr;
     long long *d_first = nullptr, *d_gfirst = nullptr;
     H *d_pts = nullptr, *d_mass = nullptr, *d_uni = nullptr, *d_rho = nullptr;
@@ -3605,7 +3551,7 @@ struct Engine : EngineBase {
       (void)rocprim::exclusive_scan(nullptr, tb, flags, rank, 0u, (size_t)scan_n, rocprim::plus<unsigned int>(), stream);
       e = rel_scan_tmp(tb, &tmp) ? hipErrorOutOfMemory : hipSuccess;
     }
-    if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_NOMEM, std::string("releaseparticles: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("releaseparticles: ") + hipGetErrorString(e));
     const int nbc = (int)((scan_n + kBlock - 1) / kBlock);
     k_rel_flags<R><<<nbc, kBlock, 0, stream>>>(P, slot_map(), scan_n, itime, flags);
     e = rocprim::exclusive_scan(tmp, tb, flags, rank, 0u, (size_t)scan_n, rocprim::plus<unsigned int>(), stream);
@@ -3613,11 +3559,9 @@ struct Engine : EngineBase {
     if (e == hipSuccess) e = hipMemcpyAsync(&last[0], rank + (scan_n - 1), 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&last[1], flags + (scan_n - 1), 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_DEVICE, std::string("releaseparticles: ") + hipGetErrorString(e)); }
-    if ((long long)last[0] + last[1] < ntotal) {
-      cleanup();
+    if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("releaseparticles: ") + hipGetErrorString(e));
+    if ((long long)last[0] + last[1] < ntotal)
       return fail(FPX_ERR_NOMEM, "releaseparticles: total number of particles required exceeds the maximum allowed number (releaseparticles.f90:369-378)");
-    }
     k_rel_targets<<<nbc, kBlock, 0, stream>>>(flags, rank, scan_n, ntotal, target);
     // ---- the four uniforms of every particle: serial ran1 stream (x, y, class, z per particle) or counter RNG ----
     std::vector<H> uni;
@@ -3639,7 +3583,7 @@ struct Engine : EngineBase {
     if (e == hipSuccess) e = hipMemcpyAsync(d_kindz, rel.kindz.data(), np * sizeof(short), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_rho, rho_h.data(), np * sizeof(H), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_max, 0, 4, stream);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(stream); cleanup(); return fail(FPX_ERR_DEVICE, std::string("releaseparticles: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(FPX_ERR_DEVICE, std::string("releaseparticles: ") + hipGetErrorString(e)); }
     RelPoints<H> RP{d_first, d_gfirst, d_pts, d_pts + np, d_pts + 2 * np, d_pts + 3 * np, d_pts + 4 * np, d_pts + 5 * np, d_mass, d_kindz, np};
     DiagP<H> D;
     D.oro = (const H *)diag_oro; D.tropo[0] = (const H *)diag_tropo[0]; D.tropo[1] = (const H *)diag_tropo[1]; D.d3 = (const H *)diag_d3;
@@ -3661,7 +3605,6 @@ struct Engine : EngineBase {
     if (e == hipSuccess) e = hipMemcpyAsync(&maxpid, d_max, 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess && rho_rel && dens) e = hipMemcpyAsync(rho_h.data(), d_rho, np * sizeof(H), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream); else (void)hipStreamSynchronize(stream);
-    cleanup();
     if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("releaseparticles: ") + hipGetErrorString(e));
     if (rho_rel && dens) for (int i = 0; i < np; i++) rho_rel[i] = rho_h[i];
     numpart = std::max<long long>(numpart, (long long)maxpid + 1);          // :362
@@ -3673,33 +3616,15 @@ struct Engine : EngineBase {
     return 0;
   }
   // grow-only scratch of fpx_releaseparticles / fpx_split_particles: two unsigned arrays of n elements and the scan's temporary
-  unsigned int *rel_flags_buf = nullptr, *rel_rank_buf = nullptr;
-  size_t rel_buf_n = 0;
-  void *rel_tmp_buf = nullptr;
-  size_t rel_tmp_bytes = 0;
+  Scratch rel_flags_buf, rel_rank_buf, rel_tmp_buf;
   int rel_scratch(size_t n, unsigned int **flags, unsigned int **rank) {
-    if (n > rel_buf_n) {
-      (void)hipStreamSynchronize(stream);
-      if (rel_flags_buf) (void)hipFree(rel_flags_buf);
-      if (rel_rank_buf) (void)hipFree(rel_rank_buf);
-      rel_flags_buf = rel_rank_buf = nullptr; rel_buf_n = 0;
-      if (hipMalloc(&rel_flags_buf, n * 4) != hipSuccess) return 1;
-      if (hipMalloc(&rel_rank_buf, n * 4) != hipSuccess) { (void)hipFree(rel_flags_buf); rel_flags_buf = nullptr; return 1; }
-      rel_buf_n = n;
-    }
-    *flags = rel_flags_buf; *rank = rel_rank_buf;
+    if (rel_flags_buf.reserve(n * 4, stream) != hipSuccess || rel_rank_buf.reserve(n * 4, stream) != hipSuccess) return 1;
+    *flags = rel_flags_buf.as<unsigned int>(); *rank = rel_rank_buf.as<unsigned int>();
     return 0;
   }
   int rel_scan_tmp(size_t bytes, void **tmp) {
-    bytes = std::max<size_t>(bytes, 16);
-    if (bytes > rel_tmp_bytes) {
-      (void)hipStreamSynchronize(stream);
-      if (rel_tmp_buf) (void)hipFree(rel_tmp_buf);
-      rel_tmp_buf = nullptr; rel_tmp_bytes = 0;
-      if (hipMalloc(&rel_tmp_buf, bytes) != hipSuccess) return 1;
-      rel_tmp_bytes = bytes;
-    }
-    *tmp = rel_tmp_buf;
+    if (rel_tmp_buf.reserve(bytes, stream) != hipSuccess) return 1;
+    *tmp = rel_tmp_buf.as();
     return 0;
   }
   int releaseparticles(int itime, int64_t *numpart_io, int32_t *npc_io, void *xmasssave, void *rho_rel, int64_t *nreleased) override {
@@ -3717,14 +3642,13 @@ struct Engine : EngineBase {
     const long long n = numpart, room = P.cap - n;
     unsigned int *flags = nullptr, *rank = nullptr;
     void *tmp = nullptr;
-    auto cleanup = [&]() {};      // the work arrays are the engine's grow-only scratch (rel_scratch)
     hipError_t e = rel_scratch((size_t)n, &flags, &rank) ? hipErrorOutOfMemory : hipSuccess;
     size_t tb = 0;
     if (e == hipSuccess) {
       (void)rocprim::exclusive_scan(nullptr, tb, flags, rank, 0u, (size_t)n, rocprim::plus<unsigned int>(), stream);
       e = rel_scan_tmp(tb, &tmp) ? hipErrorOutOfMemory : hipSuccess;
     }
-    if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_NOMEM, std::string("split_particles: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("split_particles: ") + hipGetErrorString(e));
     const int nb = (int)((n + kBlock - 1) / kBlock);
     k_split_flags<R><<<nb, kBlock, 0, stream>>>(P, slot_map(), n, itime, cfg.ldirect, flags);
     e = rocprim::exclusive_scan(tmp, tb, flags, rank, 0u, (size_t)n, rocprim::plus<unsigned int>(), stream);
@@ -3737,7 +3661,6 @@ struct Engine : EngineBase {
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream); else (void)hipStreamSynchronize(stream);
-    cleanup();
     if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("split_particles: ") + hipGetErrorString(e));
     numpart = n + std::min<long long>((long long)last[0] + last[1], room);
     *numpart_io = numpart;
@@ -3747,15 +3670,7 @@ struct Engine : EngineBase {
   // ---- particle redistribution between ranks, mpi_mod.f90:661-856 ------------------------------
   // The host keeps the transport (its MPI_Send / MPI_Recv, one message instead of the reference's 9 + nspec); the engine
   // packs and places.  buf may be host or device memory (hipMemcpyDefault).
-  void *redist_dev = nullptr;
-  size_t redist_dev_bytes = 0;
-  int redist_stage(size_t bytes) {
-    if (bytes <= redist_dev_bytes) return 0;
-    if (redist_dev) { (void)hipStreamSynchronize(stream); (void)hipFree(redist_dev); redist_dev = nullptr; redist_dev_bytes = 0; }
-    if (hipMalloc(&redist_dev, bytes) != hipSuccess) return -1;
-    redist_dev_bytes = bytes;
-    return 0;
-  }
+  Scratch redist_dev;
   size_t redist_bytes(int64_t num_trans) override { return num_trans > 0 ? RedistBuf<R>::bytes(num_trans, cfg.nspec) : 0; }
   int redist_pack(int itime, int64_t num_trans, void *buf, size_t buf_bytes, int64_t *numpart_io) override {
     (void)itime;
@@ -3764,16 +3679,16 @@ struct Engine : EngineBase {
     if (num_trans == 0) return 0;
     const size_t need = redist_bytes(num_trans);
     if (!buf || buf_bytes < need) return fail(FPX_ERR_ARG, "redist_pack: buffer smaller than fpx_redist_bytes(num_trans)");
-    if (redist_stage(need)) return fail(FPX_ERR_NOMEM, "redist_pack: staging buffer");
+    if (redist_dev.reserve(need, stream) != hipSuccess) return fail(FPX_ERR_NOMEM, "redist_pack: staging buffer");
     // first back into particle-number order over the extent the engine itself holds (the extent of the last locality sort:
     // its slots are a permutation of exactly those numbers), then the host's count -- as set_numpart does; the other order
     // would sort a range whose numbers are not a permutation and lose live particles
     { const int rc = restore_particle_order(); if (rc) return rc; }   // numpart shrinks below
     numpart = *numpart_io;
-    const RedistBuf<R> B = RedistBuf<R>::at(redist_dev, num_trans, cfg.nspec);
+    const RedistBuf<R> B = RedistBuf<R>::at(redist_dev.as(), num_trans, cfg.nspec);
     k_redist_pack<R><<<(int)((num_trans + kBlock - 1) / kBlock), kBlock, 0, stream>>>(P, slot_map(), numpart - num_trans, B, cfg.nspec);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(buf, redist_dev, need, hipMemcpyDefault, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(buf, redist_dev.as(), need, hipMemcpyDefault, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream); else (void)hipStreamSynchronize(stream);
     if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("redist_pack: ") + hipGetErrorString(e));
     numpart -= num_trans;                                 // :746
@@ -3792,7 +3707,7 @@ struct Engine : EngineBase {
     unsigned int *flags = nullptr, *rank = nullptr;
     void *tmp = nullptr;
     const size_t nwork = (size_t)maxnumpart + 3 * (size_t)num_trans + 1;
-    if (redist_stage(need)) return fail(FPX_ERR_NOMEM, "redist_unpack: staging buffer");
+    if (redist_dev.reserve(need, stream) != hipSuccess) return fail(FPX_ERR_NOMEM, "redist_unpack: staging buffer");
     if (rel_scratch(nwork, &flags, &rank)) return fail(FPX_ERR_NOMEM, "redist_unpack: work arrays");
     unsigned int *valid = flags + maxnumpart, *vrank = rank + maxnumpart;
     unsigned int *target = flags + maxnumpart + num_trans, *d_max = rank + maxnumpart + num_trans;
@@ -3801,8 +3716,8 @@ struct Engine : EngineBase {
     (void)rocprim::exclusive_scan(nullptr, tb2, valid, vrank, 0u, (size_t)num_trans, rocprim::plus<unsigned int>(), stream);
     if (rel_scan_tmp(std::max(tb1, tb2), &tmp)) return fail(FPX_ERR_NOMEM, "redist_unpack: scan storage");
     numpart = *numpart_io;
-    hipError_t e = hipMemcpyAsync(redist_dev, buf, need, hipMemcpyDefault, stream);
-    const RedistBuf<R> B = RedistBuf<R>::at(redist_dev, num_trans, cfg.nspec);
+    hipError_t e = hipMemcpyAsync(redist_dev.as(), buf, need, hipMemcpyDefault, stream);
+    const RedistBuf<R> B = RedistBuf<R>::at(redist_dev.as(), num_trans, cfg.nspec);
     const int nbm = (int)((maxnumpart + kBlock - 1) / kBlock), nbt = (int)((num_trans + kBlock - 1) / kBlock);
     if (e == hipSuccess) {
       k_rel_flags<R><<<nbm, kBlock, 0, stream>>>(P, slot_map(), maxnumpart, itime, flags);          // vacant: itra1 /= itime (:818)
@@ -3862,10 +3777,9 @@ struct Engine : EngineBase {
     float *d_area = nullptr, *d_vol = nullptr, *val = nullptr, *wr = nullptr;
     unsigned int *nz = nullptr, *rs = nullptr, *rpos = nullptr, *runid = nullptr;
     int *wi = nullptr;
-    void *tmp = nullptr;
-    std::vector<void *> mine;
-    auto cleanup = [&]() { for (void *q : mine) (void)hipFree(q); if (tmp) (void)hipFree(tmp); };
-    auto mal = [&](auto **q, size_t bytes) -> hipError_t { hipError_t e = hipMalloc((void **)q, bytes); if (e == hipSuccess) mine.push_back(*q); return e; };
+    Scratch tmp;
+    std::vector<Scratch> mine;       // this call's buffers
+    auto mal = [&](auto **q, size_t bytes) -> hipError_t { mine.emplace_back(); const hipError_t e = mine.back().reserve(bytes, stream); *q = (decltype(*q + 0))mine.back().as(); return e; };
     float *d_dens = nullptr, *d_outh = nullptr;
     hipError_t e = mal(&d_area, n2 * 4);
     if (e == hipSuccess) e = mal(&d_vol, n3 * 4);
@@ -3884,7 +3798,7 @@ struct Engine : EngineBase {
       size_t tb2 = 0;
       (void)rocprim::inclusive_scan(nullptr, tb2, rs, runid, (size_t)n3, rocprim::plus<unsigned int>(), stream);
       tb = std::max(tb, tb2);
-      e = hipMalloc(&tmp, std::max<size_t>(tb, 16));
+      e = tmp.reserve(tb, stream);
     }
     if (e == hipSuccess) e = hipMemcpyAsync(d_area, c->area, n2 * 4, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_vol, c->volume, n3 * 4, hipMemcpyHostToDevice, stream);
@@ -3897,7 +3811,7 @@ struct Engine : EngineBase {
         e = hipGetLastError();
       }
     }
-    if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_NOMEM, std::string("concoutput: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("concoutput: ") + hipGetErrorString(e));
     std::vector<int> h_wi((size_t)n3);
     std::vector<float> h_wr((size_t)n3);
     // one compressed dump: device work, then the four records (count, indices, count, values)
@@ -3907,9 +3821,9 @@ struct Engine : EngineBase {
       if (grid) {
         k_co_values<<<nb, kBlock, 0, stream>>>(grid, class_stride, Gp.nclassunc, n, val, nz, rs);
         size_t t1 = tb;
-        hipError_t e2 = rocprim::exclusive_scan(tmp, t1, nz, rpos, 0u, (size_t)n, rocprim::plus<unsigned int>(), stream);
+        hipError_t e2 = rocprim::exclusive_scan(tmp.as(), t1, nz, rpos, 0u, (size_t)n, rocprim::plus<unsigned int>(), stream);
         t1 = tb;
-        if (e2 == hipSuccess) e2 = rocprim::inclusive_scan(tmp, t1, rs, runid, (size_t)n, rocprim::plus<unsigned int>(), stream);
+        if (e2 == hipSuccess) e2 = rocprim::inclusive_scan(tmp.as(), t1, rs, runid, (size_t)n, rocprim::plus<unsigned int>(), stream);
         k_co_write<<<nb, kBlock, 0, stream>>>(val, nz, rs, rpos, runid, n, scale, conc, (float)c->outnum, 1.f, idx0, wi, wr, d_dens, wm);
         unsigned int last[3] = {0, 0, 0};
         if (e2 == hipSuccess) e2 = hipMemcpyAsync(&last[0], rpos + (n - 1), 4, hipMemcpyDeviceToHost, stream);
@@ -3952,7 +3866,6 @@ struct Engine : EngineBase {
           }
         if (fclose(fh) != 0 && !rc) rc = fail(FPX_ERR_ARG, "concoutput: write error");
       }
-    cleanup();
     if (rc) return rc;
     if (clear) {   // gridunc(:,:,:,:,:,:,:)=0., concoutput.f90:714 / griduncn, concoutput_nest.f90 (the deposition grids keep accumulating)
       HIPCHK(hipMemsetAsync(g3, 0, (c->nest ? n_grid3n : n_grid3) * sizeof(R), stream));
@@ -4009,21 +3922,19 @@ struct Engine : EngineBase {
   // ---- particles -----------------------------------------------------------
   template <typename H, typename D>
   int put(const H *host, D *dev, long long first, long long count) {
-    int rc = ensure_staging((size_t)count * sizeof(H));
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(staging, host, (size_t)count * sizeof(H), hipMemcpyHostToDevice, stream));
-    k_scatter_in<H, D><<<(int)((count + kBlock - 1) / kBlock), kBlock, 0, stream>>>((const H *)staging, dev, slot_map(), first, count);
+    HIPCHK(staging.reserve((size_t)count * sizeof(H), stream));
+    HIPCHK(hipMemcpyAsync(staging.as(), host, (size_t)count * sizeof(H), hipMemcpyHostToDevice, stream));
+    k_scatter_in<H, D><<<(int)((count + kBlock - 1) / kBlock), kBlock, 0, stream>>>(staging.as<const H>(), dev, slot_map(), first, count);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(stream));
     return 0;
   }
   template <typename H, typename D>
   int get(H *host, const D *dev, long long first, long long count) {
-    int rc = ensure_staging((size_t)count * sizeof(H));
-    if (rc) return rc;
-    k_gather_out<D, H><<<(int)((count + kBlock - 1) / kBlock), kBlock, 0, stream>>>(dev, (H *)staging, slot_map(), first, count);
+    HIPCHK(staging.reserve((size_t)count * sizeof(H), stream));
+    k_gather_out<D, H><<<(int)((count + kBlock - 1) / kBlock), kBlock, 0, stream>>>(dev, staging.as<H>(), slot_map(), first, count);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host, staging, (size_t)count * sizeof(H), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(host, staging.as(), (size_t)count * sizeof(H), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     return 0;
   }
@@ -4147,8 +4058,7 @@ struct Engine : EngineBase {
   unsigned int *conv_flag = nullptr, *conv_rank = nullptr;
   unsigned char *conv_draws = nullptr;
   void *conv_rn = nullptr;
-  void *conv_scr = nullptr, *conv_scan_tmp = nullptr;
-  size_t conv_scr_bytes = 0, conv_scan_bytes = 0;
+  Scratch conv_scr, conv_scan_tmp;
   unsigned long long *conv_nmoved = nullptr;
   double conv_last_ms = 0;
   double conv_ms() override { return conv_last_ms; }
@@ -4300,8 +4210,7 @@ struct Engine : EngineBase {
     HIPCHK(hipStreamSynchronize(stream));
     return 0;
   }
-  unsigned int *conv_alive = nullptr;
-  size_t conv_alive_cap = 0;
+  Scratch conv_alive;
   int conv_last_active = 0, conv_last_survivors = 0;
 
   template <typename H>
@@ -4346,22 +4255,17 @@ struct Engine : EngineBase {
       conv_ncol_alloc = (size_t)ncol;
     }
     const int nb = (int)((n + kBlock - 1) / kBlock), nbc = (ncol + kBlock - 1) / kBlock;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
-    HIPCHK(hipEventRecord(e0, stream));
+    Events<2> ev;
+    HIPCHK(ev.create());
+    HIPCHK(hipEventRecord(ev[0], stream));
     HIPCHK(hipMemsetAsync(conv_flag, 0, (size_t)ncol * sizeof(unsigned int), stream));
     HIPCHK(hipMemsetAsync(conv_nmoved, 0, sizeof(unsigned long long), stream));
     conv::k_conv_mark<R, H><<<nb, kBlock, 0, stream>>>(F, P.xt, P.yt, P.itra1, n, itime, conv_pcol, conv_flag);
     HIPCHK(hipGetLastError());
     size_t tb = 0;
     HIPCHK(rocprim::exclusive_scan(nullptr, tb, conv_flag, conv_rank, 0u, (size_t)ncol, rocprim::plus<unsigned int>(), stream));
-    if (tb > conv_scan_bytes) {
-      if (conv_scan_tmp) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(conv_scan_tmp)); conv_scan_tmp = nullptr; }
-      HIPCHK(hipMalloc(&conv_scan_tmp, std::max<size_t>(tb, 16)));
-      conv_scan_bytes = std::max<size_t>(tb, 16);
-    }
-    HIPCHK(rocprim::exclusive_scan(conv_scan_tmp, tb, conv_flag, conv_rank, 0u, (size_t)ncol, rocprim::plus<unsigned int>(), stream));
+    HIPCHK(conv_scan_tmp.reserve(tb, stream));
+    HIPCHK(rocprim::exclusive_scan(conv_scan_tmp.as(), tb, conv_flag, conv_rank, 0u, (size_t)ncol, rocprim::plus<unsigned int>(), stream));
     unsigned int last_rank = 0, last_flag = 0;
     HIPCHK(hipMemcpyAsync(&last_rank, conv_rank + (ncol - 1), 4, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(&last_flag, conv_flag + (ncol - 1), 4, hipMemcpyDeviceToHost, stream));
@@ -4380,29 +4284,19 @@ struct Engine : EngineBase {
     {
       size_t free_b = 0, total_b = 0;
       HIPCHK(hipMemGetInfo(&free_b, &total_b));
-      budget = (free_b + conv_scr_bytes) / 4;
+      budget = (free_b + conv_scr.bytes()) / 4;
       if (opt.conv_scratch_mb > 0) budget = (size_t)opt.conv_scratch_mb << 20;
     }
-    if ((size_t)nact > conv_alive_cap) {
-      if (conv_alive) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(conv_alive)); conv_alive = nullptr; }
-      HIPCHK(hipMalloc(&conv_alive, (size_t)nact * 3 * sizeof(unsigned int)));
-      conv_alive_cap = (size_t)nact;
-    }
-    unsigned int *alive = conv_alive, *srank = conv_alive + nact;
-    int *surv = (int *)(conv_alive + 2 * (size_t)nact);
-    auto ensure_scratch = [&](size_t bytes) -> int {
-      if (bytes <= conv_scr_bytes) return 0;
-      if (conv_scr) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(conv_scr)); conv_scr = nullptr; conv_scr_bytes = 0; }
-      hipError_t e = hipMalloc(&conv_scr, bytes);
-      if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("convmix: scratch: ") + hipGetErrorString(e));
-      conv_scr_bytes = bytes;
-      return 0;
-    };
+    HIPCHK(conv_alive.reserve((size_t)nact * 3 * sizeof(unsigned int), stream));
+    unsigned int *alive = conv_alive.as<unsigned int>(), *srank = alive + nact;
+    int *surv = (int *)(alive + 2 * (size_t)nact);
     // upper bound of the matrix batch before the survivors are known: all active columns, capped by the budget
     int Bm_cap = (int)std::min<size_t>(conv::group_round((size_t)nact), std::max<size_t>(64, budget / per_mat / conv::kGroup * conv::kGroup));
-    int rc = ensure_scratch(vec_bytes + (size_t)Bm_cap * per_mat);
-    if (rc) return rc;
-    H *vbuf = (H *)conv_scr, *cst = vbuf + vec_elems, *mbuf = cst + cst_elems;
+    {
+      const hipError_t e = conv_scr.reserve(vec_bytes + (size_t)Bm_cap * per_mat, stream);
+      if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("convmix: scratch: ") + hipGetErrorString(e));
+    }
+    H *vbuf = conv_scr.as<H>(), *cst = vbuf + vec_elems, *mbuf = cst + cst_elems;
     const H height_nz = (H)height_host[cfg.nz - 1];
     const bool seq = cfg.rng_mode == FPX_RNG_TABLE_SEQ;
     const bool conv_one_lane = opt.conv_one_lane != 0;     // the one-lane-per-column kernel (kept as the check of the level-parallel ones)
@@ -4414,8 +4308,8 @@ struct Engine : EngineBase {
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(conv_lconv, 0, (size_t)nact * sizeof(int), stream));
     HIPCHK(hipMemsetAsync(conv_ntop, 0, (size_t)nact * sizeof(int), stream));
-    tb = conv_scan_bytes;
-    HIPCHK(rocprim::exclusive_scan(conv_scan_tmp, tb, alive, srank, 0u, (size_t)nact, rocprim::plus<unsigned int>(), stream));
+    tb = conv_scan_tmp.bytes();
+    HIPCHK(rocprim::exclusive_scan(conv_scan_tmp.as(), tb, alive, srank, 0u, (size_t)nact, rocprim::plus<unsigned int>(), stream));
     HIPCHK(hipMemcpyAsync(&last_rank, srank + (nact - 1), 4, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(&last_flag, alive + (nact - 1), 4, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -4467,12 +4361,12 @@ struct Engine : EngineBase {
         HIPCHK(hipGetLastError());
       }
     }
-    HIPCHK(hipEventRecord(e1, stream));
+    HIPCHK(hipEventRecord(ev[1], stream));
     unsigned long long moved = 0;
     HIPCHK(hipMemcpyAsync(&moved, conv_nmoved, sizeof(moved), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     float ms = 0;
-    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) conv_last_ms = ms;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) conv_last_ms = ms;
     if (nmoved_out) *nmoved_out = (int64_t)moved;
     return 0;
   }
@@ -4614,7 +4508,7 @@ struct Engine : EngineBase {
     if (!path) return fail(FPX_ERR_ARG, "checkpoint_write: path is required");
     FILE *fh = fopen(path, "wb");
     if (!fh) return fail(FPX_ERR_ARG, std::string("checkpoint_write: cannot open ") + path);
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fh};
+    FileCloser closer(fh);
     CkptHeader h;
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, "FPXCKPT1", 8);
@@ -4661,8 +4555,7 @@ struct Engine : EngineBase {
       if (fwrite(&cnt, 8, 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
       if ((rc = cfg.host_real_bytes == 4 ? ckpt_put_partavg<float>(fh, n, buf) : ckpt_put_partavg<double>(fh, n, buf))) return rc;
     }
-    closer.f = nullptr;
-    if (fclose(fh) != 0) return fail(FPX_ERR_ARG, std::string("checkpoint_write: write error on ") + path);
+    if (closer.close() != 0) return fail(FPX_ERR_ARG, std::string("checkpoint_write: write error on ") + path);
     return 0;
   }
 
@@ -4670,7 +4563,7 @@ struct Engine : EngineBase {
     if (!path) return fail(FPX_ERR_ARG, "checkpoint_read: path is required");
     FILE *fh = fopen(path, "rb");
     if (!fh) return fail(FPX_ERR_ARG, std::string("checkpoint_read: cannot open ") + path);
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fh};
+    FileCloser closer(fh);
     CkptHeader h;
     if (fread(&h, sizeof(h), 1, fh) != 1 || memcmp(h.magic, "FPXCKPT1", 8) != 0 || h.version != 2)
       return fail(FPX_ERR_ARG, "checkpoint_read: not a checkpoint of this engine (version 2)");
@@ -4909,16 +4802,8 @@ struct Engine : EngineBase {
       S.nrand_adv = d_nrand_adv; S.nrand_init = d_nrand_init;
       S.cbl_dcas = d_dcas4; S.cbl_dcas1 = d_dcas14; S.cbl_dcas_d = d_dcas8; S.cbl_dcas1_d = d_dcas18;
     }
-    if (ev_used >= 64) {   // bound the pool in long runs that never ask for the timings: fold them into the totals
-      int rc = harvest_events();
-      if (rc) return rc;
-    }
-    if (ev_used == ev_pool.size()) {
-      StepEvents se;
-      for (int i = 0; i < 5; i++) HIPCHK(hipEventCreate(&se.e[i]));
-      ev_pool.push_back(se);
-    }
-    auto &ev = ev_pool[ev_used++];
+    HIPCHK(step_timer.begin(stream));
+    const Events<5> &ev = step_timer.current();
     const int nb = (int)((numpart + kBlock - 1) / kBlock);
     // the pass budgets of the Langevin kernel's launches (time slices, k_pbl_loop); the last launch has none
     if (slice_caps.empty()) {
@@ -4949,11 +4834,7 @@ struct Engine : EngineBase {
     {
       size_t need = 0;
       HIPCHK(rocprim::radix_sort_pairs(nullptr, need, d_pbl_flag, d_pbl_flag2, d_iota, d_pbl_list, (size_t)numpart, 0u, 6u, stream));
-      if (need > sel_tmp_bytes) {
-        if (d_sel_tmp) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(d_sel_tmp)); d_sel_tmp = nullptr; }
-        HIPCHK(hipMalloc(&d_sel_tmp, need));
-        sel_tmp_bytes = need;
-      }
+      HIPCHK(d_sel_tmp.reserve(need, stream));
     }
     HIPCHK(hipMemsetAsync(d_pbl_ctr, 0, kCtrWords * sizeof(unsigned int), stream));
     // Cost buckets in the work list (k_prep): pure scheduling, no effect on any result, so the rank's own particle count
@@ -4965,7 +4846,7 @@ struct Engine : EngineBase {
     { const int rc = blend_winds(itime); if (rc) return rc; }      // its own kernel (k_blend_w3), ahead of the per-kernel events
     // device_flux: k_flux_save must follow the receptor block, and fpx_kernel_times' first interval must not hold it -- the
     // interval then opens behind both (without device_flux the order is what it always was)
-    if (!cfg.device_flux) HIPCHK(hipEventRecord(ev.e[0], stream));
+    if (!cfg.device_flux) HIPCHK(hipEventRecord(ev[0], stream));
     if (P.xscav) {   // timemanager.f90:564-598, before the particle is moved
       k_bkdep<R><<<nb, kBlock, 0, stream>>>(V, Wp, P, numpart, itime, cfg.drybkdep, cfg.wetbkdep, d_zspan);
       HIPCHK(hipGetLastError());
@@ -4973,7 +4854,7 @@ struct Engine : EngineBase {
     if (cfg.device_flux) {   // timemanager.f90:560-562 -- after the receptor block, which may zero xmass1 (:578,593)
       const int rc = cfg.host_real_bytes == 4 ? flux_launch<float>(false, itime) : flux_launch<double>(false, itime);
       if (rc) return rc;
-      HIPCHK(hipEventRecord(ev.e[0], stream));
+      HIPCHK(hipEventRecord(ev[0], stream));
     }
     {
       // specialised variants: dry deposition (aerosols), initialize() only when new particles can
@@ -4989,18 +4870,18 @@ struct Engine : EngineBase {
       f<<<nb, kBlock, (size_t)prep_pad, stream>>>(V, Gp, P, S, Q, numpart, itime, step_counter, d_stats, d_pbl_flag, d_pbl_ctr);
       maybe_new = false;
     }
-    HIPCHK(hipEventRecord(ev.e[4], stream));
+    HIPCHK(hipEventRecord(ev[4], stream));
     {
       // work list = slots stably sorted by the 6-bit key of k_prep: class, cost bucket (non-PBL slots, keys 32 and 33, end
       // up behind the d_pbl_ctr[0] entries that are used)
-      size_t need = sel_tmp_bytes;
-      HIPCHK(rocprim::radix_sort_pairs(d_sel_tmp, need, d_pbl_flag, d_pbl_flag2, d_iota, d_pbl_list, (size_t)numpart, 0u, 6u, stream));
+      size_t need = d_sel_tmp.bytes();
+      HIPCHK(rocprim::radix_sort_pairs(d_sel_tmp.as(), need, d_pbl_flag, d_pbl_flag2, d_iota, d_pbl_list, (size_t)numpart, 0u, 6u, stream));
       k_list_counts<<<1, 64, 0, stream>>>(d_pbl_flag2, numpart, d_pbl_ctr, d_stats);
     }
     // (k_pbl_finish needs every lane of its waves in the dry-deposition scatter -- wave_kernel_add: whole blocks of kBlock, no early return)
     int fin_grid = std::min(nb, 8 * 256 * 4);
     if (opt.finish_blocks > 0) fin_grid = std::min(fin_grid, opt.finish_blocks);   // tests: several tiles / strides per wave
-    HIPCHK(hipEventRecord(ev.e[1], stream));
+    HIPCHK(hipEventRecord(ev[1], stream));
     for (size_t j = 0; j < slice_caps.size(); j++) {
       // launch j works through the particles launch j-1 suspended (k_pbl_loop); a launch whose list is empty ends at once;
       // the last launch suspends nothing
@@ -5009,7 +4890,7 @@ struct Engine : EngineBase {
       loop_kernel()<<<pbl_grid, kBlock, loop_smem_bytes(), stream>>>(V, P, Q, itime, step_counter, d_stats, list, d_pbl_ctr + kCtrBase + kCtrStride * j, last ? 0 : slice_caps[j],
                                                                      last ? 0 : drain_lanes(), d_surv[j & 1]);
     }
-    HIPCHK(hipEventRecord(ev.e[2], stream));
+    HIPCHK(hipEventRecord(ev[2], stream));
     {
       const bool polar = cfg.nglobal || cfg.sglobal, nest = V.numbnests > 0;
       typedef void (*fin_fn)(View<R>, GridP<R>, Parts<R>, PblRec<R>, int, unsigned int, Stats *, const unsigned char *, long long, const unsigned int *, const unsigned int *);
@@ -5017,7 +4898,8 @@ struct Engine : EngineBase {
       f<<<fin_grid, kBlock, 0, stream>>>(V, Gp, P, Q, itime, step_counter, d_stats, d_pbl_flag, numpart,
                                          V.pbl_cost_buckets ? (const unsigned int *)nullptr : d_pbl_list, d_pbl_ctr);
     }
-    HIPCHK(hipEventRecord(ev.e[3], stream));
+    HIPCHK(hipEventRecord(ev[3], stream));
+    step_timer.commit();      // the set's last event is in the stream: from here on it counts
     HIPCHK(hipGetLastError());
     if (cfg.device_flux) {   // timemanager.f90:623
       const int rc = cfg.host_real_bytes == 4 ? flux_launch<float>(true, itime) : flux_launch<double>(true, itime);
@@ -5047,7 +4929,7 @@ struct Engine : EngineBase {
     if (out) {
       fill_stats(out, hs, snap);
       float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[3]));
+      HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[3]));
       out->kernel_ms = ms;
     }
     snap = hs;
@@ -5181,35 +5063,15 @@ struct Engine : EngineBase {
     return 0;
   }
 
-  int harvest_events() {
-    HIPCHK(hipStreamSynchronize(stream));
-    for (size_t i = 0; i < ev_used; i++) {
-      float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, ev_pool[i].e[0], ev_pool[i].e[3]));
-      acc_ms += t;
-      for (int k = 0; k < 3; k++) {
-        HIPCHK(hipEventElapsedTime(&t, ev_pool[i].e[k], ev_pool[i].e[k + 1]));
-        acc_part_ms[k] += t;
-      }
-      HIPCHK(hipEventElapsedTime(&t, ev_pool[i].e[0], ev_pool[i].e[4]));
-      acc_part_ms[3] += t;
-      acc_launches++;
-    }
-    ev_used = 0;
-    return 0;
-  }
   int kernel_time(double *ms, long long *launches, int reset, double *parts) override {
-    int rc = harvest_events();
-    if (rc) return rc;
-    if (ms) *ms = acc_ms;
-    if (launches) *launches = acc_launches;
-    if (parts) for (int k = 0; k < 4; k++) parts[k] = acc_part_ms[k];
-    if (reset) { acc_ms = 0; acc_launches = 0; acc_part_ms[0] = acc_part_ms[1] = acc_part_ms[2] = acc_part_ms[3] = 0; }
+    double t[5];
+    HIPCHK(step_timer.read(stream, t, launches, reset != 0));
+    if (ms) *ms = t[0];
+    if (parts) for (int k = 0; k < 4; k++) parts[k] = t[1 + k];
     return 0;
   }
 
-  SortRecord<R> *d_sort_rec = nullptr;
-  size_t sort_rec_cap = 0;
+  Scratch d_sort_rec;
   unsigned long long *d_disorder = nullptr;
   bool last_permute_staged = false;
   int alloc_parts(Parts<R> &Q) {
@@ -5279,12 +5141,8 @@ struct Engine : EngineBase {
     HIPCHK(hipGetLastError());
     size_t need = 0;
     HIPCHK(rocprim::radix_sort_pairs(nullptr, need, d_keys, d_keys2, d_vals, d_vals2, (size_t)n, 0u, bits, stream));
-    if (need > sort_tmp_bytes) {
-      if (d_sort_tmp) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(d_sort_tmp)); d_sort_tmp = nullptr; }
-      HIPCHK(hipMalloc(&d_sort_tmp, need));
-      sort_tmp_bytes = need;
-    }
-    HIPCHK(rocprim::radix_sort_pairs(d_sort_tmp, need, d_keys, d_keys2, d_vals, d_vals2, (size_t)n, 0u, bits, stream));
+    HIPCHK(d_sort_tmp.reserve(need, stream));
+    HIPCHK(rocprim::radix_sort_pairs(d_sort_tmp.as(), need, d_keys, d_keys2, d_vals, d_vals2, (size_t)n, 0u, bits, stream));
     // which gather: by the locality of the permutation (fpx_set_option "permute" = direct|staged overrides, for tests)
     bool staged = false;
     {
@@ -5300,16 +5158,11 @@ struct Engine : EngineBase {
     }
     last_permute_staged = staged;
     if (staged) {
-      if ((size_t)n > sort_rec_cap) {
-        if (d_sort_rec) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(d_sort_rec)); d_sort_rec = nullptr; sort_rec_cap = 0; }
-        HIPCHK(hipMalloc(&d_sort_rec, (size_t)n * sizeof(SortRecord<R>)));
-        sort_rec_cap = (size_t)n;
-      }
-      k_permute_pack<R><<<nb, kBlock, 0, stream>>>(P, d_sort_rec, n);
-      k_permute_unpack<R><<<nb, kBlock, 0, stream>>>(d_sort_rec, P, P2, d_vals2, n, cfg.nspec);
+      HIPCHK(d_sort_rec.reserve((size_t)n * sizeof(SortRecord<R>), stream));
+      k_permute_pack<R><<<nb, kBlock, 0, stream>>>(P, d_sort_rec.as<SortRecord<R>>(), n);
+      k_permute_unpack<R><<<nb, kBlock, 0, stream>>>(d_sort_rec.as<SortRecord<R>>(), P, P2, d_vals2, n, cfg.nspec);
       // 12.8 GB at 1e8 particles, needed once in a run: give it back
-      HIPCHK(hipStreamSynchronize(stream));
-      HIPCHK(hipFree(d_sort_rec)); d_sort_rec = nullptr; sort_rec_cap = 0;
+      HIPCHK(d_sort_rec.release(stream));
     } else {
       const int tiles_per_xcd = (nb + 7) / 8;
       k_permute<R, 0><<<8 * tiles_per_xcd, kBlock, 0, stream>>>(P, P2, d_vals2, n, cfg.nspec, tiles_per_xcd);
@@ -5405,13 +5258,12 @@ struct Engine : EngineBase {
       HIPCHK(hipMemcpyAsync(host, dev, n * sizeof(R), hipMemcpyDeviceToHost, stream));
       return 0;
     }
-    int rc = ensure_staging(n * cfg.host_real_bytes);
-    if (rc) return rc;
+    HIPCHK(staging.reserve(n * cfg.host_real_bytes, stream));
     const int nb = (int)((n + kBlock - 1) / kBlock);
-    k_convert<R><<<nb, kBlock, 0, stream>>>(dev, cfg.host_real_bytes == 8 ? (double *)staging : nullptr,
-                                            cfg.host_real_bytes == 4 ? (float *)staging : nullptr, (long long)n);
+    k_convert<R><<<nb, kBlock, 0, stream>>>(dev, cfg.host_real_bytes == 8 ? staging.as<double>() : nullptr,
+                                            cfg.host_real_bytes == 4 ? staging.as<float>() : nullptr, (long long)n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host, staging, n * cfg.host_real_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(host, staging.as(), n * cfg.host_real_bytes, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));   // staging is reused
     return 0;
   }
@@ -5509,16 +5361,12 @@ struct Engine : EngineBase {
       return 0;
     }
     const size_t bytes = n * sizeof(T);
-    if (2 * bytes > red_pin_bytes) {
-      if (red_pin) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipHostFree(red_pin)); red_pin = nullptr; red_pin_bytes = 0; }
-      HIPCHK(hipHostMalloc(&red_pin, 2 * bytes));
-      red_pin_bytes = 2 * bytes;
-    }
-    HIPCHK(hipMemcpyAsync(red_pin, send, bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(red_pin.reserve(2 * bytes, stream));
+    HIPCHK(hipMemcpyAsync(red_pin.as(), send, bytes, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    if (host_allreduce(host_allreduce_user, red_pin, (char *)red_pin + bytes, (int64_t)n, sizeof(T) == 8 ? 1 : 0) != 0)
+    if (host_allreduce(host_allreduce_user, red_pin.as(), red_pin.as<char>() + bytes, (int64_t)n, sizeof(T) == 8 ? 1 : 0) != 0)
       return fail(FPX_ERR_DEVICE, std::string(who) + ": the host's all-reduce callback failed");
-    HIPCHK(hipMemcpyAsync(*recv, (char *)red_pin + bytes, bytes, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(*recv, red_pin.as<char>() + bytes, bytes, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));    // the bounce buffer is reused by the next grid
     return 0;
   }
@@ -5608,11 +5456,7 @@ struct Engine : EngineBase {
   size_t n_flux = 0;
   double fx_geo[4] = {};                               // dxout, dyout, xoutshift, youtshift as the host passed them
   bool fx_red_valid = false;
-  struct FluxEvents { hipEvent_t e[4]; };
-  std::vector<FluxEvents> fx_ev_pool;
-  size_t fx_ev_used = 0;
-  double fx_acc_ms = 0;
-  long long fx_acc_launches = 0;
+  IntervalTimer<4> fx_timer{{0, 1}, {2, 3}};           // around k_flux_save | around k_calcfluxes
   template <typename H>
   int flux_init_t(const fpx_outgrid *g, const void *outheight) {
     n_flux = (size_t)6 * g->numxgrid * g->numygrid * g->numzgrid * cfg.nspec * g->maxpointspec_act * g->nageclass;
@@ -5645,13 +5489,8 @@ struct Engine : EngineBase {
       if ((rc = dalloc(&q, cap * hb * cfg.nspec))) return rc; fx_mass = q;
       if ((rc = dalloc(&fx_due, cap))) return rc;
     }
-    if (fx_ev_used >= 64) { const int rc = flux_harvest(); if (rc) return rc; }
-    if (fx_ev_used == fx_ev_pool.size()) {
-      FluxEvents fe;
-      for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&fe.e[i]));
-      fx_ev_pool.push_back(fe);
-    }
-    return 0;      // set fx_ev_used is this step's; it counts once both kernels are in the stream (flux_launch)
+    HIPCHK(fx_timer.begin(stream));
+    return 0;      // the timer's current set is this step's; it counts once both kernels are in the stream (flux_launch)
   }
   template <typename H>
   cf::Args<H> flux_args() const {
@@ -5670,33 +5509,20 @@ struct Engine : EngineBase {
   int flux_launch(bool after, int itime) {
     static_assert(cf::kMaxAgeCf == kMaxAge, "age-class limit");
     const cf::Args<H> A = flux_args<H>();
-    FluxEvents &fe = fx_ev_pool[fx_ev_used];
+    const Events<4> &fe = fx_timer.current();
     const int nb = (int)((numpart + 255) / 256);
-    HIPCHK(hipEventRecord(fe.e[after ? 2 : 0], stream));
+    HIPCHK(hipEventRecord(fe[after ? 2 : 0], stream));
     if (!after) cf::k_flux_save<H, R><<<nb, 256, 0, stream>>>(A, P.xt, P.yt, P.zt, P.xmass1, P.itra1, P.cap, numpart, itime);
     else cf::k_calcfluxes<H, R><<<nb, 256, 0, stream>>>(A, P.xt, P.yt, P.zt, P.npoint, P.itramem, numpart, itime);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(fe.e[after ? 3 : 1], stream));
-    if (after) { fx_ev_used++; fx_red_valid = false; }   // the partial sums move on
-    return 0;
-  }
-  int flux_harvest() {
-    HIPCHK(hipStreamSynchronize(stream));
-    for (size_t i = 0; i < fx_ev_used; i++) {
-      float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, fx_ev_pool[i].e[0], fx_ev_pool[i].e[1])); fx_acc_ms += t;
-      HIPCHK(hipEventElapsedTime(&t, fx_ev_pool[i].e[2], fx_ev_pool[i].e[3])); fx_acc_ms += t;
-      fx_acc_launches++;
-    }
-    fx_ev_used = 0;
+    HIPCHK(hipEventRecord(fe[after ? 3 : 1], stream));
+    if (after) { fx_timer.commit(); fx_red_valid = false; }   // the partial sums move on
     return 0;
   }
   int calcfluxes_time(double *ms, long long *launches, int reset) override {
-    const int rc = flux_harvest();
-    if (rc) return rc;
-    if (ms) *ms = fx_acc_ms;
-    if (launches) *launches = fx_acc_launches;
-    if (reset) { fx_acc_ms = 0; fx_acc_launches = 0; }
+    double t[2];
+    HIPCHK(fx_timer.read(stream, t, launches, reset != 0));
+    if (ms) *ms = t[0] + t[1];
     return 0;
   }
   template <typename H>
@@ -5813,11 +5639,7 @@ struct Engine : EngineBase {
   int *pa_n[2] = {nullptr, nullptr};
   void *pa_sum[2] = {nullptr, nullptr};
   int pa_cur = 0;
-  struct PaEvents { hipEvent_t e[2]; };
-  std::vector<PaEvents> pa_ev_pool;
-  size_t pa_ev_used = 0;
-  double pa_acc_ms = 0;
-  long long pa_acc_launches = 0;
+  IntervalTimer<2> pa_timer{{0, 1}};
   int partavg_alloc(int k) {
     const size_t cap = (size_t)P.cap, hb = (size_t)cfg.host_real_bytes;
     unsigned char *q;
@@ -5846,40 +5668,23 @@ struct Engine : EngineBase {
     return D;
   }
   int partavg_prepare() {
-    if (pa_ev_used >= 64) { const int rc = partavg_harvest(); if (rc) return rc; }
-    if (pa_ev_used == pa_ev_pool.size()) {
-      PaEvents pe;
-      for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&pe.e[i]));
-      pa_ev_pool.push_back(pe);
-    }
+    HIPCHK(pa_timer.begin(stream));
     return 0;
   }
   template <typename H>
   int partavg_launch(int itime) {
-    PaEvents &pe = pa_ev_pool[pa_ev_used];
-    HIPCHK(hipEventRecord(pe.e[0], stream));
+    const Events<2> &pe = pa_timer.current();
+    HIPCHK(hipEventRecord(pe[0], stream));
     pa::k_partavg<R, H><<<(int)((numpart + 255) / 256), 256, 0, stream>>>(V, P, diag_args<H>(), partavg_state<H>(pa_cur), d_pbl_flag, kKeyNotDue, numpart, itime);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(pe.e[1], stream));
-    pa_ev_used++;
-    return 0;
-  }
-  int partavg_harvest() {
-    HIPCHK(hipStreamSynchronize(stream));
-    for (size_t i = 0; i < pa_ev_used; i++) {
-      float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, pa_ev_pool[i].e[0], pa_ev_pool[i].e[1])); pa_acc_ms += t;
-      pa_acc_launches++;
-    }
-    pa_ev_used = 0;
+    HIPCHK(hipEventRecord(pe[1], stream));
+    pa_timer.commit();
     return 0;
   }
   int partavg_time(double *ms, long long *launches, int reset) override {
-    const int rc = partavg_harvest();
-    if (rc) return rc;
-    if (ms) *ms = pa_acc_ms;
-    if (launches) *launches = pa_acc_launches;
-    if (reset) { pa_acc_ms = 0; pa_acc_launches = 0; }
+    double t;
+    HIPCHK(pa_timer.read(stream, &t, launches, reset != 0));
+    if (ms) *ms = t;
     return 0;
   }
   template <typename H>
@@ -5905,20 +5710,15 @@ struct Engine : EngineBase {
     const long long n = numpart;
     FILE *fh = fopen(name, "wb");
     if (!fh) return fail(FPX_ERR_ARG, std::string("partoutput_average: cannot open ") + name);
-    unsigned int *out = nullptr, *stat = nullptr;
-    void *pin = nullptr;
-    auto cleanup = [&]() {
-      if (out) (void)hipFree(out);
-      if (stat) (void)hipFree(stat);
-      if (pin) (void)hipHostFree(pin);
-      if (fh) fclose(fh);
-    };
+    FileCloser closer(fh);
+    Scratch b_out, b_stat, pin(true);
     unsigned int hs[2] = {0, 0};
     bool io_ok = true;
     if (n > 0) {
-      hipError_t e = hipMalloc(&out, (size_t)n * 24);
-      if (e == hipSuccess) e = hipMalloc(&stat, 2 * sizeof(unsigned int));
-      if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_NOMEM, std::string("partoutput_average: record buffer: ") + hipGetErrorString(e)); }
+      hipError_t e = b_out.reserve((size_t)n * 24, stream);
+      if (e == hipSuccess) e = b_stat.reserve(2 * sizeof(unsigned int), stream);
+      if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("partoutput_average: record buffer: ") + hipGetErrorString(e));
+      unsigned int *out = b_out.as<unsigned int>(), *stat = b_stat.as<unsigned int>();
       e = hipMemsetAsync(out, 0, (size_t)n * 24, stream);
       if (e == hipSuccess) e = hipMemsetAsync(stat, 0, 2 * sizeof(unsigned int), stream);
       if (e == hipSuccess) {
@@ -5928,18 +5728,16 @@ struct Engine : EngineBase {
       if (e == hipSuccess) e = hipMemcpyAsync(hs, stat, sizeof hs, hipMemcpyDeviceToHost, stream);
       if (e == hipSuccess) e = hipStreamSynchronize(stream);
       const size_t total = (size_t)hs[1] * 24, chunk = (size_t)64 << 20;
-      if (e == hipSuccess && total) e = hipHostMalloc(&pin, std::min(chunk, total));
+      if (e == hipSuccess && total) e = pin.reserve(std::min(chunk, total), stream);
       for (size_t off = 0; e == hipSuccess && io_ok && off < total; off += chunk) {
         const size_t nbytes = std::min(chunk, total - off);
-        e = hipMemcpyAsync(pin, (const char *)out + off, nbytes, hipMemcpyDeviceToHost, stream);
+        e = hipMemcpyAsync(pin.as(), (const char *)out + off, nbytes, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e == hipSuccess) io_ok = fwrite(pin, 1, nbytes, fh) == nbytes;
+        if (e == hipSuccess) io_ok = fwrite(pin.as(), 1, nbytes, fh) == nbytes;
       }
-      if (e != hipSuccess) { cleanup(); return fail(FPX_ERR_DEVICE, std::string("partoutput_average: ") + hipGetErrorString(e)); }
+      if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("partoutput_average: ") + hipGetErrorString(e));
     }
-    io_ok = (fclose(fh) == 0) && io_ok;
-    fh = nullptr;
-    cleanup();
+    io_ok = (closer.close() == 0) && io_ok;
     if (!io_ok) return fail(FPX_ERR_ARG, std::string("partoutput_average: write error on ") + name);
     if (nrecords) *nrecords = hs[0];
     return 0;
@@ -6420,9 +6218,9 @@ int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n) {
   if (fn < 0 || fn > 31 || !x || !y || n < 0) return FPX_ERR_ARG;
   if (n == 0) return FPX_OK;
   const int64_t nin = (fn == 12 || fn == 13) ? 2 * n : n;   // fn 12, 13: x[0 .. n) the points, x[n .. 2n) their exp(-x*x)
-  double *dx = nullptr, *dy = nullptr;
-  if (hipMalloc(&dx, nin * sizeof(double)) != hipSuccess) return FPX_ERR_NOMEM;
-  if (hipMalloc(&dy, n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); return FPX_ERR_NOMEM; }
+  fpx::Scratch bx, by;
+  if (bx.reserve(nin * sizeof(double), nullptr) != hipSuccess || by.reserve(n * sizeof(double), nullptr) != hipSuccess) return FPX_ERR_NOMEM;
+  double *dx = bx.as<double>(), *dy = by.as<double>();
   hipError_t e = hipMemcpy(dx, x, nin * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     if (fn >= 12 && fn <= 14) fpx::k_erf_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(fn, dx, dy, n);
@@ -6430,32 +6228,30 @@ int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(y, dy, n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dx); (void)hipFree(dy);
   return e == hipSuccess ? FPX_OK : FPX_ERR_DEVICE;
 }
 
 int fpx_hanna_probe(const double *in, double *out, int64_t n) {
   if (!in || !out || n < 0) return FPX_ERR_ARG;
   if (n == 0) return FPX_OK;
-  double *dx = nullptr, *dy = nullptr;
-  if (hipMalloc(&dx, 5 * n * sizeof(double)) != hipSuccess) return FPX_ERR_NOMEM;
-  if (hipMalloc(&dy, 10 * n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); return FPX_ERR_NOMEM; }
+  fpx::Scratch bx, by;
+  if (bx.reserve(5 * n * sizeof(double), nullptr) != hipSuccess || by.reserve(10 * n * sizeof(double), nullptr) != hipSuccess) return FPX_ERR_NOMEM;
+  double *dx = bx.as<double>(), *dy = by.as<double>();
   hipError_t e = hipMemcpy(dx, in, 5 * n * sizeof(double), hipMemcpyHostToDevice);
   for (int which = 0; which < 2 && e == hipSuccess; which++) {   // out: all points of the engine's form, then all of the plain one
     fpx::k_hanna_probe<<<(unsigned)((n + fpx::kBlock - 1) / fpx::kBlock), fpx::kBlock>>>(which, dx, dy, n);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out + 10 * n * which, dy, 10 * n * sizeof(double), hipMemcpyDeviceToHost);
   }
-  (void)hipFree(dx); (void)hipFree(dy);
   return e == hipSuccess ? FPX_OK : FPX_ERR_DEVICE;
 }
 
 int fpx_cbl_probe(int32_t form, const double *in, double *out, int64_t n) {
   if ((form != 0 && form != 1) || !in || !out || n < 0) return FPX_ERR_ARG;
   if (n == 0) return FPX_OK;
-  double *dx = nullptr, *dy = nullptr;
-  if (hipMalloc(&dx, 10 * n * sizeof(double)) != hipSuccess) return FPX_ERR_NOMEM;
-  if (hipMalloc(&dy, 3 * n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); return FPX_ERR_NOMEM; }
+  fpx::Scratch bx, by;
+  if (bx.reserve(10 * n * sizeof(double), nullptr) != hipSuccess || by.reserve(3 * n * sizeof(double), nullptr) != hipSuccess) return FPX_ERR_NOMEM;
+  double *dx = bx.as<double>(), *dy = by.as<double>();
   hipError_t e = hipMemcpy(dx, in, 10 * n * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     const unsigned blocks = (unsigned)((n + fpx::kBlock - 1) / fpx::kBlock);
@@ -6464,20 +6260,20 @@ int fpx_cbl_probe(int32_t form, const double *in, double *out, int64_t n) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(out, dy, 3 * n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dx); (void)hipFree(dy);
   return e == hipSuccess ? FPX_OK : FPX_ERR_DEVICE;
 }
 
 }  // extern "C"
 template <typename R>
 static int find_level_probe(const R *height, int32_t nz, const R *z, const int32_t *guess, int64_t n, int32_t *idx, R *zz) {
-  R *dh = nullptr, *dz = nullptr, *dzz = nullptr;
-  int *dg = nullptr, *di = nullptr;
-  hipError_t e = hipMalloc(&dh, nz * sizeof(R));
-  if (e == hipSuccess) e = hipMalloc(&dz, n * sizeof(R));
-  if (e == hipSuccess) e = hipMalloc(&dg, n * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&di, n * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&dzz, 2 * n * sizeof(R));
+  fpx::Scratch bh, bz, bg, bi, bzz;
+  hipError_t e = bh.reserve(nz * sizeof(R), nullptr);
+  if (e == hipSuccess) e = bz.reserve(n * sizeof(R), nullptr);
+  if (e == hipSuccess) e = bg.reserve(n * sizeof(int), nullptr);
+  if (e == hipSuccess) e = bi.reserve(n * sizeof(int), nullptr);
+  if (e == hipSuccess) e = bzz.reserve(2 * n * sizeof(R), nullptr);
+  R *dh = bh.as<R>(), *dz = bz.as<R>(), *dzz = bzz.as<R>();
+  int *dg = bg.as<int>(), *di = bi.as<int>();
   const bool nomem = e != hipSuccess;
   if (e == hipSuccess) e = hipMemcpy(dh, height, nz * sizeof(R), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dz, z, n * sizeof(R), hipMemcpyHostToDevice);
@@ -6488,7 +6284,6 @@ static int find_level_probe(const R *height, int32_t nz, const R *z, const int32
     if (e == hipSuccess) e = hipMemcpy(idx + n * which, di, n * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(zz + 2 * n * which, dzz, 2 * n * sizeof(R), hipMemcpyDeviceToHost);
   }
-  (void)hipFree(dh); (void)hipFree(dz); (void)hipFree(dg); (void)hipFree(di); (void)hipFree(dzz);
   return e == hipSuccess ? FPX_OK : nomem ? FPX_ERR_NOMEM : FPX_ERR_DEVICE;
 }
 
