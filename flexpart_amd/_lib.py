@@ -45,7 +45,7 @@ class FpxConfig(C.Structure):
         ("drybkdep", C.c_int32), ("wetbkdep", C.c_int32),
         ("turboff", C.c_int32), ("interpolhmix", C.c_int32), ("blend_mode", C.c_int32), ("pbl_slice_passes", C.c_int32),
         ("global_particles", C.c_int64), ("ipout", C.c_int32), ("iflux", C.c_int32), ("linit_cond", C.c_int32),
-        ("device_flux", C.c_int32), ("device_partavg", C.c_int32), ("reserved", C.c_int32 * 1),
+        ("device_flux", C.c_int32), ("device_partavg", C.c_int32), ("device_initcond", C.c_int32),
     ]
 
 
@@ -113,6 +113,10 @@ class FpxCalcpvCfg(C.Structure):
 class FpxFluxout(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("bdate", C.c_double), ("outstep", C.c_double),
                 ("area", C.c_void_p), ("areaeast", C.c_void_p), ("areanorth", C.c_void_p)]
+
+
+class FpxInitout(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("ind_rel", C.c_int32), ("rho_rel", C.c_void_p)]
 
 
 class FpxDiagFields(C.Structure):
@@ -197,7 +201,7 @@ SYMBOLS = [
     "fpx_rng_get_table", "fpx_upload_particles", "fpx_download_particles", "fpx_set_numpart", "fpx_set_release_points", "fpx_set_release_heights", "fpx_release_init", "fpx_releaseparticles", "fpx_split_particles", "fpx_redist_plan", "fpx_redist_bytes", "fpx_redist_pack", "fpx_redist_unpack",
     "fpx_step", "fpx_step_async", "fpx_sync", "fpx_counters", "fpx_kernel_time", "fpx_kernel_times", "fpx_sort_particles",
     "fpx_seed_particles", "fpx_stream", "fpx_outgrid_init", "fpx_set_output_times", "fpx_conccalc",
-    "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
+    "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_initcond_finish", "fpx_get_initcond", "fpx_initial_cond_output", "fpx_initcond_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
     "fpx_wetdepo", "fpx_get_wetgrid", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_cbl_probe", "fpx_find_level_probe",
     "fpx_outgrid_nest_init", "fpx_get_grids_nest", "fpx_receptors_init", "fpx_get_receptors", "fpx_upload_wet_nest_fields",
     "fpx_verttransform_ecmwf", "fpx_verttransform_nest", "fpx_verttransform_time", "fpx_calcpar", "fpx_calcpar_time", "fpx_getvdep_init", "fpx_getvdep", "fpx_getvdep_time", "fpx_calcpv_init", "fpx_get_pvh", "fpx_calcpv_time", "fpx_upload_diag_fields", "fpx_partoutput", "fpx_partoutput_time", "fpx_readpartpositions", "fpx_concoutput",
@@ -301,6 +305,10 @@ def load():
     lib.fpx_get_partavg.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
     lib.fpx_partoutput_average.argtypes = [vp, C.c_int32, C.c_char_p, C.POINTER(C.c_int64)]
     lib.fpx_partavg_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
+    lib.fpx_initcond_finish.argtypes = [vp, C.c_int32]
+    lib.fpx_get_initcond.argtypes = [vp, vp, C.c_int32, C.c_int32]
+    lib.fpx_initial_cond_output.argtypes = [vp, C.c_int32, C.POINTER(FpxInitout), C.c_char_p, C.c_int32]
+    lib.fpx_initcond_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
     lib.fpx_comm_unique_id.argtypes = [vp, C.c_int32]
     lib.fpx_comm_init.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32]
     lib.fpx_nests_init.argtypes = [vp, C.POINTER(FpxNests)]

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -27,6 +28,7 @@
 #include "fpx_calcpv.hpp"
 #include "fpx_calcfluxes.hpp"
 #include "fpx_partavg.hpp"
+#include "fpx_initcond.hpp"
 #include "fpx_convect.hpp"
 #include "fpx_rng_host.hpp"
 #include "fpx_host_res.hpp"
@@ -2067,6 +2069,10 @@ struct EngineBase {
   virtual int get_partavg(long long first, long long count, int32_t *npart_av, void *const *sums) = 0;
   virtual int partoutput_average(int itime, const char *prefix, int64_t *nrecords) = 0;
   virtual int partavg_time(double *ms, long long *launches, int reset) = 0;
+  virtual int initcond_finish(int itime) = 0;
+  virtual int get_initcond(void *init_cond, int allreduce, int clear) = 0;
+  virtual int initial_cond_output(int itime, const fpx_initout *o, const char *prefix, int reduced) = 0;
+  virtual int initcond_time(double *ms, long long *launches, int reset) = 0;
   virtual int count_particles(int64_t *local, int64_t *total, int allreduce) = 0;
   virtual int lane_stats(uint64_t *out, int n, int reset) = 0;
   virtual int set_option(const char *name, const char *value) = 0;
@@ -2279,7 +2285,10 @@ struct Engine : EngineBase {
     if (cfg.device_flux != 0 && cfg.device_flux != 1) return fail(FPX_ERR_ARG, "device_flux must be 0 or 1");
     if (cfg.device_flux == 1 && cfg.iflux != 1) return fail(FPX_ERR_ARG, "device_flux = 1 without iflux = 1: there is no flux to compute");
     if (cfg.iflux == 1 && !cfg.device_flux) return fail(FPX_ERR_UNSUPPORTED, "iflux = 1: the particle loop's calcfluxes (timemanager.f90:623) is not computed by this engine");
-    if (cfg.linit_cond >= 1) return fail(FPX_ERR_UNSUPPORTED, "linit_cond >= 1: the particle loop's initial_cond_calc (timemanager.f90:631,702) is not computed by this engine");
+    if (cfg.linit_cond >= 1 && !cfg.device_initcond) return fail(FPX_ERR_UNSUPPORTED, "linit_cond >= 1: the particle loop's initial_cond_calc (timemanager.f90:631,702) is not computed by this engine");
+    if (cfg.device_initcond != 0 && cfg.device_initcond != 1) return fail(FPX_ERR_ARG, "device_initcond must be 0 or 1");
+    if (cfg.device_initcond == 1 && cfg.linit_cond != 1 && cfg.linit_cond != 2) return fail(FPX_ERR_ARG, "device_initcond = 1 needs linit_cond = 1 or 2: there is no sensitivity to compute");
+    if (cfg.device_initcond == 1 && cfg.ldirect == 1) return fail(FPX_ERR_ARG, "device_initcond = 1 with ldirect = 1: the sensitivity to initial conditions belongs to backward runs (readcommand.f90:349)");
     if (cfg.lsettling && cfg.compute_real_bytes == 4 && (long long)cfg.nx * cfg.ny > (1ll << 24)) return fail(FPX_ERR_ARG, "lsettling with the f32 engine: nx*ny must not exceed 2^24 (the Langevin kernel keeps the column index of get_settling in an f32 stash slot)");
     if (cfg.blend_mode < 0 || cfg.blend_mode > 2) return fail(FPX_ERR_ARG, "blend_mode must be 0 (automatic), 1 (on) or 2 (off)");
     if (cfg.global_particles < 0) return fail(FPX_ERR_ARG, "global_particles must not be negative");
@@ -4494,6 +4503,9 @@ struct Engine : EngineBase {
     for (int k = 0; k < pa::kSums; k++) if ((rc = ckpt_get_array(fh, S.sum + (size_t)k * S.cap, n, buf))) return rc;
     return 0;
   }
+  // bit 2: last, init_cond of a run with device_initcond (uint64 count, then the values in the host's real kind)
+  static constexpr int32_t kCkptInitcond = 4;
+  uint64_t ckpt_initcond_bytes(const CkptHeader &h) const { return (h.reserved & kCkptInitcond) ? 8 + (uint64_t)n_initcond * cfg.host_real_bytes : 0; }
   uint64_t ckpt_flux_bytes(const CkptHeader &h) const { return (h.reserved & kCkptFlux) ? 8 + (uint64_t)n_flux * cfg.host_real_bytes : 0; }
   struct CkptRng { HostRng<float> r4; HostRng<double> r8; Ran1 rel; };
   uint64_t conv_cbase_bytes() const {      // cbaseflux of the mother grid and of every nest that has convection fields
@@ -4524,7 +4536,8 @@ struct Engine : EngineBase {
     ckpt_describe_grid(h);
     h.reserved = cfg.device_flux && fx_flux ? kCkptFlux : 0;      // the flux section follows cbaseflux: a count and the values
     if (cfg.device_partavg) h.reserved |= kCkptPartavg;
-    h.total_bytes = ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h);
+    if (cfg.device_initcond && ic_grid) h.reserved |= kCkptInitcond;
+    h.total_bytes = ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h) + ckpt_initcond_bytes(h);
     if (fwrite(&h, sizeof(h), 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
     CkptRng rs{rng4, rng8, rel_ran1};
     if (fwrite(&rs, sizeof(rs), 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
@@ -4555,6 +4568,11 @@ struct Engine : EngineBase {
       if (fwrite(&cnt, 8, 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
       if ((rc = cfg.host_real_bytes == 4 ? ckpt_put_partavg<float>(fh, n, buf) : ckpt_put_partavg<double>(fh, n, buf))) return rc;
     }
+    if (h.reserved & kCkptInitcond) {
+      const uint64_t cnt = n_initcond;
+      if (fwrite(&cnt, 8, 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
+      if ((rc = ckpt_put_plain(fh, (const unsigned char *)ic_grid, n_initcond * cfg.host_real_bytes, buf))) return rc;
+    }
     if (closer.close() != 0) return fail(FPX_ERR_ARG, std::string("checkpoint_write: write error on ") + path);
     return 0;
   }
@@ -4584,12 +4602,14 @@ struct Engine : EngineBase {
         return fail(FPX_ERR_ARG, "checkpoint_read: written on another grid (nx, ny, nz, maxspec or the nest extents differ)");
       if (mine.pad != h.pad) return fail(FPX_ERR_ARG, "checkpoint_read: written with (without) DRYBKDEP / WETBKDEP");
       // the whole file must be there before a single array is touched
-      if ((h.reserved & ~(kCkptFlux | kCkptPartavg)) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: unknown sections in the file");
+      if ((h.reserved & ~(kCkptFlux | kCkptPartavg | kCkptInitcond)) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: unknown sections in the file");
+      if (((h.reserved & kCkptInitcond) != 0) != (cfg.device_initcond && ic_grid))
+        return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_initcond; create the engine alike and call fpx_outgrid_init first");
       if (((h.reserved & kCkptPartavg) != 0) != (cfg.device_partavg != 0))
         return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_partavg; create the engine alike");
       if (((h.reserved & kCkptFlux) != 0) != (cfg.device_flux && fx_flux))
         return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_flux; create the engine alike and call fpx_outgrid_init first");
-      if (h.total_bytes != ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h)) return fail(FPX_ERR_ARG, "checkpoint_read: inconsistent header");
+      if (h.total_bytes != ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h) + ckpt_initcond_bytes(h)) return fail(FPX_ERR_ARG, "checkpoint_read: inconsistent header");
       if (fseek(fh, 0, SEEK_END) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: cannot seek");
       const long long len = (long long)ftell(fh);
       if (len < 0 || (uint64_t)len != h.total_bytes)
@@ -4640,6 +4660,12 @@ struct Engine : EngineBase {
       uint64_t cnt = 0;
       if (fread(&cnt, 8, 1, fh) != 1 || cnt != (uint64_t)n) return ckpt_invalidate(fail(FPX_ERR_ARG, "checkpoint_read: the section of the interval averages does not match the particle count"));
       if ((rc = cfg.host_real_bytes == 4 ? ckpt_get_partavg<float>(fh, n, buf) : ckpt_get_partavg<double>(fh, n, buf))) return ckpt_invalidate(rc);
+    }
+    if (h.reserved & kCkptInitcond) {
+      uint64_t cnt = 0;
+      if (fread(&cnt, 8, 1, fh) != 1 || cnt != (uint64_t)n_initcond) return ckpt_invalidate(fail(FPX_ERR_ARG, "checkpoint_read: the init_cond grid of the checkpoint is not the one configured"));
+      if ((rc = ckpt_get_plain(fh, (unsigned char *)ic_grid, n_initcond * cfg.host_real_bytes, buf))) return ckpt_invalidate(rc);
+      ic_red_valid = false;
     }
     for (bool &v : red_valid) v = false;
     rng4 = rs.r4; rng8 = rs.r8; rel_ran1 = rs.rel;
@@ -4782,6 +4808,7 @@ struct Engine : EngineBase {
     for (int l = 0; l < V.numbnests; l++)
       if (!nest_loaded[l][0] || !nest_loaded[l][1]) return fail(FPX_ERR_STATE, "step: nest fields missing (fpx_upload_nest_fields, both slots)");
     if (cfg.device_flux && !Gp.on) return fail(FPX_ERR_STATE, "step: device_flux = 1 needs the output grid the fluxes are counted on (fpx_outgrid_init)");
+    if (cfg.device_initcond && !ic_grid) return fail(FPX_ERR_STATE, "step: device_initcond = 1 needs the output grid init_cond is counted on (fpx_outgrid_init)");
     if (cfg.device_partavg)
       for (int i = 0; i < 9; i++)
         if (!diag_have[i]) return fail(FPX_ERR_STATE, "step: device_partavg = 1 needs oro, pv, qv, tt of both slots on the device (fpx_upload_diag_fields or fpx_verttransform_ecmwf)");
@@ -4789,6 +4816,7 @@ struct Engine : EngineBase {
     if (numpart == 0) return 0;
     if (cfg.device_flux) { const int rc = flux_prepare(); if (rc) return rc; }
     if (cfg.device_partavg) { const int rc = partavg_prepare(); if (rc) return rc; }
+    if (cfg.device_initcond) HIPCHK(ic_timer.begin(stream));
     if (cfg.drydep) red_valid[RG_DRY] = red_valid[RG_DRYN] = false;
     if (cfg.sort_interval > 0 && step_counter > 0 && step_counter % (unsigned)cfg.sort_interval == 0) {
       int rc = sort_particles();
@@ -4908,6 +4936,10 @@ struct Engine : EngineBase {
     V.w3t0 = nullptr; V.w3t1 = nullptr; V.r2t0 = nullptr;      // the blended packs belong to this step's itime only
     if (cfg.device_partavg) {   // timemanager.f90:617 -- the position after advance, the particles k_prep found due (its keys outlive the step)
       const int rc = cfg.host_real_bytes == 4 ? partavg_launch<float>(itime) : partavg_launch<double>(itime);
+      if (rc) return rc;
+    }
+    if (cfg.device_initcond) {   // timemanager.f90:631,702 -- the particles the epilogue has just terminated
+      const int rc = cfg.host_real_bytes == 4 ? initcond_launch<float>() : initcond_launch<double>();
       if (rc) return rc;
     }
     if (opt.verbose > 1) {   // the lists of the launches (a synchronisation per step: diagnostics only)
@@ -5226,6 +5258,10 @@ struct Engine : EngineBase {
     Gp.nested = 0; Gp.numreceptor = 0;
     if (cfg.device_flux) {
       rc = cfg.host_real_bytes == 4 ? flux_init_t<float>(g, outheight) : flux_init_t<double>(g, outheight);
+      if (rc) return rc;
+    }
+    if (cfg.device_initcond) {
+      rc = cfg.host_real_bytes == 4 ? initcond_init_t<float>(g, outheight) : initcond_init_t<double>(g, outheight);
       if (rc) return rc;
     }
     Gp.on = 1;
@@ -5759,6 +5795,172 @@ struct Engine : EngineBase {
     return cfg.host_real_bytes == 4 ? partoutput_average_t<float>(itime, name, nrecords) : partoutput_average_t<double>(itime, name, nrecords);
   }
 
+  // ---- sensitivity to initial conditions (fpx_initcond.hpp; fpx_config.device_initcond) --------------------------
+  // init_cond and everything the kernels compare a position with are kept in the host's real kind H, whatever the engine
+  // computes in: initial_cond_calc.f90 declares them default real.  Allocated by fpx_outgrid_init, zero at creation;
+  // nothing but the `clear` of fpx_get_initcond resets it -- it accumulates over the whole run.
+  void *ic_grid = nullptr, *ic_grid0 = nullptr;        // unc_mod's init_cond; the receive buffer of its reduction
+  void *ic_outh = nullptr;                             // outheight in H
+  size_t n_initcond = 0;
+  double ic_geo[4] = {};                               // dxout, dyout, xoutshift, youtshift as the host passed them
+  int ic_iofr = 0;
+  bool ic_red_valid = false;
+  IntervalTimer<2> ic_timer{{0, 1}}, ic_fin_timer{{0, 1}};   // k_initcond per step; k_initcond_finish
+  template <typename H>
+  int initcond_init_t(const fpx_outgrid *g, const void *outheight) {
+    n_initcond = (size_t)g->numxgrid * g->numygrid * g->numzgrid * cfg.nspec * g->maxpointspec_act;   // outgrid_init.f90:296 (maxspec -> nspec)
+    ic_geo[0] = g->dxout; ic_geo[1] = g->dyout; ic_geo[2] = g->xoutshift; ic_geo[3] = g->youtshift;
+    ic_iofr = g->ioutputforeachrelease;
+    int rc;
+    H *a, *f;
+    if ((rc = dalloc(&a, (size_t)g->numzgrid)) || (rc = dalloc(&f, n_initcond))) return rc;
+    HIPCHK(hipMemcpyAsync(a, outheight, g->numzgrid * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(f, 0, n_initcond * sizeof(H), stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    ic_outh = a; ic_grid = f;
+    return 0;
+  }
+  template <typename H>
+  ic::Args<H> initcond_args() const {
+    ic::Args<H> A;
+    A.linit_cond = cfg.linit_cond;
+    A.nx = cfg.nx; A.ny = cfg.ny; A.nz = cfg.nz;
+    A.numxgrid = Gp.numxgrid; A.numygrid = Gp.numygrid; A.numzgrid = Gp.numzgrid; A.nspec = cfg.nspec; A.maxpointspec_act = Gp.maxpointspec_act;
+    A.use_npoint = ic_iofr == 1 && cfg.mdomainfill == 0;
+    A.dx = (H)cfg.dx; A.dy = (H)cfg.dy; A.dxout = (H)ic_geo[0]; A.dyout = (H)ic_geo[1]; A.xoutshift = (H)ic_geo[2]; A.youtshift = (H)ic_geo[3];
+    A.outheight = (const H *)ic_outh; A.init_cond = (H *)ic_grid;
+    return A;
+  }
+  template <typename H>
+  int initcond_launch() {
+    const Events<2> &ie = ic_timer.current();
+    HIPCHK(hipEventRecord(ie[0], stream));
+    ic::k_initcond<R, H><<<(int)((numpart + 255) / 256), 256, 0, stream>>>(initcond_args<H>(), V, P, d_pbl_flag, kKeyNotDue, kDead, numpart);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ie[1], stream));
+    ic_timer.commit();
+    ic_red_valid = false;
+    return 0;
+  }
+  // the device time of k_initcond and k_initcond_finish; the launches are the steps that ran k_initcond
+  int initcond_time(double *ms, long long *launches, int reset) override {
+    double t = 0, tf = 0;
+    HIPCHK(ic_timer.read(stream, &t, launches, reset != 0));
+    HIPCHK(ic_fin_timer.read(stream, &tf, nullptr, reset != 0));
+    if (ms) *ms = t + tf;
+    return 0;
+  }
+  // timemanager.f90:735-737
+  int initcond_finish(int itime) override {
+    if (!cfg.device_initcond) return fail(FPX_ERR_STATE, "initcond_finish: the engine was created without device_initcond");
+    if (!Gp.on || !ic_grid) return fail(FPX_ERR_STATE, "initcond_finish: fpx_outgrid_init first");
+    if (numpart == 0) return 0;
+    if (!height_set || !slot_loaded[0] || !slot_loaded[1]) return fail(FPX_ERR_STATE, "initcond_finish: height and both field slots must be set first");
+    HIPCHK(ic_fin_timer.begin(stream));
+    const Events<2> &ie = ic_fin_timer.current();
+    const int nb = (int)((numpart + 255) / 256);      // whole blocks: the kernel keeps its waves convergent
+    HIPCHK(hipEventRecord(ie[0], stream));
+    if (cfg.host_real_bytes == 4) ic::k_initcond_finish<R, float, kMaxNz><<<nb, 256, 0, stream>>>(initcond_args<float>(), V, P, numpart, itime);
+    else ic::k_initcond_finish<R, double, kMaxNz><<<nb, 256, 0, stream>>>(initcond_args<double>(), V, P, numpart, itime);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ie[1], stream));
+    ic_fin_timer.commit();
+    ic_red_valid = false;
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  template <typename H>
+  int initcond_reduce_t() {
+    H *recv = (H *)ic_grid0;
+    const int rc = reduce_into((const H *)ic_grid, &recv, n_initcond, "get_initcond");
+    ic_grid0 = recv;
+    if (!rc) ic_red_valid = true;
+    return rc;
+  }
+  int get_initcond(void *init_cond, int allreduce, int clear) override {
+    if (!cfg.device_initcond) return fail(FPX_ERR_STATE, "get_initcond: the engine was created without device_initcond");
+    if (!Gp.on || !ic_grid) return fail(FPX_ERR_STATE, "get_initcond: fpx_outgrid_init first");
+    const void *src = ic_grid;
+    if (allreduce && comm_ranks > 1) {
+      const int rc = cfg.host_real_bytes == 4 ? initcond_reduce_t<float>() : initcond_reduce_t<double>();
+      if (rc) return rc;
+      src = ic_grid0;
+    }
+    if (init_cond) HIPCHK(hipMemcpyAsync(init_cond, src, n_initcond * cfg.host_real_bytes, hipMemcpyDeviceToHost, stream));
+    if (clear) HIPCHK(hipMemsetAsync(ic_grid, 0, n_initcond * cfg.host_real_bytes, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  // initial_cond_output.f90:58-130 on the host from the downloaded grid, in the host's real kind: per species one
+  // unformatted sequential file
+  template <typename H>
+  int initial_cond_output_t(int itime, const fpx_initout *o, const char *prefix, const void *src) {
+#pragma clang fp contract(off)
+    std::vector<H> g(n_initcond);
+    HIPCHK(hipMemcpyAsync(g.data(), src, n_initcond * sizeof(H), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const int nxg = Gp.numxgrid, nyg = Gp.numygrid, nzg = Gp.numzgrid, ns = cfg.nspec, nkp = Gp.maxpointspec_act, np = V.numpoint;
+    const H smallnum = std::numeric_limits<H>::min();      // tiny(0.0)
+    std::vector<int32_t> di;
+    std::vector<H> dr;
+    for (int ks = 0; ks < ns; ks++) {
+      char name[1200];
+      snprintf(name, sizeof name, "%sgrid_initial_%03d", prefix, ks + 1);
+      FileCloser fc(fopen(name, "wb"));
+      FILE *fh = fc.f;
+      if (!fh) return fail(FPX_ERR_ARG, std::string("initial_cond_output: cannot open ") + name);
+      bool ok = true;
+      auto record = [&](const void *q, size_t n) {      // one unformatted sequential record: length, payload, length
+        const int32_t len = (int32_t)n;
+        ok = ok && fwrite(&len, 4, 1, fh) == 1 && (n == 0 || fwrite(q, 1, n, fh) == n) && fwrite(&len, 4, 1, fh) == 1;
+      };
+      const int32_t it = itime, zero = 0;
+      record(&it, 4);
+      for (int kp = 0; kp < nkp && ok; kp++) {
+        const H fact_recept = o->ind_rel == 1 ? ((const H *)o->rho_rel)[kp] : (H)1.;
+        const H xm = (H)rel_xmass_h[(size_t)ks * np + kp];
+        for (int d = 0; d < 2; d++) { record(&zero, 4); record(nullptr, 0); record(&zero, 4); record(nullptr, 0); }   // :83-92
+        di.clear(); dr.clear();
+        H sp_fact = (H)-1.;
+        bool sp_zer = true;
+        const H *gk = g.data() + (size_t)nxg * nyg * nzg * ((size_t)ks + (size_t)ns * kp);
+        for (int kz = 1; kz <= nzg; kz++) for (int jy = 0; jy < nyg; jy++) for (int ix = 0; ix < nxg; ix++) {
+          const H v = gk[(size_t)ix + (size_t)nxg * ((size_t)jy + (size_t)nyg * (size_t)(kz - 1))];
+          if (v > smallnum) {
+            if (sp_zer) {
+              di.push_back(ix + jy * nxg + kz * nxg * nyg);
+              sp_zer = false;
+              sp_fact = sp_fact * (H)-1.;
+            }
+            dr.push_back(sp_fact * v / xm * fact_recept);
+          } else sp_zer = true;
+        }
+        const int32_t ci = (int32_t)di.size(), cr = (int32_t)dr.size();
+        record(&ci, 4); record(di.data(), di.size() * 4);
+        record(&cr, 4); record(dr.data(), dr.size() * sizeof(H));
+      }
+      ok = (fc.close() == 0) && ok;
+      if (!ok) return fail(FPX_ERR_ARG, std::string("initial_cond_output: write error on ") + name);
+    }
+    return 0;
+  }
+  int initial_cond_output(int itime, const fpx_initout *o, const char *prefix, int reduced) override {
+    if (!cfg.device_initcond) return fail(FPX_ERR_STATE, "initial_cond_output: the engine was created without device_initcond");
+    if (!Gp.on || !ic_grid) return fail(FPX_ERR_STATE, "initial_cond_output: fpx_outgrid_init first");
+    if (!o || o->struct_bytes != (int32_t)sizeof(fpx_initout)) return fail(FPX_ERR_ARG, "initial_cond_output: null or fpx_initout size mismatch (ABI)");
+    if (!prefix) return fail(FPX_ERR_ARG, "initial_cond_output: null path prefix");
+    if (strlen(prefix) > 1000) return fail(FPX_ERR_ARG, "initial_cond_output: prefix too long");
+    if (o->ind_rel == 1 && !o->rho_rel) return fail(FPX_ERR_ARG, "initial_cond_output: ind_rel = 1 needs rho_rel");
+    if (V.numpoint < Gp.maxpointspec_act || rel_xmass_h.size() < (size_t)cfg.nspec * V.numpoint)
+      return fail(FPX_ERR_STATE, "initial_cond_output: xmass of every release point is needed (fpx_set_release_points)");
+    const void *src = ic_grid;
+    if (reduced && comm_ranks > 1) {
+      if (!ic_red_valid) return fail(FPX_ERR_STATE, "initial_cond_output: reduced = 1 needs fpx_get_initcond with allreduce = 1 first");
+      src = ic_grid0;
+    }
+    return cfg.host_real_bytes == 4 ? initial_cond_output_t<float>(itime, o, prefix, src) : initial_cond_output_t<double>(itime, o, prefix, src);
+  }
+
   // ---- nested grids --------------------------------------------------------------
   int nest_nxmaxn = 0, nest_nymaxn = 0;
   bool nest_loaded[kMaxNests][2] = {};
@@ -6183,6 +6385,16 @@ int fpx_partavg_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset)
   FPX_GUARD(h);
   long long l = 0;
   const int rc = h->impl->partavg_time(ms, &l, reset);
+  if (launches) *launches = l;
+  return rc;
+}
+int fpx_initcond_finish(fpx_handle h, int32_t itime) { FPX_GUARD(h); return h->impl->initcond_finish(itime); }
+int fpx_get_initcond(fpx_handle h, void *init_cond, int32_t allreduce, int32_t clear) { FPX_GUARD(h); return h->impl->get_initcond(init_cond, allreduce, clear); }
+int fpx_initial_cond_output(fpx_handle h, int32_t itime, const fpx_initout *o, const char *prefix, int32_t reduced) { FPX_GUARD(h); return h->impl->initial_cond_output(itime, o, prefix, reduced); }
+int fpx_initcond_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset) {
+  FPX_GUARD(h);
+  long long l = 0;
+  const int rc = h->impl->initcond_time(ms, &l, reset);
   if (launches) *launches = l;
   return rc;
 }

@@ -108,6 +108,7 @@ class Engine:
         cfg.turboff, cfg.interpolhmix = int(sc.get("turboff", 0)), int(sc.get("interpolhmix", 0))   # com_mod.f90:777-778
         cfg.ipout, cfg.iflux, cfg.linit_cond = int(sc.get("ipout", 0)), int(sc.get("iflux", 0)), int(sc.get("linit_cond", 0))   # refused when set
         cfg.device_flux = int(sc.get("device_flux", 0))   # iflux = 1 is accepted with it: the fluxes are computed here (get_flux, fluxoutput)
+        cfg.device_initcond = int(sc.get("device_initcond", 0))   # linit_cond = 1, 2 is accepted with it: init_cond is summed here (initcond_finish, get_initcond, initial_cond_output)
         cfg.device_partavg = int(sc.get("device_partavg", 0))   # ipout = 3 is accepted with it: the interval averages are kept here (get_partavg, partoutput_average)
         cfg.blend_mode = int(blend_mode)                # 0: from global_particles, 1 on, 2 off
         cfg.global_particles = int(global_particles)    # the run's particle count over all ranks
@@ -557,6 +558,34 @@ class Engine:
         check(self.lib.fpx_calcfluxes_time(self.h, C.byref(ms), C.byref(n), int(reset)), "fpx_calcfluxes_time")
         return ms.value, int(n.value)
 
+    def initcond_finish(self, itime=None):
+        """fpx_initcond_finish: the loop of timemanager.f90:735-737 -- every particle with itra1 = itime contributes."""
+        check(self.lib.fpx_initcond_finish(self.h, int(self.itime if itime is None else itime)), "fpx_initcond_finish")
+
+    def get_initcond(self, allreduce=False, clear=False):
+        """fpx_get_initcond: init_cond as summed so far (device_initcond = 1), in the host's real kind,
+        shape (maxpointspec_act, nspec, numzgrid, numygrid, numxgrid)."""
+        out = np.zeros(self.icshape, self.hreal)
+        check(self.lib.fpx_get_initcond(self.h, _vp(out), int(allreduce), int(clear)), "fpx_get_initcond")
+        return out
+
+    def initial_cond_output(self, itime, prefix, ind_rel=0, rho_rel=None, reduced=False):
+        """fpx_initial_cond_output: writes <prefix>grid_initial_<nnn> per species (initial_cond_output.f90); returns the
+        file names."""
+        from ._lib import FpxInitout
+        rr = None if rho_rel is None else np.ascontiguousarray(np.asarray(rho_rel, dtype=self.hreal))
+        if rr is not None and rr.size != self.icshape[0]:
+            raise ValueError("initial_cond_output: rho_rel [maxpointspec_act]")
+        o = FpxInitout(C.sizeof(FpxInitout), int(ind_rel), None if rr is None else rr.ctypes.data)
+        check(self.lib.fpx_initial_cond_output(self.h, int(itime), C.byref(o), str(prefix).encode(), int(reduced)), "fpx_initial_cond_output")
+        return [str(prefix) + "grid_initial_%03d" % (k + 1) for k in range(self.nspec)]
+
+    def initcond_time(self, reset=False):
+        """fpx_initcond_time: (device ms of k_initcond and k_initcond_finish since the last reset, steps that ran k_initcond)."""
+        ms = C.c_double(0); n = C.c_int64(0)
+        check(self.lib.fpx_initcond_time(self.h, C.byref(ms), C.byref(n), int(reset)), "fpx_initcond_time")
+        return ms.value, int(n.value)
+
     PARTAVG_SUMS = ("cartx", "carty", "cartz", "z", "topo", "pv", "qv", "tt", "uu", "vv", "rho", "tro", "hmix", "energy")
 
     def get_partavg(self, first=0, count=None):
@@ -810,6 +839,7 @@ class Engine:
                   "fpx_set_output_times")
         self.gshape = (len(lage), ncu, mps, self.nspec, nzg, nyg, nxg)
         self.fshape = (len(lage), mps, self.nspec, nzg, nyg, nxg, 6)      # flux_mod's flux, first index fastest
+        self.icshape = (mps, self.nspec, nzg, nyg, nxg)                   # unc_mod's init_cond, first index fastest
         if "outgridn" in sc:          # OUTGRID_NEST (readoutgrid_nest.f90)
             nxn, nyn = (int(v) for v in sc["outgridn"])
             dxn, dyn, lon0n, lat0n = (float(v) for v in sc["outgeomn"])

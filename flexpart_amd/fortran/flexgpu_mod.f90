@@ -25,7 +25,7 @@ module flexgpu_mod
 #ifdef FLEXGPU_FLUX
   use flux_mod, only: flux
 #endif
-  use unc_mod, only: gridunc, drygridunc, wetgridunc, griduncn, drygriduncn, wetgriduncn
+  use unc_mod, only: gridunc, drygridunc, wetgridunc, griduncn, drygriduncn, wetgriduncn, init_cond
   use conv_mod, only: nconvlev, cbaseflux, cbasefluxn
   implicit none
   private
@@ -36,6 +36,7 @@ module flexgpu_mod
             flexgpu_wet_init, flexgpu_upload_wet_fields, flexgpu_wetdepo, flexgpu_verttransform, &
             flexgpu_upload_diag_fields, flexgpu_partoutput, flexgpu_readpartpositions, &
             flexgpu_partoutput_average, flexgpu_get_partavg, &
+            flexgpu_initcond_finish, flexgpu_get_initcond, flexgpu_initial_cond_output, &
             flexgpu_concoutput, flexgpu_abi_sizes, flexgpu_comm_init_host, flexgpu_count_particles, flexgpu_set_option, flexgpu_get_info, &
             flexgpu_release_init, flexgpu_releaseparticles, flexgpu_split_particles, flexgpu_calcpar, &
             flexgpu_getvdep_init, flexgpu_getvdep, &
@@ -83,7 +84,7 @@ module flexgpu_mod
     integer(c_int32_t) :: ipout, iflux, linit_cond
     integer(c_int32_t) :: device_flux
     integer(c_int32_t) :: device_partavg
-    integer(c_int32_t) :: reserved(1)
+    integer(c_int32_t) :: device_initcond
   end type fpx_config
 
   type, bind(C) :: fpx_fields
@@ -128,6 +129,10 @@ module flexgpu_mod
     real(c_double) :: bdate, outstep
     type(c_ptr) :: area, areaeast, areanorth
   end type fpx_fluxout
+  type, bind(C) :: fpx_initout
+    integer(c_int32_t) :: struct_bytes, ind_rel
+    type(c_ptr) :: rho_rel
+  end type fpx_initout
 
   integer, parameter :: FPX_MAXNESTS = 4
   type, bind(C) :: fpx_nests
@@ -352,6 +357,30 @@ module flexgpu_mod
       integer(c_int64_t), intent(out) :: launches
       integer(c_int32_t), value :: reset
     end function fpx_partavg_time
+    integer(c_int) function fpx_initcond_finish(h, itime) bind(C, name='fpx_initcond_finish')
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: itime
+    end function fpx_initcond_finish
+    integer(c_int) function fpx_get_initcond(h, init_cond, allreduce, clear) bind(C, name='fpx_get_initcond')
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: h, init_cond
+      integer(c_int32_t), value :: allreduce, clear
+    end function fpx_get_initcond
+    integer(c_int) function fpx_initial_cond_output(h, itime, o, prefix, reduced) bind(C, name='fpx_initial_cond_output')
+      import :: c_ptr, c_int, c_int32_t, c_char, fpx_initout
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: itime, reduced
+      type(fpx_initout), intent(in) :: o
+      character(kind=c_char), intent(in) :: prefix(*)
+    end function fpx_initial_cond_output
+    integer(c_int) function fpx_initcond_time(h, ms, launches, reset) bind(C, name='fpx_initcond_time')
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: ms
+      integer(c_int64_t), intent(out) :: launches
+      integer(c_int32_t), value :: reset
+    end function fpx_initcond_time
     integer(c_int) function fpx_conv_init(h, c) bind(C, name='fpx_conv_init')
       import :: c_ptr, c_int, fpx_conv_config
       type(c_ptr), value :: h
@@ -690,11 +719,14 @@ contains
   ! host fetches them with flexgpu_get_flux or lets flexgpu_fluxoutput write the file; without it iflux = 1 is refused.
   ! device_partavg = .true.: with ipout = 3 the engine keeps the interval averages of partpos_average.f90 itself (in
   ! flexgpu_step) and flexgpu_partoutput_average writes their file; without it ipout = 3 is refused.
+  ! device_initcond = .true.: with linit_cond = 1 or 2 (backward runs) the engine sums init_cond of initial_cond_calc.f90 itself
+  ! (in flexgpu_step and flexgpu_initcond_finish); the host fetches it with flexgpu_get_initcond or lets
+  ! flexgpu_initial_cond_output write the files; without it linit_cond >= 1 is refused.
   subroutine flexgpu_init(ierr, device, nmaxpart, compute_real_bytes, rng_mode, seed, defer_height, particle_base, &
-                          global_particles, blend_mode, device_flux, device_partavg)
+                          global_particles, blend_mode, device_flux, device_partavg, device_initcond)
     integer, intent(out) :: ierr
     integer, intent(in), optional :: device, nmaxpart, compute_real_bytes, rng_mode, blend_mode
-    logical, intent(in), optional :: defer_height, device_flux, device_partavg
+    logical, intent(in), optional :: defer_height, device_flux, device_partavg, device_initcond
     integer(c_int64_t), intent(in), optional :: seed, particle_base, global_particles
     type(fpx_config) :: cfg
     integer :: ks
@@ -738,7 +770,7 @@ contains
     cfg%ipout = ipout; cfg%iflux = iflux; cfg%linit_cond = linit_cond
     cfg%device_flux = 0; if (present(device_flux)) cfg%device_flux = merge(1, 0, device_flux)
     cfg%device_partavg = 0; if (present(device_partavg)) cfg%device_partavg = merge(1, 0, device_partavg)
-    cfg%reserved = 0
+    cfg%device_initcond = 0; if (present(device_initcond)) cfg%device_initcond = merge(1, 0, device_initcond)
     ierr = fpx_create(flexgpu_handle, cfg)
     if (ierr /= 0) return
     ! point_mod xmass(numpoint,maxspec), npart(numpoint): indexed by npoint(j) in the particle loop
@@ -1055,6 +1087,44 @@ contains
     if (present(reduced)) red = merge(1, 0, reduced)
     ierr = fpx_fluxoutput(flexgpu_handle, int(itime, c_int32_t), f, path(2)(1:length(2)) // c_null_char, red)
   end subroutine flexgpu_fluxoutput
+
+  ! Replaces the loop `do j=1,numpart; if (linit_cond.ge.1) call initial_cond_calc(itime,j)` (timemanager.f90:735-737; engine
+  ! created with device_initcond = .true.): every particle still alive contributes to the device's init_cond.
+  subroutine flexgpu_initcond_finish(itime, ierr)
+    integer, intent(in) :: itime
+    integer, intent(out) :: ierr
+    ierr = fpx_initcond_finish(flexgpu_handle, int(itime, c_int32_t))
+  end subroutine flexgpu_initcond_finish
+
+  ! The device's init_cond overwrites unc_mod's init_cond (allocated by the host's outgrid_init.f90:296 with maxspec = nspec
+  ! species), so that the host may keep calling its own initial_cond_output (or initial_cond_output_inversion,
+  ! timemanager.f90:743-745).  allreduce = .true.: the sums over all ranks, the ranks' partial sums stay.
+  subroutine flexgpu_get_initcond(clear, ierr, allreduce)
+    integer, intent(in) :: clear
+    integer, intent(out) :: ierr
+    logical, intent(in), optional :: allreduce
+    integer(c_int32_t) :: ar
+    ar = 0
+    if (present(allreduce)) ar = merge(1, 0, allreduce)
+    ierr = fpx_get_initcond(flexgpu_handle, loc_r(init_cond), ar, int(clear, c_int32_t))
+  end subroutine flexgpu_get_initcond
+
+  ! Replaces `call initial_cond_output(itime)` (timemanager.f90:745): writes path(2)//'grid_initial_'//nnn per species from the
+  ! device's grid with the host's ind_rel, rho_rel and the xmass of flexgpu_init.
+  ! reduced = .true. (MPI host, after flexgpu_get_initcond(0, ierr, allreduce=.true.)): the files hold the sums over all ranks.
+  subroutine flexgpu_initial_cond_output(itime, ierr, reduced)
+    integer, intent(in) :: itime
+    integer, intent(out) :: ierr
+    logical, intent(in), optional :: reduced
+    type(fpx_initout) :: o
+    integer(c_int32_t) :: red
+    o%struct_bytes = int(c_sizeof(o), c_int32_t); o%ind_rel = ind_rel
+    o%rho_rel = c_null_ptr
+    if (ind_rel == 1) o%rho_rel = loc_r(rho_rel)
+    red = 0
+    if (present(reduced)) red = merge(1, 0, reduced)
+    ierr = fpx_initial_cond_output(flexgpu_handle, int(itime, c_int32_t), o, path(2)(1:length(2)) // c_null_char, red)
+  end subroutine flexgpu_initial_cond_output
 
   ! one time slot of the com_mod fields (slot = the value found in memind(k))
   subroutine flexgpu_upload_fields(slot, ierr)

@@ -1133,3 +1133,66 @@ def partavg_case():
         c[f"itra1_{iv}"] = itra1
     c["ncalls"] = ncall
     return c
+
+
+# --------------------------------------------------------------------------
+# initial_cond_calc / initial_cond_output (tests/golden/ic_r*.npz)
+# --------------------------------------------------------------------------
+IC_VARIANTS = ("mass", "mixing", "points", "domainfill")
+
+
+def initcond_case(variant="mass"):
+    """Prepared particles for the reference's initial_cond_calc and initial_cond_output, from integer hashes and IEEE-exact
+    operations only, so that the tests regenerate the fixture's inputs bit for bit.  Met grid 20 x 12 x 10 (dx 1, dy 0.5
+    from (-10, 40)), memind = (2, 1): the second wind field in memory is the physical slot 1.  Output grid 12 x 8 x 3 of
+    quarter cells with its origin at met (7.5, 4.0): xl = 4 xt - 30, yl = 4 yt - 16, exact in both real kinds.  300
+    particles over xl -1.2 .. 12.9, yl -0.7 .. 8.6 -- outside on all four sides -- with a band xl 5.1 .. 6.9 left empty so
+    that the rows of the grid have holes; heights up to 2000 m (the top output level is 1500 m); every seventh particle is
+    not due (itra1 differs from itime).  The first four particles sit at xl = 0.5 and at yl = 0.5 exactly: the uniform
+    kernel then looks at column -1 / row -1 (the only neighbours outside the grid it can ever look at: beyond
+    numxgrid - 1.5 the direct attribution takes over).
+      mass        linit_cond = 1, one species, one release index
+      mixing      linit_cond = 2, the same particles
+      points      linit_cond = 1, ioutputforeachrelease = 1, three release points, two species, ind_rel = 1 with a rho_rel
+      domainfill  linit_cond = 2, mdomainfill = 1, npoint = the particle number: nrelpointer = 1 all the same"""
+    if variant not in IC_VARIANTS:
+        raise ValueError(variant)
+    nx, ny, nz, n = 20, 12, 10, 300
+    points, fill = variant == "points", variant == "domainfill"
+    nspec = 2 if points else 1
+    mps = 3 if points else 1
+    height = make_height(nz)
+    f = make_fields(nx, ny, nz, height)
+    c = dict(grid=np.array([nx, ny, nz], np.int32), geom=np.array([1.0, 0.5, -10.0, 40.0], np.float64), height=height,
+             memind=np.array([2, 1], np.int32), rho=f["rho"],
+             outgrid=np.array([12, 8, 3], np.int32), outgeom=np.array([0.25, 0.125, -2.5, 42.0], np.float64),
+             outheight=np.array([100.0, 500.0, 1500.0], np.float64), nspec=nspec, maxpointspec_act=mps,
+             ioutputforeachrelease=int(points), mdomainfill=int(fill), linit_cond=1 if variant in ("mass", "points") else 2,
+             ind_rel=int(points), itime=-10800, npart=n)
+    s = 9800 + 10 * IC_VARIANTS.index(variant if variant != "mixing" else "mass")
+    xl = -1.2 + 14.1 * _uniform01(n, s + 1)
+    band = (xl > 5.1) & (xl < 6.9)
+    xl[band] = xl[band] + 1.8
+    yl = -0.7 + 9.3 * _uniform01(n, s + 2)
+    xt = (np.floor(xl * 4096.0) / 4096.0 + 30.0) / 4.0
+    yt = (np.floor(yl * 4096.0) / 4096.0 + 16.0) / 4.0
+    zt = 2000.0 * _uniform01(n, s + 3) ** 2
+    xt[0], yt[0] = 7.625, 4.6                            # xl = 0.5: ixp = -1
+    xt[1], yt[1] = 7.625, 5.3
+    xt[2], yt[2] = 8.4, 4.125                            # yl = 0.5: jyp = -1
+    xt[3], yt[3] = 9.7, 4.125
+    zt[:4] = (40.0, 300.0, 900.0, 60.0)
+    h = _splitmix64(n, s + 4)
+    m = np.zeros((nspec, n), np.float64)
+    m[0] = (1.0 + (h % np.uint64(1000)).astype(np.float64)) / 3000.0
+    if nspec > 1:
+        m[1] = (1.0 + ((h >> np.uint64(16)) % np.uint64(1000)).astype(np.float64)) / 7000.0
+    itra1 = np.full(n, c["itime"], np.int32)
+    idx = np.arange(n)
+    itra1[idx % 7 == 5] = c["itime"] + 900
+    itra1[idx % 31 == 11] = DEAD
+    c["xtra1"], c["ytra1"], c["ztra1"], c["xmass1"], c["itra1"] = xt, yt, zt, m, itra1
+    c["npoint"] = (idx + 1).astype(np.int32) if fill else (1 + ((h >> np.uint64(48)) % np.uint64(mps)).astype(np.int64)).astype(np.int32)
+    c["xmass"] = np.array([[1.0, 2.5, 0.75], [0.5, 4.0, 1.25]][:nspec], np.float64)[:, :mps]      # [nspec][numpoint]
+    c["rho_rel"] = np.array([1.125, 0.9375, 1.0625][:mps], np.float64)
+    return c

@@ -124,7 +124,8 @@ typedef struct {
   /* Diagnostics inside the particle loop that the engine does NOT compute (out of scope): the host passes
    * its COMMAND switches and fpx_create refuses (FPX_ERR_UNSUPPORTED) a run that would need them, instead of dropping their
    * output silently: ipout = 3 (partpos_average, timemanager.f90:617; unless device_partavg = 1, below), iflux = 1 (calcfluxes, :623; unless device_flux = 1,
-   * below), linit_cond >= 1 (initial_cond_calc, :631,702).  Zero-initialised fields mean "not requested". */
+   * below), linit_cond >= 1 (initial_cond_calc, :631,702; unless device_initcond = 1, below).  Zero-initialised fields mean
+   * "not requested". */
   int32_t ipout, iflux, linit_cond;
   /* Gross mass fluxes on the device (calcfluxes.f90, timemanager.f90:623): iflux = 1 is accepted only together with
    * device_flux = 1, by which the host declares that it fetches the flux grid from the engine (fpx_get_flux, fpx_fluxoutput);
@@ -138,7 +139,14 @@ typedef struct {
    * ipout != 3 is FPX_ERR_ARG.  With it fpx_create allocates fifteen values per storage space and fpx_step runs one more
    * kernel after the particle is moved; without it nothing is allocated and the step launches what it always did. */
   int32_t device_partavg;
-  int32_t reserved[1];
+  /* Sensitivity to initial conditions of a backward run on the device (initial_cond_calc.f90:37-197, timemanager.f90:631,702,
+   * 735-737): linit_cond = 1 (mass unit) or 2 (mass mixing ratio unit) is accepted only together with device_initcond = 1, by
+   * which the host declares that it fetches init_cond from the engine (fpx_initcond_finish, fpx_get_initcond,
+   * fpx_initial_cond_output); linit_cond >= 1 alone is refused as above; device_initcond = 1 with any other linit_cond or with
+   * ldirect = 1 (readcommand.f90:349 zeroes linit_cond for forward runs) is FPX_ERR_ARG, as is any other value of the
+   * switch.  With it fpx_outgrid_init allocates init_cond and fpx_step runs one more kernel behind the particle's epilogue;
+   * without it nothing is allocated and the step launches what it always did. */
+  int32_t device_initcond;
 } fpx_config;
 
 /* One time slot of the met fields the path gathers from (com_mod.f90:355-371,
@@ -693,6 +701,45 @@ int fpx_partoutput_average(fpx_handle h, int32_t itime, const char *path_or_pref
 /* cumulative device time (ms) of k_partavg, by events of its own, and the number of steps that ran it since the last
  * reset.  fpx_kernel_times keeps its meaning: the kernel lies outside its intervals. */
 int fpx_partavg_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset);
+/* ---- sensitivity to initial conditions (fpx_config.device_initcond = 1, linit_cond = 1 or 2; backward runs) -------
+ * fpx_step then does what `if (linit_cond.ge.1) call initial_cond_calc(itime,j)` (timemanager.f90:631) and
+ * `call initial_cond_calc(itime+lsynctime,j)` (timemanager.f90:702; the routine: initial_cond_calc.f90:37-197) do for a
+ * particle the step terminates: one that left the domain (nstop > 1) contributes with the position advance left and the
+ * masses the epilogue has not touched, one that exceeded lage(nageclass) with the masses after deposition and decay, one
+ * terminated for small mass (:681) not at all.  A contribution is xmass1/rhoi -- rhoi the air density of the second wind
+ * field in memory at the particle for linit_cond = 1, 1 for linit_cond = 2 -- spread over up to four cells by the uniform
+ * kernel, summed into the device's init_cond(0:numxgrid-1,0:numygrid-1,numzgrid,nspec,maxpointspec_act) of unc_mod
+ * (allocated as outgrid_init.f90:296 does, with nspec for maxspec; host_real_bytes per value; zero after fpx_outgrid_init).
+ * mdomainfill of fpx_config and ioutputforeachrelease of fpx_outgrid decide the release index (initial_cond_calc.f90:99-103).
+ * All arithmetic is in the host's real kind, in the reference's order of operations; the order of the sums is not the
+ * reference's.  Contributing nothing, where the reference would index out of bounds: a release index outside
+ * 1..maxpointspec_act, a position that is not finite, and for linit_cond = 1 a position outside the met grid or at or above
+ * height(nz).  A step without fpx_outgrid_init returns FPX_ERR_STATE.
+ * fpx_initcond_finish replaces the loop `do j=1,numpart; if (linit_cond.ge.1) call initial_cond_calc(itime,j)`
+ * (timemanager.f90:735-737) after the last step: every particle with itra1 = itime contributes.  FPX_ERR_STATE without the
+ * switch or without an output grid. */
+int fpx_initcond_finish(fpx_handle h, int32_t itime);
+/* copies init_cond to the host (may be NULL), with the semantics of fpx_get_flux: allreduce != 0 sums over the communicator
+ * into a receive buffer of its own and copies out from that (the rank's partial sums stay); clear != 0 zeroes the rank's
+ * grid afterwards (the reference never does: init_cond accumulates over the run).  FPX_ERR_STATE before fpx_outgrid_init. */
+int fpx_get_initcond(fpx_handle h, void *init_cond, int32_t allreduce, int32_t clear);
+/* Replaces `call initial_cond_output(itime)` (timemanager.f90:745; the routine: initial_cond_output.f90:58-130): per species
+ * a file "<prefix>grid_initial_<nnn>" (prefix = path(2)(1:length(2))), Fortran unformatted sequential, byte-identical to the
+ * reference's for the same grid: itime, then per kp the eight empty records of the dummy deposition fields (:83-92) and the
+ * sparse index and value records of init_cond with the alternating sign (:96-123), smallnum = tiny of the host's real kind,
+ * the values sp_fact*init_cond/xmass(kp,ks)*fact_recept in that order of operations; xmass is the table of
+ * fpx_set_release_points (FPX_ERR_STATE without it).  The grid is not zeroed (the reference does not zero it).
+ * reduced = 1: write the sums over all ranks that a preceding fpx_get_initcond(h, NULL, 1, 0) left in the receive buffer.
+ * Out of scope: linversionout = 1 (initial_cond_output_inversion, timemanager.f90:743). */
+typedef struct {
+  int32_t struct_bytes;
+  int32_t ind_rel;       /* com_mod ind_rel: 1 = fact_recept is rho_rel(kp), else 1 (initial_cond_output.f90:67-71) */
+  const void *rho_rel;   /* point_mod rho_rel(maxpointspec_act), host_real_bytes per value; may be NULL when ind_rel != 1 */
+} fpx_initout;
+int fpx_initial_cond_output(fpx_handle h, int32_t itime, const fpx_initout *o, const char *prefix, int32_t reduced);
+/* cumulative device time (ms) of k_initcond and k_initcond_finish, by events of their own, and the number of steps that ran
+ * k_initcond since the last reset.  fpx_kernel_times keeps its meaning: the kernels lie outside its intervals. */
+int fpx_initcond_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset);
 /* Communicator for the grid reduction, one of:
  * (a) RCCL: rank 0 obtains an id (128 bytes), the host distributes it (MPI_Bcast / torch.distributed / a file), every
  *     rank calls fpx_comm_init; the reduction then runs device to device on the handle's stream. */
