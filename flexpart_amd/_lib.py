@@ -119,6 +119,11 @@ class FpxInitout(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("ind_rel", C.c_int32), ("rho_rel", C.c_void_p)]
 
 
+class FpxPlumetrajCfg(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("numpoint", C.c_int32), ("ncluster", C.c_int32), ("reserved", C.c_int32),
+                ("ireleasestart", C.c_void_p), ("ireleaseend", C.c_void_p)]
+
+
 class FpxDiagFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oro", "pv", "qv", "tt")]
 
@@ -201,7 +206,7 @@ SYMBOLS = [
     "fpx_rng_get_table", "fpx_upload_particles", "fpx_download_particles", "fpx_set_numpart", "fpx_set_release_points", "fpx_set_release_heights", "fpx_release_init", "fpx_releaseparticles", "fpx_split_particles", "fpx_redist_plan", "fpx_redist_bytes", "fpx_redist_pack", "fpx_redist_unpack",
     "fpx_step", "fpx_step_async", "fpx_sync", "fpx_counters", "fpx_kernel_time", "fpx_kernel_times", "fpx_sort_particles",
     "fpx_seed_particles", "fpx_stream", "fpx_outgrid_init", "fpx_set_output_times", "fpx_conccalc",
-    "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_initcond_finish", "fpx_get_initcond", "fpx_initial_cond_output", "fpx_initcond_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
+    "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_initcond_finish", "fpx_get_initcond", "fpx_initial_cond_output", "fpx_initcond_time", "fpx_plumetraj_init", "fpx_plumetraj", "fpx_get_plumetraj", "fpx_plumetraj_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
     "fpx_wetdepo", "fpx_get_wetgrid", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_cbl_probe", "fpx_find_level_probe",
     "fpx_outgrid_nest_init", "fpx_get_grids_nest", "fpx_receptors_init", "fpx_get_receptors", "fpx_upload_wet_nest_fields",
     "fpx_verttransform_ecmwf", "fpx_verttransform_nest", "fpx_verttransform_time", "fpx_calcpar", "fpx_calcpar_time", "fpx_getvdep_init", "fpx_getvdep", "fpx_getvdep_time", "fpx_calcpv_init", "fpx_get_pvh", "fpx_calcpv_time", "fpx_upload_diag_fields", "fpx_partoutput", "fpx_partoutput_time", "fpx_readpartpositions", "fpx_concoutput",
@@ -309,6 +314,10 @@ def load():
     lib.fpx_get_initcond.argtypes = [vp, vp, C.c_int32, C.c_int32]
     lib.fpx_initial_cond_output.argtypes = [vp, C.c_int32, C.POINTER(FpxInitout), C.c_char_p, C.c_int32]
     lib.fpx_initcond_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
+    lib.fpx_plumetraj_init.argtypes = [vp, C.POINTER(FpxPlumetrajCfg)]
+    lib.fpx_plumetraj.argtypes = [vp, C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]
+    lib.fpx_get_plumetraj.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.c_int32]
+    lib.fpx_plumetraj_time.argtypes = [vp, C.POINTER(C.c_double)]
     lib.fpx_comm_unique_id.argtypes = [vp, C.c_int32]
     lib.fpx_comm_init.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32]
     lib.fpx_nests_init.argtypes = [vp, C.POINTER(FpxNests)]

@@ -29,6 +29,7 @@
 #include "fpx_calcfluxes.hpp"
 #include "fpx_partavg.hpp"
 #include "fpx_initcond.hpp"
+#include "fpx_plumetraj.hpp"
 #include "fpx_convect.hpp"
 #include "fpx_rng_host.hpp"
 #include "fpx_host_res.hpp"
@@ -2073,6 +2074,10 @@ struct EngineBase {
   virtual int get_initcond(void *init_cond, int allreduce, int clear) = 0;
   virtual int initial_cond_output(int itime, const fpx_initout *o, const char *prefix, int reduced) = 0;
   virtual int initcond_time(double *ms, long long *launches, int reset) = 0;
+  virtual int plumetraj_init(const fpx_plumetraj_cfg *c) = 0;
+  virtual int plumetraj(int itime, const char *path, int32_t *nrecords) = 0;
+  virtual int get_plumetraj(int max_records, int32_t *jpoint, int32_t *npart, int32_t *iterations, int32_t *numb, void *values, int ld) = 0;
+  virtual double plumetraj_ms() = 0;
   virtual int count_particles(int64_t *local, int64_t *total, int allreduce) = 0;
   virtual int lane_stats(uint64_t *out, int n, int reset) = 0;
   virtual int set_option(const char *name, const char *value) = 0;
@@ -5046,6 +5051,8 @@ struct Engine : EngineBase {
       else { const int d[] = {FPX_SLICE_SCHEDULE}; *value = (int64_t)(sizeof(d) / sizeof(d[0])); }
     } else if (n == "pbl_grid") *value = pbl_grid;
     else if (n == "pbl_blocks_per_cu") *value = pbl_per_cu;
+    else if (n == "plumetraj_sweep_us") *value = (int64_t)(pt_sweep_ms * 1000.);   // of the last fpx_plumetraj: its passes of clustering.f90:78-162
+    else if (n == "plumetraj_sweeps") { int m = 0; for (int v : pt_rec_it) m = std::max(m, v); *value = m; }
     else if (n == "pbl_list_length") {   // the four class counts k_list_counts left for the first launch of the last step
       unsigned int hc[4] = {0u, 0u, 0u, 0u};
       if (step_counter > 0) {
@@ -5961,6 +5968,184 @@ struct Engine : EngineBase {
     return cfg.host_real_bytes == 4 ? initial_cond_output_t<float>(itime, o, prefix, src) : initial_cond_output_t<double>(itime, o, prefix, src);
   }
 
+  // ---- plume trajectories (fpx_plumetraj.hpp; iout = 4, 5) --------------------------------------------------------
+  // Nothing here exists before fpx_plumetraj_init: the buffers are grow-only Scratch members a call reserves.
+  bool pt_on = false;
+  int pt_numpoint = 0, pt_K = 0;
+  std::vector<int32_t> pt_start, pt_end;                 // ireleasestart, ireleaseend
+  Scratch pt_keys[2], pt_vals[2], pt_tmp, pt_active, pt_bounds, pt_segs, pt_chunkseg, pt_part, pt_zl, pt_ncl, pt_pending;
+  double pt_last_ms = 0, pt_sweep_ms = 0;
+  // the records of the last call
+  std::vector<int32_t> pt_rec_j, pt_rec_n, pt_rec_it, pt_rec_numb;
+  std::vector<double> pt_rec_val;                        // [record][14 + 5 ncluster], exact copies of the values in H
+  int plumetraj_init(const fpx_plumetraj_cfg *c) override {
+    if (!c || c->struct_bytes != (int32_t)sizeof(fpx_plumetraj_cfg)) return fail(FPX_ERR_ARG, "plumetraj_init: null or fpx_plumetraj_cfg size mismatch (ABI)");
+    if (c->numpoint < 1 || !c->ireleasestart || !c->ireleaseend) return fail(FPX_ERR_ARG, "plumetraj_init: numpoint >= 1 and both release-time arrays are needed");
+    if (c->ncluster < 1 || c->ncluster > FPX_MAXCLUSTER) return fail(FPX_ERR_ARG, "plumetraj_init: ncluster must be 1 .. FPX_MAXCLUSTER");
+    pt_numpoint = c->numpoint; pt_K = c->ncluster;
+    pt_start.assign(c->ireleasestart, c->ireleasestart + c->numpoint);
+    pt_end.assign(c->ireleaseend, c->ireleaseend + c->numpoint);
+    pt_rec_j.clear(); pt_rec_n.clear(); pt_rec_it.clear(); pt_rec_numb.clear(); pt_rec_val.clear();
+    pt_on = true;
+    return 0;
+  }
+  template <typename H, int KM>
+  int plumetraj_kernels(int itime, int nseg, int nchunk, bool any_clustered, const Events<4> &ev) {
+    const int K = pt_K;
+    const pt::Geo<H> G{(H)cfg.xlon0, (H)cfg.ylat0, (H)cfg.dx, (H)cfg.dy};
+    pt::Seg<H> *segs = pt_segs.as<pt::Seg<H>>();
+    const int *chunk_seg = pt_chunkseg.as<int>();
+    const unsigned int *list = pt_vals[1].as<unsigned int>();
+    unsigned char *ncl = pt_ncl.as<unsigned char>();
+    double *part = pt_part.as<double>();
+    int *pending = pt_pending.as<int>();
+    HIPCHK(hipMemsetAsync(pending, 0, (pt::kMaxSweeps + 1) * sizeof(int), stream));
+    HIPCHK(hipEventRecord(ev[1], stream));
+    if (any_clustered) {
+      pt::k_pt_seed<R, H><<<(nseg * K + 63) / 64, 64, 0, stream>>>(P, G, segs, nseg, K, list);
+      HIPCHK(hipGetLastError());
+      for (int l = 1; l <= pt::kMaxSweeps; l++) {        // clustering.f90:78
+        pt::k_pt_sweep<R, H, KM><<<nchunk, pt::kThreads, 0, stream>>>(P, G, segs, chunk_seg, list, ncl, part, K);
+        pt::k_pt_sweep_seg<H, KM><<<nseg, 64, 0, stream>>>(segs, part, K, l, pending);
+        HIPCHK(hipGetLastError());
+        if (l == 1) continue;                            // no release point leaves the loop in its first pass
+        int more = 0;
+        HIPCHK(hipMemcpyAsync(&more, pending + l, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (!more) break;
+      }
+    }
+    HIPCHK(hipEventRecord(ev[2], stream));
+    pt::k_pt_final1<R, H, KM><<<nchunk, pt::kThreads, 0, stream>>>(V, P, diag_args<H>(), segs, chunk_seg, list, ncl, pt_zl.as<H>(), part, itime);
+    pt::k_pt_final1_seg<H, KM><<<nseg, 64, 0, stream>>>(segs, part, K);
+    pt::k_pt_final2<R, H><<<nchunk, pt::kThreads, 0, stream>>>(P, G, segs, chunk_seg, list, ncl, pt_zl.as<H>(), part);
+    pt::k_pt_final2_seg<H><<<nseg, 64, 0, stream>>>(segs, part, K);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  template <typename H>
+  int plumetraj_t(int itime, const char *path, int32_t *nrecords) {
+    const long long n = numpart;
+    const int np = pt_numpoint, K = pt_K;
+    pt_rec_j.clear(); pt_rec_n.clear(); pt_rec_it.clear(); pt_rec_numb.clear(); pt_rec_val.clear();
+    pt_last_ms = 0; pt_sweep_ms = 0;
+    std::vector<unsigned char> active((size_t)np);
+    bool any = false;
+    for (int j = 0; j < np; j++) {                        // plumetraj.f90:65
+      const long long d = (long long)pt_start[j] - itime;
+      active[j] = (d < 0 ? -d : d) <= (long long)cfg.lage_last;
+      any = any || active[j];
+    }
+    std::vector<pt::Seg<H>> segs((size_t)np);
+    if (n > 0 && any) {
+      hipError_t e = hipSuccess;
+      for (int k = 0; k < 2 && e == hipSuccess; k++) {
+        e = pt_keys[k].reserve((size_t)n * 4, stream);
+        if (e == hipSuccess) e = pt_vals[k].reserve((size_t)n * 4, stream);
+      }
+      if (e == hipSuccess) e = pt_active.reserve((size_t)np, stream);
+      if (e == hipSuccess) e = pt_bounds.reserve(((size_t)np + 1) * 4, stream);
+      if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("plumetraj: ") + hipGetErrorString(e));
+      Events<4> ev;
+      HIPCHK(ev.create());
+      HIPCHK(hipEventRecord(ev[0], stream));
+      HIPCHK(hipMemcpyAsync(pt_active.as(), active.data(), (size_t)np, hipMemcpyHostToDevice, stream));
+      unsigned int *k0 = pt_keys[0].as<unsigned int>(), *k1 = pt_keys[1].as<unsigned int>();
+      unsigned int *v0 = pt_vals[0].as<unsigned int>(), *v1 = pt_vals[1].as<unsigned int>();
+      HIPCHK(hipMemsetAsync(k0, 0xFF, (size_t)n * 4, stream));   // a particle number no storage space holds: no member
+      HIPCHK(hipMemsetAsync(v0, 0, (size_t)n * 4, stream));
+      pt::k_pt_key<R><<<(int)((n + 255) / 256), 256, 0, stream>>>(V, P, n, itime, np, pt_active.as<unsigned char>(), k0, v0);
+      HIPCHK(hipGetLastError());
+      int bits = 1;
+      while (bits < 32 && (1ll << bits) <= (long long)np) bits++;
+      size_t tb = 0;
+      HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, k0, k1, v0, v1, (size_t)n, 0u, (unsigned int)bits, stream));
+      if ((e = pt_tmp.reserve(tb, stream)) != hipSuccess) return fail(FPX_ERR_NOMEM, "plumetraj: sort storage");
+      HIPCHK(rocprim::radix_sort_pairs(pt_tmp.as(), tb, k0, k1, v0, v1, (size_t)n, 0u, (unsigned int)bits, stream));
+      pt::k_pt_bounds<<<(np + 1 + 255) / 256, 256, 0, stream>>>(k1, n, np, pt_bounds.as<int>());
+      HIPCHK(hipGetLastError());
+      std::vector<int> start((size_t)np + 1);
+      HIPCHK(hipMemcpyAsync(start.data(), pt_bounds.as(), ((size_t)np + 1) * 4, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      std::vector<int> chunk_seg;
+      bool any_clustered = false;
+      for (int j = 0; j < np; j++) {
+        pt::Seg<H> &S = segs[j];
+        memset(&S, 0, sizeof(S));
+        S.begin = start[j]; S.n = start[j + 1] - start[j];
+        S.chunk0 = (int)chunk_seg.size(); S.nchunk = (S.n + pt::kChunk - 1) / pt::kChunk;
+        S.clustered = S.n >= K && S.n > 0;
+        S.frozen = !S.clustered;
+        any_clustered = any_clustered || S.clustered;
+        chunk_seg.insert(chunk_seg.end(), (size_t)S.nchunk, j);
+      }
+      const int nchunk = (int)chunk_seg.size(), members = start[np];
+      if (nchunk > 0) {
+        if ((e = pt_segs.reserve(segs.size() * sizeof(pt::Seg<H>), stream)) != hipSuccess || (e = pt_chunkseg.reserve((size_t)nchunk * 4, stream)) != hipSuccess ||
+            (e = pt_part.reserve((size_t)nchunk * pt::kMaxQ * 8, stream)) != hipSuccess || (e = pt_zl.reserve((size_t)members * sizeof(H), stream)) != hipSuccess ||
+            (e = pt_ncl.reserve((size_t)members, stream)) != hipSuccess || (e = pt_pending.reserve((pt::kMaxSweeps + 1) * sizeof(int), stream)) != hipSuccess)
+          return fail(FPX_ERR_NOMEM, std::string("plumetraj: ") + hipGetErrorString(e));
+        HIPCHK(hipMemcpyAsync(pt_segs.as(), segs.data(), segs.size() * sizeof(pt::Seg<H>), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(pt_chunkseg.as(), chunk_seg.data(), (size_t)nchunk * 4, hipMemcpyHostToDevice, stream));
+        const int rc = K <= 5 ? plumetraj_kernels<H, 5>(itime, np, nchunk, any_clustered, ev) : plumetraj_kernels<H, pt::kMaxCluster>(itime, np, nchunk, any_clustered, ev);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(segs.data(), pt_segs.as(), segs.size() * sizeof(pt::Seg<H>), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipEventRecord(ev[3], stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[3]) == hipSuccess) pt_last_ms = ms;
+        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) pt_sweep_ms = ms;
+      }
+    }
+    std::string text;
+    for (int j = 0; j < np; j++) {
+      const pt::Seg<H> &S = segs[j];
+      if (!active[j] || S.n <= 0) continue;               // plumetraj.f90:183
+      pt_rec_j.push_back(j + 1); pt_rec_n.push_back(S.n); pt_rec_it.push_back(S.iterations);
+      for (int k = 0; k < K; k++) pt_rec_numb.push_back(S.clustered ? S.numb[k] : 0);
+      for (int k = 0; k < 14 + 5 * K; k++) pt_rec_val.push_back((double)S.val[k]);
+      if (path) text += pt::pt_record<H>(j + 1, (int)(itime - (pt_start[j] + pt_end[j]) / 2), S.val);
+    }
+    if (path) {
+      FILE *fh = fopen(path, "ab");
+      if (!fh) return fail(FPX_ERR_ARG, std::string("plumetraj: cannot open ") + path);
+      FileCloser closer(fh);
+      bool ok = fwrite(text.data(), 1, text.size(), fh) == text.size();
+      ok = (closer.close() == 0) && ok;
+      if (!ok) return fail(FPX_ERR_ARG, std::string("plumetraj: write error on ") + path);
+    }
+    if (nrecords) *nrecords = (int32_t)pt_rec_j.size();
+    return 0;
+  }
+  int plumetraj(int itime, const char *path, int32_t *nrecords) override {
+    if (!pt_on) return fail(FPX_ERR_STATE, "plumetraj: fpx_plumetraj_init first");
+    if (comm_ranks > 1) return fail(FPX_ERR_UNSUPPORTED, "plumetraj: a communicator of several ranks -- the seeds and the sums of a release point span the ranks");
+    if (path && pt_K != 5) return fail(FPX_ERR_ARG, "plumetraj: the record's format has five clusters (plumetraj.f90:218-219); a path needs ncluster = 5");
+    if (!height_set || !window_set || !slot_loaded[0] || !slot_loaded[1]) return fail(FPX_ERR_STATE, "plumetraj: height, both field slots and the wind-time window must be set first");
+    if (!diag_have[DG_ORO] || !diag_have[DG_PV] || !diag_have[DG_PV + 1] || !diag_have[DG_TROPO] || !diag_have[DG_TROPO + 1])
+      return fail(FPX_ERR_STATE, "plumetraj: oro, pv (fpx_upload_diag_fields or fpx_verttransform_ecmwf) and tropopause of both slots are needed");
+    if (numpart > 0x7fffffffll) return fail(FPX_ERR_UNSUPPORTED, "plumetraj: more than 2^31 - 1 storage spaces in use");
+    return cfg.host_real_bytes == 4 ? plumetraj_t<float>(itime, path, nrecords) : plumetraj_t<double>(itime, path, nrecords);
+  }
+  int get_plumetraj(int max_records, int32_t *jpoint, int32_t *npart, int32_t *iterations, int32_t *numb, void *values, int ld) override {
+    if (!pt_on) return fail(FPX_ERR_STATE, "get_plumetraj: fpx_plumetraj_init first");
+    const int nr = (int)pt_rec_j.size(), K = pt_K, nv = 14 + 5 * K;
+    if (max_records < nr) return fail(FPX_ERR_ARG, "get_plumetraj: max_records is smaller than the number of records of the last call");
+    if (values && ld < nv) return fail(FPX_ERR_ARG, "get_plumetraj: ld must be at least 14 + 5 ncluster");
+    for (int r = 0; r < nr; r++) {
+      if (jpoint) jpoint[r] = pt_rec_j[r];
+      if (npart) npart[r] = pt_rec_n[r];
+      if (iterations) iterations[r] = pt_rec_it[r];
+      for (int k = 0; numb && k < K; k++) numb[(size_t)r * K + k] = pt_rec_numb[(size_t)r * K + k];
+      for (int k = 0; values && k < nv; k++) {
+        if (cfg.host_real_bytes == 4) ((float *)values)[(size_t)r * ld + k] = (float)pt_rec_val[(size_t)r * nv + k];
+        else ((double *)values)[(size_t)r * ld + k] = pt_rec_val[(size_t)r * nv + k];
+      }
+    }
+    return 0;
+  }
+  double plumetraj_ms() override { return pt_last_ms; }
+
   // ---- nested grids --------------------------------------------------------------
   int nest_nxmaxn = 0, nest_nymaxn = 0;
   bool nest_loaded[kMaxNests][2] = {};
@@ -6391,6 +6576,13 @@ int fpx_partavg_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset)
 int fpx_initcond_finish(fpx_handle h, int32_t itime) { FPX_GUARD(h); return h->impl->initcond_finish(itime); }
 int fpx_get_initcond(fpx_handle h, void *init_cond, int32_t allreduce, int32_t clear) { FPX_GUARD(h); return h->impl->get_initcond(init_cond, allreduce, clear); }
 int fpx_initial_cond_output(fpx_handle h, int32_t itime, const fpx_initout *o, const char *prefix, int32_t reduced) { FPX_GUARD(h); return h->impl->initial_cond_output(itime, o, prefix, reduced); }
+int fpx_plumetraj_init(fpx_handle h, const fpx_plumetraj_cfg *c) { FPX_GUARD(h); return h->impl->plumetraj_init(c); }
+int fpx_plumetraj(fpx_handle h, int32_t itime, const char *path, int32_t *nrecords) { FPX_GUARD(h); return h->impl->plumetraj(itime, path, nrecords); }
+int fpx_get_plumetraj(fpx_handle h, int32_t max_records, int32_t *jpoint, int32_t *npart, int32_t *iterations, int32_t *numb, void *values, int32_t ld) {
+  FPX_GUARD(h);
+  return h->impl->get_plumetraj(max_records, jpoint, npart, iterations, numb, values, ld);
+}
+int fpx_plumetraj_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_plumetraj_time: null"); *ms = h->impl->plumetraj_ms(); return FPX_OK; }
 int fpx_initcond_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset) {
   FPX_GUARD(h);
   long long l = 0;

@@ -586,6 +586,43 @@ class Engine:
         check(self.lib.fpx_initcond_time(self.h, C.byref(ms), C.byref(n), int(reset)), "fpx_initcond_time")
         return ms.value, int(n.value)
 
+    def plumetraj_init(self, ireleasestart, ireleaseend, ncluster=5):
+        """fpx_plumetraj_init: the release times of point_mod (seconds, one per release point) and par_mod's ncluster."""
+        from ._lib import FpxPlumetrajCfg
+        a = np.ascontiguousarray(ireleasestart, np.int32)
+        b = np.ascontiguousarray(ireleaseend, np.int32)
+        if a.ndim != 1 or a.shape != b.shape:
+            raise ValueError("plumetraj_init: ireleasestart and ireleaseend [numpoint]")
+        c = FpxPlumetrajCfg(C.sizeof(FpxPlumetrajCfg), a.size, int(ncluster), 0, a.ctypes.data, b.ctypes.data)
+        check(self.lib.fpx_plumetraj_init(self.h, C.byref(c)), "fpx_plumetraj_init")
+        self.pt_numpoint, self.pt_ncluster = int(a.size), int(ncluster)
+
+    def plumetraj(self, itime=None, path=None):
+        """fpx_plumetraj: `call plumetraj(itime)` on the device; with `path` the records are appended to that file.
+        Returns the number of records (release points with particles)."""
+        n = C.c_int32(0)
+        check(self.lib.fpx_plumetraj(self.h, int(self.itime if itime is None else itime), None if path is None else str(path).encode(), C.byref(n)),
+              "fpx_plumetraj")
+        return int(n.value)
+
+    def get_plumetraj(self):
+        """fpx_get_plumetraj: the records of the last call as a dict of jpoint, npart, iterations [records],
+        numb [records][ncluster] (int32) and values [records][14 + 5 ncluster] (the host's real kind, the order of the write
+        statement plumetraj.f90:218-225 from xcenter on)."""
+        nr, k = self.pt_numpoint, self.pt_ncluster
+        out = dict(jpoint=np.zeros(nr, np.int32), npart=np.zeros(nr, np.int32), iterations=np.zeros(nr, np.int32),
+                   numb=np.zeros((nr, k), np.int32), values=np.zeros((nr, 14 + 5 * k), self.hreal))
+        check(self.lib.fpx_get_plumetraj(self.h, nr, _vp(out["jpoint"]), _vp(out["npart"]), _vp(out["iterations"]), _vp(out["numb"]),
+                                         _vp(out["values"]), 14 + 5 * k), "fpx_get_plumetraj")
+        used = int(np.count_nonzero(out["jpoint"]))          # jpoint is 1-based: the records the call filled
+        return {key: v[:used] for key, v in out.items()}
+
+    def plumetraj_time(self):
+        """fpx_plumetraj_time: device ms of the last fpx_plumetraj."""
+        ms = C.c_double(0)
+        check(self.lib.fpx_plumetraj_time(self.h, C.byref(ms)), "fpx_plumetraj_time")
+        return ms.value
+
     PARTAVG_SUMS = ("cartx", "carty", "cartz", "z", "topo", "pv", "qv", "tt", "uu", "vv", "rho", "tro", "hmix", "energy")
 
     def get_partavg(self, first=0, count=None):

@@ -37,6 +37,7 @@ module flexgpu_mod
             flexgpu_upload_diag_fields, flexgpu_partoutput, flexgpu_readpartpositions, &
             flexgpu_partoutput_average, flexgpu_get_partavg, &
             flexgpu_initcond_finish, flexgpu_get_initcond, flexgpu_initial_cond_output, &
+            flexgpu_plumetraj_init, flexgpu_plumetraj, &
             flexgpu_concoutput, flexgpu_abi_sizes, flexgpu_comm_init_host, flexgpu_count_particles, flexgpu_set_option, flexgpu_get_info, &
             flexgpu_release_init, flexgpu_releaseparticles, flexgpu_split_particles, flexgpu_calcpar, &
             flexgpu_getvdep_init, flexgpu_getvdep, &
@@ -133,6 +134,11 @@ module flexgpu_mod
     integer(c_int32_t) :: struct_bytes, ind_rel
     type(c_ptr) :: rho_rel
   end type fpx_initout
+
+  type, bind(C) :: fpx_plumetraj_cfg
+    integer(c_int32_t) :: struct_bytes, numpoint, ncluster, reserved
+    type(c_ptr) :: ireleasestart, ireleaseend
+  end type fpx_plumetraj_cfg
 
   integer, parameter :: FPX_MAXNESTS = 4
   type, bind(C) :: fpx_nests
@@ -374,6 +380,18 @@ module flexgpu_mod
       type(fpx_initout), intent(in) :: o
       character(kind=c_char), intent(in) :: prefix(*)
     end function fpx_initial_cond_output
+    integer(c_int) function fpx_plumetraj_init(h, c) bind(C, name='fpx_plumetraj_init')
+      import :: c_ptr, c_int, fpx_plumetraj_cfg
+      type(c_ptr), value :: h
+      type(fpx_plumetraj_cfg), intent(in) :: c
+    end function fpx_plumetraj_init
+    integer(c_int) function fpx_plumetraj(h, itime, path, nrecords) bind(C, name='fpx_plumetraj')
+      import :: c_ptr, c_int, c_int32_t, c_char
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: itime
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int32_t), intent(out) :: nrecords
+    end function fpx_plumetraj
     integer(c_int) function fpx_initcond_time(h, ms, launches, reset) bind(C, name='fpx_initcond_time')
       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
       type(c_ptr), value :: h
@@ -1125,6 +1143,29 @@ contains
     if (present(reduced)) red = merge(1, 0, reduced)
     ierr = fpx_initial_cond_output(flexgpu_handle, int(itime, c_int32_t), o, path(2)(1:length(2)) // c_null_char, red)
   end subroutine flexgpu_initial_cond_output
+
+  ! After readreleases (iout = 4 or 5): the release times of point_mod and par_mod's ncluster for flexgpu_plumetraj.
+  subroutine flexgpu_plumetraj_init(ierr)
+    integer, intent(out) :: ierr
+    type(fpx_plumetraj_cfg) :: c
+    c%struct_bytes = int(c_sizeof(c), c_int32_t); c%numpoint = numpoint; c%ncluster = ncluster; c%reserved = 0
+    c%ireleasestart = loc_i(ireleasestart); c%ireleaseend = loc_i(ireleaseend)
+    ierr = fpx_plumetraj_init(flexgpu_handle, c)
+  end subroutine flexgpu_plumetraj_init
+
+  ! Replaces `call plumetraj(itime)` (timemanager.f90:438): the records are appended to path(2)//'trajectories.txt', the file
+  ! openouttraj.f90 has opened on unitouttraj and written the header to.  The engine writes through a stream of its own, so
+  ! the host flushes its unit before the call (`flush(unitouttraj)`; a host that opens the file with position='append' for
+  ! every write of its own may as well close it) and writes nothing to it in between.
+  subroutine flexgpu_plumetraj(itime, ierr, nrecords)
+    integer, intent(in) :: itime
+    integer, intent(out) :: ierr
+    integer, intent(out), optional :: nrecords
+    integer(c_int32_t) :: nrec
+    flush(unitouttraj)
+    ierr = fpx_plumetraj(flexgpu_handle, int(itime, c_int32_t), path(2)(1:length(2)) // 'trajectories.txt' // c_null_char, nrec)
+    if (present(nrecords)) nrecords = nrec
+  end subroutine flexgpu_plumetraj
 
   ! one time slot of the com_mod fields (slot = the value found in memind(k))
   subroutine flexgpu_upload_fields(slot, ierr)

@@ -1196,3 +1196,119 @@ def initcond_case(variant="mass"):
     c["xmass"] = np.array([[1.0, 2.5, 0.75], [0.5, 4.0, 1.25]][:nspec], np.float64)[:, :mps]      # [nspec][numpoint]
     c["rho_rel"] = np.array([1.125, 0.9375, 1.0625][:mps], np.float64)
     return c
+
+
+PT_VARIANTS = ("blobs", "diffuse")
+PT_NCLUSTER = 5
+# per release point: live particles (multiples of 5 where the point is clustered), ireleasestart, ireleaseend
+PT_POINTS = ((2380, -1800, 0), (300, -60000, -58200), (0, -900, 1), (3, -3600, -1801), (5, 0, 900), (600, -7200, -3600), (600, -5400, -2700))
+PT_CENTRES = ((-8.0, 3.5), (6.0, -5.0), (0.0, 0.0), (11.0, 6.0), (0.0, 0.0), (7.0, 4.5), (0.0, 0.0))   # lon, lat of the points
+PT_OFFSETS = ((-5.0, -3.0), (-5.0, 3.0), (0.0, 0.0), (5.0, -3.0), (5.0, 3.0))                           # of a point's five groups
+
+
+def _pt_lattice(nxl, nyl, step, last, hollow):
+    """A symmetric nxl x nyl lattice of offsets (degrees) around (0, 0), row by row, without the offsets closer than `hollow`
+    to the centre in both directions, and with the offset `last` ('centre', kept then, or 'corner') moved to the end: the
+    k-means takes its seeds from the ends of the fifths of a point's list."""
+    ox = (np.arange(nxl) - (nxl - 1) / 2.0) * step
+    oy = (np.arange(nyl) - (nyl - 1) / 2.0) * step
+    gx, gy = np.meshgrid(ox, oy)
+    gx, gy = gx.ravel(), gy.ravel()
+    centre = (gx == 0.0) & (gy == 0.0)
+    keep = ~((np.abs(gx) < hollow) & (np.abs(gy) < hollow)) | (centre & (last == "centre"))
+    gx, gy = gx[keep], gy[keep]
+    k = int(np.nonzero((gx == 0.0) & (gy == 0.0))[0][0]) if last == "centre" else gx.size - 1
+    order = np.r_[np.delete(np.arange(gx.size), k), k]
+    return gx[order], gy[order]
+
+
+def plumetraj_case(variant="blobs"):
+    """A scenario for plumetraj.f90 / clustering.f90 (iout = 4, 5): small(nx=40, ny=24, nz=30) as a limited-area grid of one
+    degree from (-20, -12), so that both hemispheres are present, with oro, pv, qv of add_partoutput_fields, the PV scaled
+    to pvu and signed like the latitude (|PV| passes 2 near 6 km).  Every seventh particle is terminated; the live ones
+    belong to seven release points (PT_POINTS) and six to none (npoint 0 and 8).  Point 1 has 2380 particles (three chunks
+    of 1024), point 2 is too old at itime = 0 (lage = 20000 s), point 3 has no particle, point 4 three (fewer than
+    clusters), point 5 exactly five, points 6 and 7 600 each.  The particles of the points lie interleaved in storage; the
+    order within a point is what counts.  Heights cycle through 50 m .. 14 km: both sides of hmix, of the tropopause and of
+    |PV| = 2.
+      blobs    every point's particles lie on symmetric lattices of 0.05 degrees around five group centres several degrees
+               apart, stored group by group in equal numbers, each group ending with a corner of its lattice: the five seeds
+               fall into five groups, pass 2 moves the centroids to the groups' centres and pass 3 repeats pass 2 bit for
+               bit (the ratio of the exit test is exactly 0, whatever the order of the sums).  The lattices are hollow: no
+               particle lies within 0.2 degrees of its group's centre, i.e. near the edge of distance2's box around a
+               centroid that carries a summation error.
+      diffuse  one wide cloud of several degrees per point: many passes, bisectors through the cloud.  Point 6 ends its fourth
+               and fifth fifth with one and the same position: two equal seeds, cluster 5 is empty in pass 1.  Point 7 (605
+               particles here) keeps lattices, each ending with its centre: the seeds are the groups' centres and the loop
+               is left in pass 2.
+    In both, point 5's five particles lie within a degree of (0, 0), where longitude and latitude in radians are small and the
+    relative errors of sin, cos and atan2 leave them accurate to 1e-8 rad even in r4: each is its own seed and its own centroid
+    (distance2's box in every pass: rms = 0, the exit test is 0/0 and never true, 100 passes), and the centre of mass falls on the
+    middle one (distance's 0.03 degree box)."""
+    if variant not in PT_VARIANTS:
+        raise ValueError(variant)
+    points = [list(p) for p in PT_POINTS]
+    if variant == "diffuse":
+        points[6][0] = 605
+    nlive = sum(p[0] for p in points) + 6
+    n = (7 * nlive + 5) // 6
+    assert n - (n + 6) // 7 == nlive
+    sc = small(n=n, nx=40, ny=24, nz=30, nsteps=1, global_grid=False, seed=770)
+    sc["geom"] = np.array([1.0, 1.0, -20.0, -12.0], np.float64)
+    add_partoutput_fields(sc, itime=0)
+    ny = 24
+    lat = -12.0 + np.arange(ny, dtype=np.float64)
+    sign = np.where(lat > 0.0, 1.0, -1.0)[None, None, :, None]
+    sc["pv"] = np.abs(sc["pv"]) * 2.0e6 * sign
+    numpoint = len(points)
+    sc["numpoint"] = numpoint
+    sc["xmass"] = np.ones((1, numpoint), np.float64)
+    sc["npart_rel"] = np.full(numpoint, 1000, np.int32)
+    sc["lage"] = np.array([20000], np.int32)
+    sc["ireleasestart"] = np.array([p[1] for p in points], np.int32)
+    sc["ireleaseend"] = np.array([p[2] for p in points], np.int32)
+    # labels of the live particles: the multiset of the points, interleaved by a hash, the order within a point kept
+    lab = np.concatenate([np.full(p[0], j + 1, np.int64) for j, p in enumerate(points)] + [np.array([0, 8, 0, 8, 0, 8], np.int64)])
+    lab = lab[np.argsort(_splitmix64(nlive, 0x9717), kind="stable")]
+    lon = np.zeros(nlive); la = np.zeros(nlive)
+    u1, u2 = _uniform01(nlive, 0x9718), _uniform01(nlive, 0x9719)
+    for j, (cnt, _, _) in enumerate(points):
+        who = np.nonzero(lab == j + 1)[0]
+        if cnt == 0:
+            continue
+        cx, cy = PT_CENTRES[j]
+        lattice = cnt >= 5 and j != 1 and (variant == "blobs" or j == 6)
+        if not lattice:
+            # a wide cloud: +-4 degrees by +-2.5 (the small points: their first particles)
+            lon[who] = cx + 8.0 * (u1[who] - 0.5); la[who] = cy + 5.0 * (u2[who] - 0.5)
+            if j == 5:                                  # point 6: the fourth and the fifth seed are one and the same position
+                lon[who[cnt - 1]] = lon[who[4 * cnt // 5 - 1]]; la[who[cnt - 1]] = la[who[4 * cnt // 5 - 1]]
+            continue
+        m = cnt // 5
+        if cnt == 5:                                    # point 5: (0, 0) and four positions less than a degree from it
+            lon[who] = np.array([-0.8, -0.8, 0.0, 0.8, 0.8]); la[who] = np.array([-0.5, 0.5, 0.0, -0.5, 0.5])
+            continue
+        elif variant == "diffuse":
+            gx, gy = _pt_lattice(11, 11, 0.05, "centre", 0.0)
+        elif m == 476:
+            gx, gy = _pt_lattice(21, 25, 0.05, "corner", 0.2)
+        else:
+            gx, gy = _pt_lattice(13, 13, 0.05, "corner", 0.2)
+        assert gx.size == m
+        for g in range(5):
+            ox, oy = PT_OFFSETS[g]
+            w = who[g * m:(g + 1) * m]
+            lon[w] = cx + ox + gx; la[w] = cy + oy + gy
+    lon[lab == 0] = -15.0; la[lab == 0] = 8.0
+    lon[lab == 8] = 15.0; la[lab == 8] = -8.0
+    live = np.arange(n) % 7 != 0
+    x = np.asarray(sc["xtra1"]).copy(); y = np.asarray(sc["ytra1"]).copy()
+    x[live] = lon + 20.0; y[live] = la + 12.0
+    npoint = (1 + np.arange(n) % numpoint).astype(np.int32)
+    npoint[live] = lab
+    zs = np.array([50.0, 300.0, 900.0, 2500.0, 6000.0, 9000.0, 11500.0, 14000.0])
+    z = zs[(_splitmix64(n, 0x971A) % np.uint64(8)).astype(np.int64)] * (0.75 + 0.5 * _uniform01(n, 0x971B))
+    itra1 = np.where(live, 0, DEAD).astype(np.int32)
+    sc.update(xtra1=x, ytra1=y, ztra1=z, npoint=npoint, itra1=itra1, itime=0)
+    assert x[live].min() > 0.5 and x[live].max() < 38.5 and y[live].min() > 0.5 and y[live].max() < 22.5
+    return sc

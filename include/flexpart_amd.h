@@ -740,6 +740,40 @@ int fpx_initial_cond_output(fpx_handle h, int32_t itime, const fpx_initout *o, c
 /* cumulative device time (ms) of k_initcond and k_initcond_finish, by events of their own, and the number of steps that ran
  * k_initcond since the last reset.  fpx_kernel_times keeps its meaning: the kernels lie outside its intervals. */
 int fpx_initcond_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset);
+/* ---- plume trajectories and their clustering (iout = 4, 5) ---------------------------------------------------------
+ * fpx_plumetraj replaces `call plumetraj(itime)` (timemanager.f90:438; the routine: plumetraj.f90:56-230 with
+ * clustering.f90, centerofmass.f90, distance.f90, distance2.f90 and mean of mean_mod) without moving a particle to the
+ * host.  A release point j takes part when abs(ireleasestart(j) - itime) <= lage(nageclass) (fpx_config.lage_last); its
+ * particles are those with itra1 = itime and npoint = j exactly (an npoint outside 1..numpoint belongs to no point), taken
+ * in the order of their particle numbers, which is the order of the reference's loop and does not change with
+ * fpx_sort_particles.  All arithmetic is in the host's real kind in the reference's order of operations; the sums are
+ * formed in a fixed order of their own (fp64 partials per 1024 particles, rounded once), so a call gives the same bits
+ * every time.  A release point with fewer particles than clusters (clustering.f90:52 returns at once): rms, zrms and the
+ * cluster columns are zero where the reference prints what its locals held.  No member of any release point: a particle
+ * outside the met grid or with a position that is not finite.
+ * Needs what fpx_partoutput needs (wind-time window, both slots, oro, pv and tropopause of both slots), else
+ * FPX_ERR_STATE; FPX_ERR_STATE before fpx_plumetraj_init; FPX_ERR_UNSUPPORTED on a handle whose communicator has more than
+ * one rank.  A handle that never calls fpx_plumetraj_init allocates nothing for it. */
+#define FPX_MAXCLUSTER 8
+typedef struct {
+  int32_t struct_bytes, numpoint;
+  int32_t ncluster;                 /* par_mod.f90:263 (shipped: 5); 1..FPX_MAXCLUSTER */
+  int32_t reserved;
+  const int32_t *ireleasestart, *ireleaseend;   /* (numpoint) point_mod.f90:8-9, copied */
+} fpx_plumetraj_cfg;
+int fpx_plumetraj_init(fpx_handle h, const fpx_plumetraj_cfg *c);
+/* path != NULL: append the records, as the format plumetraj.f90:218-219 writes them, to that file (the host has written
+ * the header, openouttraj.f90, and has closed or flushed its own unit); needs ncluster = 5, else FPX_ERR_ARG.
+ * *nrecords (may be NULL): the release points with n > 0. */
+int fpx_plumetraj(fpx_handle h, int32_t itime, const char *path, int32_t *nrecords);
+/* the records of the last call, in release-point order: jpoint[r], npart[r], iterations[r] (passes of the loop
+ * clustering.f90:78-162), numb[r*ncluster+k] (any may be NULL) and values(ld, r), ld >= 14 + 5*ncluster, host_real_bytes per
+ * value, in the order of the write statement plumetraj.f90:218-225 from xcenter on.  max_records smaller than the number
+ * of records, or ld too small: FPX_ERR_ARG. */
+int fpx_get_plumetraj(fpx_handle h, int32_t max_records, int32_t *jpoint, int32_t *npart, int32_t *iterations,
+                      int32_t *numb, void *values, int32_t ld);
+/* device time (ms) of the last fpx_plumetraj, by events of its own */
+int fpx_plumetraj_time(fpx_handle h, double *ms);
 /* Communicator for the grid reduction, one of:
  * (a) RCCL: rank 0 obtains an id (128 bytes), the host distributes it (MPI_Bcast / torch.distributed / a file), every
  *     rank calls fpx_comm_init; the reduction then runs device to device on the handle's stream. */
