@@ -124,6 +124,18 @@ class FpxPlumetrajCfg(C.Structure):
                 ("ireleasestart", C.c_void_p), ("ireleaseend", C.c_void_p)]
 
 
+class FpxDomainfillCfg(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("nx_we", C.c_int32 * 2), ("ny_sn", C.c_int32 * 2), ("gdomainfill", C.c_int32),
+                ("maxcolumn", C.c_int32), ("nclassunc", C.c_int32), ("itsplit", C.c_int32), ("ipout", C.c_int32),
+                ("xmassperparticle", C.c_double), ("numcolumn_we", C.c_void_p), ("numcolumn_sn", C.c_void_p),
+                ("zcolumn_we", C.c_void_p), ("zcolumn_sn", C.c_void_p), ("acc_mass_we", C.c_void_p), ("acc_mass_sn", C.c_void_p)]
+
+
+class FpxDomainfillStats(C.Structure):
+    _fields_ = [("n_terminated", C.c_int64), ("n_released", C.c_int64), ("n_rejected", C.c_int64), ("numactiveparticles", C.c_int64),
+                ("accmasst", C.c_double)]
+
+
 class FpxDiagFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("oro", "pv", "qv", "tt")]
 
@@ -206,7 +218,7 @@ SYMBOLS = [
     "fpx_rng_get_table", "fpx_upload_particles", "fpx_download_particles", "fpx_set_numpart", "fpx_set_release_points", "fpx_set_release_heights", "fpx_release_init", "fpx_releaseparticles", "fpx_split_particles", "fpx_redist_plan", "fpx_redist_bytes", "fpx_redist_pack", "fpx_redist_unpack",
     "fpx_step", "fpx_step_async", "fpx_sync", "fpx_counters", "fpx_kernel_time", "fpx_kernel_times", "fpx_sort_particles",
     "fpx_seed_particles", "fpx_stream", "fpx_outgrid_init", "fpx_set_output_times", "fpx_conccalc",
-    "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_initcond_finish", "fpx_get_initcond", "fpx_initial_cond_output", "fpx_initcond_time", "fpx_plumetraj_init", "fpx_plumetraj", "fpx_get_plumetraj", "fpx_plumetraj_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
+    "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_initcond_finish", "fpx_get_initcond", "fpx_initial_cond_output", "fpx_initcond_time", "fpx_plumetraj_init", "fpx_plumetraj", "fpx_get_plumetraj", "fpx_plumetraj_time", "fpx_domainfill_init", "fpx_boundcond_domainfill", "fpx_get_domainfill_acc", "fpx_set_domainfill_acc", "fpx_boundcond_output", "fpx_domainfill_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
     "fpx_wetdepo", "fpx_get_wetgrid", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_cbl_probe", "fpx_find_level_probe",
     "fpx_outgrid_nest_init", "fpx_get_grids_nest", "fpx_receptors_init", "fpx_get_receptors", "fpx_upload_wet_nest_fields",
     "fpx_verttransform_ecmwf", "fpx_verttransform_nest", "fpx_verttransform_time", "fpx_calcpar", "fpx_calcpar_time", "fpx_getvdep_init", "fpx_getvdep", "fpx_getvdep_time", "fpx_calcpv_init", "fpx_get_pvh", "fpx_calcpv_time", "fpx_upload_diag_fields", "fpx_partoutput", "fpx_partoutput_time", "fpx_readpartpositions", "fpx_concoutput",
@@ -318,6 +330,12 @@ def load():
     lib.fpx_plumetraj.argtypes = [vp, C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]
     lib.fpx_get_plumetraj.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.c_int32]
     lib.fpx_plumetraj_time.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.fpx_domainfill_init.argtypes = [vp, C.POINTER(FpxDomainfillCfg)]
+    lib.fpx_boundcond_domainfill.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(FpxDomainfillStats)]
+    lib.fpx_get_domainfill_acc.argtypes = [vp, vp, vp]
+    lib.fpx_set_domainfill_acc.argtypes = [vp, vp, vp]
+    lib.fpx_boundcond_output.argtypes = [vp, C.c_char_p]
+    lib.fpx_domainfill_time.argtypes = [vp, C.POINTER(C.c_double)]
     lib.fpx_comm_unique_id.argtypes = [vp, C.c_int32]
     lib.fpx_comm_init.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32]
     lib.fpx_nests_init.argtypes = [vp, C.POINTER(FpxNests)]

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <rccl/rccl.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_reduce.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -30,6 +31,7 @@
 #include "fpx_partavg.hpp"
 #include "fpx_initcond.hpp"
 #include "fpx_plumetraj.hpp"
+#include "fpx_domainfill.hpp"
 #include "fpx_convect.hpp"
 #include "fpx_rng_host.hpp"
 #include "fpx_host_res.hpp"
@@ -2078,6 +2080,11 @@ struct EngineBase {
   virtual int plumetraj(int itime, const char *path, int32_t *nrecords) = 0;
   virtual int get_plumetraj(int max_records, int32_t *jpoint, int32_t *npart, int32_t *iterations, int32_t *numb, void *values, int ld) = 0;
   virtual double plumetraj_ms() = 0;
+  virtual int domainfill_init(const fpx_domainfill_cfg *c) = 0;
+  virtual int boundcond_domainfill(int itime, int64_t *numpart, int32_t *numparticlecount, fpx_domainfill_stats *out) = 0;
+  virtual int domainfill_acc(void *we, void *sn, const void *we_in, const void *sn_in) = 0;
+  virtual int boundcond_output(const char *path) = 0;
+  virtual double domainfill_ms() = 0;
   virtual int count_particles(int64_t *local, int64_t *total, int allreduce) = 0;
   virtual int lane_stats(uint64_t *out, int n, int reset) = 0;
   virtual int set_option(const char *name, const char *value) = 0;
@@ -4523,6 +4530,7 @@ struct Engine : EngineBase {
 
   int checkpoint_write(const char *path, int itime, int numparticlecount) override {
     if (!path) return fail(FPX_ERR_ARG, "checkpoint_write: path is required");
+    if (dfl_on) return fail(FPX_ERR_UNSUPPORTED, "checkpoint_write: the checkpoint does not carry acc_mass_we / acc_mass_sn of fpx_domainfill_init (boundcond.bin does: fpx_boundcond_output)");
     FILE *fh = fopen(path, "wb");
     if (!fh) return fail(FPX_ERR_ARG, std::string("checkpoint_write: cannot open ") + path);
     FileCloser closer(fh);
@@ -5052,6 +5060,11 @@ struct Engine : EngineBase {
     } else if (n == "pbl_grid") *value = pbl_grid;
     else if (n == "pbl_blocks_per_cu") *value = pbl_per_cu;
     else if (n == "plumetraj_sweep_us") *value = (int64_t)(pt_sweep_ms * 1000.);   // of the last fpx_plumetraj: its passes of clustering.f90:78-162
+    else if (n == "domainfill_flux_us") *value = (int64_t)(dfl_stage_ms[0] * 1000.);
+    else if (n == "domainfill_stage1_us") *value = (int64_t)(dfl_stage_ms[1] * 1000.);
+    else if (n == "domainfill_cand_us") *value = (int64_t)(dfl_stage_ms[2] * 1000.);
+    else if (n == "domainfill_place_us") *value = (int64_t)(dfl_stage_ms[3] * 1000.);
+    else if (n == "domainfill_candidates") *value = dfl_last_ncand;
     else if (n == "plumetraj_sweeps") { int m = 0; for (int v : pt_rec_it) m = std::max(m, v); *value = m; }
     else if (n == "pbl_list_length") {   // the four class counts k_list_counts left for the first launch of the last step
       unsigned int hc[4] = {0u, 0u, 0u, 0u};
@@ -6146,6 +6159,285 @@ struct Engine : EngineBase {
   }
   double plumetraj_ms() override { return pt_last_ms; }
 
+  // ---- boundary conditions of a domain-filling run (fpx_domainfill.hpp; boundcond_domainfill.f90) -----------------
+  // Nothing here exists before fpx_domainfill_init.
+  bool dfl_on = false;
+  fpx_domainfill_cfg dfl_cfg = {};
+  std::vector<int32_t> dfl_nc_we, dfl_nc_sn;             // the host's numcolumn_we, numcolumn_sn
+  std::vector<unsigned char> dfl_zc_we, dfl_zc_sn;       // the host's zcolumn_*, its bytes (boundcond.bin)
+  std::vector<df::Loc> dfl_locs;                         // the release locations in the reference's loop order
+  Scratch dfl_d_nc[2], dfl_d_zc[2], dfl_d_acc[2][2], dfl_d_locs, dfl_d_height;   // acc: [buffer][we | sn]
+  int dfl_cur = 0;                                       // the buffer that holds acc_mass_*
+  Scratch dfl_mmass, dfl_first, dfl_accv, dfl_accsum, dfl_cnt, dfl_term, dfl_uni, dfl_target, dfl_arank, dfl_tmp;
+  Scratch dfl_cx, dfl_cy, dfl_cz, dfl_cm, dfl_cn, dfl_ca;
+  Ran1 dfl_ran1 = [] { Ran1 r; r.idum = -11; return r; }();   // boundcond_domainfill.f90:48: integer :: idummy = -11 (SAVE'd)
+  double dfl_last_ms = 0, dfl_stage_ms[4] = {0, 0, 0, 0};
+  long long dfl_last_ncand = 0;
+  size_t dfl_acc_bytes(int side) const { return (size_t)2 * (side == 0 ? cfg.nymax : cfg.nxmax) * dfl_cfg.maxcolumn * cfg.host_real_bytes; }
+
+  int domainfill_init(const fpx_domainfill_cfg *c) override {
+    if (!c || c->struct_bytes != (int32_t)sizeof(fpx_domainfill_cfg)) return fail(FPX_ERR_ARG, "domainfill_init: null or fpx_domainfill_cfg size mismatch (ABI)");
+    if (cfg.mdomainfill != 1 && cfg.mdomainfill != 2) return fail(FPX_ERR_ARG, "domainfill_init: the run is not domain-filling (mdomainfill = 0)");
+    if (comm_ranks > 1) return fail(FPX_ERR_UNSUPPORTED, "domainfill_init: a communicator of several ranks -- the vacancies and the serial stream span the ranks");
+    if (!height_set) return fail(FPX_ERR_STATE, "domainfill_init: fpx_set_height first");
+    if (!c->numcolumn_we || !c->numcolumn_sn || !c->zcolumn_we || !c->zcolumn_sn || !c->acc_mass_we || !c->acc_mass_sn)
+      return fail(FPX_ERR_ARG, "domainfill_init: numcolumn_*, zcolumn_* and acc_mass_* are required");
+    if (c->maxcolumn < 2) return fail(FPX_ERR_ARG, "domainfill_init: maxcolumn >= 2 (the first height of a column reads the second)");
+    if (c->nclassunc < 1) return fail(FPX_ERR_ARG, "domainfill_init: nclassunc >= 1");
+    if (!(c->xmassperparticle > 0.) || !std::isfinite(c->xmassperparticle)) return fail(FPX_ERR_ARG, "domainfill_init: xmassperparticle must be positive");
+    if (c->nx_we[0] < 0 || c->nx_we[0] > c->nx_we[1] || c->nx_we[1] > cfg.nx - 2 || c->ny_sn[0] < 0 || c->ny_sn[0] > c->ny_sn[1] || c->ny_sn[1] > cfg.ny - 2)
+      return fail(FPX_ERR_ARG, "domainfill_init: nx_we must lie in 0 .. nx-2 and ny_sn in 0 .. ny-2, ascending");
+    const int nymax = cfg.nymax, nxmax = cfg.nxmax, mc = c->maxcolumn, hb = cfg.host_real_bytes;
+    auto rd = [&](const void *p, size_t i) -> double { return hb == 4 ? (double)((const float *)p)[i] : ((const double *)p)[i]; };
+    std::vector<df::Loc> locs;
+    const double top = height_host[cfg.nz - 1];
+    for (int side = 0; side < 2; side++) {
+      const int lo = side == 0 ? c->ny_sn[0] : c->nx_we[0], hi = side == 0 ? c->ny_sn[1] : c->nx_we[1], nrow = side == 0 ? nymax : nxmax;
+      const int32_t *nc = side == 0 ? c->numcolumn_we : c->numcolumn_sn;
+      const void *zc = side == 0 ? c->zcolumn_we : c->zcolumn_sn;
+      for (int row = lo; row <= hi; row++)
+        for (int k = 0; k < 2; k++) {
+          const int n = nc[k + 2 * row];
+          if (n < 0 || n > mc) return fail(FPX_ERR_ARG, "domainfill_init: a column with a negative number of heights or more than maxcolumn");
+          if (n == 2) return fail(FPX_ERR_ARG, "domainfill_init: a column of exactly two release heights (boundcond_domainfill.f90:117 reads zcolumn(.., 0), outside its array)");
+          for (int j = 1; j <= n; j++) {
+            if (!(rd(zc, (size_t)k + 2 * ((size_t)row + (size_t)nrow * (j - 1))) < top))
+              return fail(FPX_ERR_ARG, "domainfill_init: a release height reaches height(nz) (the level search :134-141 finds nothing)");
+            locs.push_back(df::Loc{side, row, k, j});
+          }
+        }
+    }
+    dfl_cfg = *c;
+    dfl_nc_we.assign(c->numcolumn_we, c->numcolumn_we + (size_t)2 * nymax);
+    dfl_nc_sn.assign(c->numcolumn_sn, c->numcolumn_sn + (size_t)2 * nxmax);
+    dfl_cfg.numcolumn_we = dfl_cfg.numcolumn_sn = nullptr;
+    dfl_cfg.zcolumn_we = dfl_cfg.zcolumn_sn = dfl_cfg.acc_mass_we = dfl_cfg.acc_mass_sn = nullptr;
+    dfl_zc_we.assign((const unsigned char *)c->zcolumn_we, (const unsigned char *)c->zcolumn_we + dfl_acc_bytes(0));
+    dfl_zc_sn.assign((const unsigned char *)c->zcolumn_sn, (const unsigned char *)c->zcolumn_sn + dfl_acc_bytes(1));
+    dfl_locs = std::move(locs);
+    hipError_t e = hipSuccess;
+    for (int side = 0; side < 2 && e == hipSuccess; side++) {
+      const std::vector<int32_t> &nc = side == 0 ? dfl_nc_we : dfl_nc_sn;
+      const std::vector<unsigned char> &zc = side == 0 ? dfl_zc_we : dfl_zc_sn;
+      const void *acc = side == 0 ? c->acc_mass_we : c->acc_mass_sn;
+      if ((e = dfl_d_nc[side].reserve(nc.size() * 4, stream)) == hipSuccess) e = hipMemcpyAsync(dfl_d_nc[side].as(), nc.data(), nc.size() * 4, hipMemcpyHostToDevice, stream);
+      if (e == hipSuccess && (e = dfl_d_zc[side].reserve(zc.size(), stream)) == hipSuccess) e = hipMemcpyAsync(dfl_d_zc[side].as(), zc.data(), zc.size(), hipMemcpyHostToDevice, stream);
+      for (int b = 0; b < 2 && e == hipSuccess; b++)
+        if ((e = dfl_d_acc[b][side].reserve(dfl_acc_bytes(side), stream)) == hipSuccess) e = hipMemcpyAsync(dfl_d_acc[b][side].as(), acc, dfl_acc_bytes(side), hipMemcpyHostToDevice, stream);
+    }
+    std::vector<unsigned char> hh((size_t)cfg.nz * hb);
+    for (int k = 0; k < cfg.nz; k++) { if (hb == 4) ((float *)hh.data())[k] = (float)height_host[k]; else ((double *)hh.data())[k] = height_host[k]; }
+    if (e == hipSuccess && (e = dfl_d_height.reserve(hh.size(), stream)) == hipSuccess) e = hipMemcpyAsync(dfl_d_height.as(), hh.data(), hh.size(), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && (e = dfl_d_locs.reserve(dfl_locs.size() * sizeof(df::Loc), stream)) == hipSuccess && !dfl_locs.empty())
+      e = hipMemcpyAsync(dfl_d_locs.as(), dfl_locs.data(), dfl_locs.size() * sizeof(df::Loc), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("domainfill_init: ") + hipGetErrorString(e));
+    dfl_cur = 0;
+    dfl_ran1 = Ran1(); dfl_ran1.idum = -11;
+    dfl_on = true;
+    return 0;
+  }
+
+  template <typename H>
+  int boundcond_t(int itime, int64_t *numpart_io, int32_t *npc_io, fpx_domainfill_stats *out) {
+    const int nloc = (int)dfl_locs.size();
+    const long long cap = P.cap;
+    const bool seq = cfg.rng_mode == FPX_RNG_TABLE_SEQ;
+    numpart = *numpart_io;
+    df::Fields<R, H> F{V.w3, V.r2, (const H *)diag_d3, dfl_d_height.as<H>(), cfg.nx, cfg.ny, cfg.nz, V.m1, V.m2};
+    df::Cfg<H> C;
+    for (int k = 0; k < 2; k++) { C.nx_we[k] = dfl_cfg.nx_we[k]; C.ny_sn[k] = dfl_cfg.ny_sn[k]; }
+    C.nxmax = cfg.nxmax; C.nymax = cfg.nymax; C.maxcolumn = dfl_cfg.maxcolumn;
+    C.mdomainfill = cfg.mdomainfill; C.nclassunc = dfl_cfg.nclassunc;
+    C.xmpp = (H)dfl_cfg.xmassperparticle;
+    C.dx = (H)cfg.dx; C.dy = (H)cfg.dy; C.ylat0 = (H)cfg.ylat0;
+    C.dt1 = (H)(itime - V.memtime0); C.dt2 = (H)(V.memtime1 - itime);      // :79-81
+    C.dtt = (H)1. / (C.dt1 + C.dt2);
+    C.lsync = (H)cfg.lsynctime;
+    for (int k = 0; k < 2; k++) {                                          // :334-335, the one libm call, in the host's kind
+      C.ylat_sn[k] = C.ylat0 + (H)C.ny_sn[k] * C.dy;
+      C.cos_sn[k] = (H)std::cos(C.ylat_sn[k] * ((H)3.14159265 / (H)180.));
+    }
+    C.nc_we = dfl_d_nc[0].as<int>(); C.nc_sn = dfl_d_nc[1].as<int>();
+    C.zc_we = dfl_d_zc[0].as<H>(); C.zc_sn = dfl_d_zc[1].as<H>();
+    const int nxt = 1 - dfl_cur;
+    hipError_t e = hipSuccess;
+    auto need = [&](Scratch &s, size_t bytes) { if (e == hipSuccess) e = s.reserve(bytes, stream); };
+    need(dfl_mmass, ((size_t)nloc + 1) * 4); need(dfl_first, ((size_t)nloc + 1) * 4); need(dfl_accv, ((size_t)nloc + 1) * 8);
+    need(dfl_accsum, 8); need(dfl_cnt, sizeof(df::Counters)); need(dfl_term, (size_t)std::max<long long>(numpart, 1) * 4);
+    size_t tb = 0, tb2 = 0;
+    if (e == hipSuccess) {
+      (void)rocprim::exclusive_scan(nullptr, tb, dfl_mmass.as<unsigned int>(), dfl_first.as<unsigned int>(), 0u, (size_t)nloc + 1, rocprim::plus<unsigned int>(), stream);
+      (void)rocprim::reduce(nullptr, tb2, dfl_accv.as<double>(), dfl_accsum.as<double>(), 0., (size_t)std::max(nloc, 1), rocprim::plus<double>(), stream);
+      tb = std::max(tb, tb2);
+    }
+    need(dfl_tmp, tb);
+    Events<5> ev;
+    if (e == hipSuccess) e = ev.create();
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("boundcond_domainfill: ") + hipGetErrorString(e));
+    df::Counters *cnt = dfl_cnt.as<df::Counters>();
+    unsigned int *mmass = dfl_mmass.as<unsigned int>(), *first = dfl_first.as<unsigned int>();
+    HIPCHK(hipEventRecord(ev[0], stream));
+    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(df::Counters), stream));
+    HIPCHK(hipMemsetAsync(dfl_accsum.as(), 0, 8, stream));
+    // ---- flux, mmass and its scan in the reference's loop order ------------------------------------------------
+    std::vector<unsigned int> h_first((size_t)nloc + 1, 0u);
+    if (nloc > 0) {
+      // the acc_mass of the entries that are no release location carry over
+      for (int side = 0; side < 2; side++)
+        HIPCHK(hipMemcpyAsync(dfl_d_acc[nxt][side].as(), dfl_d_acc[dfl_cur][side].as(), dfl_acc_bytes(side), hipMemcpyDeviceToDevice, stream));
+      HIPCHK(hipMemsetAsync(mmass + nloc, 0, 4, stream));
+      df::k_df_flux<R, H><<<(nloc + 255) / 256, 256, 0, stream>>>(F, C, dfl_d_locs.as<df::Loc>(), nloc, dfl_d_acc[dfl_cur][0].as<H>(), dfl_d_acc[dfl_cur][1].as<H>(),
+                                                                  dfl_d_acc[nxt][0].as<H>(), dfl_d_acc[nxt][1].as<H>(), mmass, dfl_accv.as<double>());
+      HIPCHK(hipGetLastError());
+      HIPCHK(rocprim::exclusive_scan(dfl_tmp.as(), tb, mmass, first, 0u, (size_t)nloc + 1, rocprim::plus<unsigned int>(), stream));
+      HIPCHK(rocprim::reduce(dfl_tmp.as(), tb2, dfl_accv.as<double>(), dfl_accsum.as<double>(), 0., (size_t)nloc, rocprim::plus<double>(), stream));
+      // the one round trip before the end: the launches and the buffers below are sized by the number of candidates
+      // (parity mode: the scan itself, which tells the host which candidate draws what)
+      if (seq) HIPCHK(hipMemcpyAsync(h_first.data(), first, ((size_t)nloc + 1) * 4, hipMemcpyDeviceToHost, stream));
+      else HIPCHK(hipMemcpyAsync(&h_first[nloc], first + nloc, 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipEventRecord(ev[1], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const unsigned int ncand = h_first[nloc];
+    if ((long long)ncand > 0x3fffffffll) return fail(FPX_ERR_NOMEM, "boundcond_domainfill: more than 2^30 particles required in one call");
+    // ---- stage 1: terminate and flag; the spaces behind numpart are vacant, so the first ncand vacancies lie in 1 .. numpart + ncand
+    const long long scan_n = std::min<long long>(cap, std::max<long long>(numpart + (long long)ncand, 1));
+    unsigned int *flags = nullptr, *rank = nullptr;
+    if (rel_scratch((size_t)scan_n, &flags, &rank)) return fail(FPX_ERR_NOMEM, "boundcond_domainfill: scratch");
+    size_t tb3 = 0, tb4 = 0;
+    (void)rocprim::exclusive_scan(nullptr, tb3, flags, rank, 0u, (size_t)scan_n, rocprim::plus<unsigned int>(), stream);
+    need(dfl_arank, ((size_t)ncand + 1) * 4); need(dfl_ca, ((size_t)ncand + 1) * 4);
+    if (e == hipSuccess) (void)rocprim::exclusive_scan(nullptr, tb4, dfl_ca.as<unsigned int>(), dfl_arank.as<unsigned int>(), 0u, (size_t)ncand + 1, rocprim::plus<unsigned int>(), stream);
+    void *tmp = nullptr;
+    if (e == hipSuccess && rel_scan_tmp(std::max(tb3, tb4), &tmp)) e = hipErrorOutOfMemory;
+    need(dfl_target, (size_t)std::max(ncand, 1u) * 4);
+    need(dfl_cx, (size_t)ncand * 8); need(dfl_cy, (size_t)ncand * 8); need(dfl_cz, (size_t)ncand * sizeof(H)); need(dfl_cm, (size_t)ncand * sizeof(H));
+    need(dfl_cn, (size_t)ncand * 4); need(dfl_uni, (size_t)3 * ncand * sizeof(H));
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("boundcond_domainfill: ") + hipGetErrorString(e));
+    const int do_x = !cfg.xglobal || dfl_cfg.nx_we[1] != cfg.nx - 2;       // :67
+    df::k_df_stage1<R><<<(int)std::min<long long>((scan_n + 255) / 256, 2048), 256, 0, stream>>>(P, slot_map(), numpart, scan_n, itime, (double)(H)dfl_cfg.nx_we[0], (double)(H)dfl_cfg.nx_we[1],
+                                                                      (double)(H)dfl_cfg.ny_sn[0], (double)(H)dfl_cfg.ny_sn[1], do_x, flags, dfl_term.as<unsigned int>(), cnt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(rocprim::exclusive_scan(tmp, tb3, flags, rank, 0u, (size_t)scan_n, rocprim::plus<unsigned int>(), stream));
+    HIPCHK(hipEventRecord(ev[2], stream));
+    // ---- candidates ------------------------------------------------------------------------------------------------
+    df::CandOut<H> O{dfl_cx.as<double>(), dfl_cy.as<double>(), dfl_cz.as<H>(), dfl_cm.as<H>(), dfl_cn.as<int>(), dfl_ca.as<unsigned int>()};
+    unsigned int *arank = dfl_arank.as<unsigned int>();
+    Ran1 stream_copy = dfl_ran1;                          // the real stream advances only when the call succeeds
+    const bool seq2 = seq && cfg.mdomainfill == 2;
+    std::vector<H> uni;
+    if (ncand > 0) {
+      if (seq) {
+        uni.resize((size_t)3 * ncand);
+        if (seq2) {                                       // the worst case of three per candidate, resolved on the device
+          for (size_t i = 0; i < uni.size(); i++) uni[i] = stream_copy.template next<H>();
+        } else {                                          // every candidate is accepted: x | y, z at an interior height, nclass
+          for (int l = 0; l < nloc; l++) {
+            const df::Loc &L = dfl_locs[l];
+            const int nc = (L.side == 0 ? dfl_nc_we : dfl_nc_sn)[L.k + 2 * L.row];
+            const bool interior = L.j != 1 && L.j != nc;
+            for (unsigned int c = h_first[l]; c < h_first[l + 1]; c++) {
+              uni[c] = stream_copy.template next<H>();
+              uni[(size_t)ncand + c] = interior ? stream_copy.template next<H>() : (H)0;
+              uni[(size_t)2 * ncand + c] = stream_copy.template next<H>();
+            }
+          }
+        }
+        HIPCHK(hipMemcpyAsync(dfl_uni.as(), uni.data(), uni.size() * sizeof(H), hipMemcpyHostToDevice, stream));
+      }
+      HIPCHK(hipMemsetAsync(O.accepted + ncand, 0, 4, stream));
+      if (seq2) df::k_df_cand_seq<R, H><<<1, 64, 0, stream>>>(F, C, dfl_d_locs.as<df::Loc>(), first, nloc, ncand, dfl_uni.as<H>(), O, cnt);
+      else df::k_df_cand<R, H><<<(int)((ncand + 255) / 256), 256, 0, stream>>>(F, C, dfl_d_locs.as<df::Loc>(), first, nloc, ncand, seq ? dfl_uni.as<H>() : (const H *)nullptr,
+                                                                            itime, (unsigned long long)cfg.seed, O);
+      HIPCHK(hipGetLastError());
+      HIPCHK(rocprim::exclusive_scan(tmp, tb4, O.accepted, arank, 0u, (size_t)ncand + 1, rocprim::plus<unsigned int>(), stream));
+      k_rel_targets<<<(int)((scan_n + kBlock - 1) / kBlock), kBlock, 0, stream>>>(flags, rank, scan_n, (long long)ncand, dfl_target.as<unsigned int>());
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(ev[3], stream));
+    // ---- decide, then commit and place (both do nothing when the call fails) ---------------------------------------
+    df::k_df_decide<<<1, 64, 0, stream>>>(flags, rank, scan_n, arank, ncand, cnt);
+    df::k_df_commit<R><<<64, 256, 0, stream>>>(P, slot_map(), dfl_term.as<unsigned int>(), cnt);
+    if (ncand > 0)
+      df::k_df_place<R, H><<<(int)((ncand + 255) / 256), 256, 0, stream>>>(P, slot_map(), O, arank, dfl_target.as<unsigned int>(), ncand, itime, (int)*npc_io, cfg.mintime,
+                                                                           cfg.ldirect, dfl_cfg.itsplit, cnt);
+    HIPCHK(hipGetLastError());
+    df::Counters hc;
+    double accsum = 0;
+    HIPCHK(hipMemcpyAsync(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&accsum, dfl_accsum.as(), 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipEventRecord(ev[4], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[4]) == hipSuccess) dfl_last_ms = ms;
+    for (int k = 0; k < 4; k++) if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) dfl_stage_ms[k] = ms;
+    dfl_last_ncand = ncand;
+    if (!hc.ok)
+      return fail(FPX_ERR_NOMEM, "boundcond_domainfill: too many particles required (boundcond_domainfill.f90:307-310); nothing was changed");
+    // ---- the call succeeded: acc_mass, numpart, numparticlecount and the stream follow ------------------------------
+    if (nloc > 0) dfl_cur = nxt;
+    if (seq) {
+      if (seq2) for (unsigned int i = 0; i < hc.consumed; i++) (void)dfl_ran1.template next<H>();
+      else dfl_ran1 = stream_copy;
+    }
+    if (hc.naccepted > 0) numpart = std::max<long long>(numpart, (long long)hc.maxpid + 1);   // :303
+    *numpart_io = numpart;
+    *npc_io = (int32_t)(*npc_io + (int32_t)hc.naccepted);
+    if (hc.naccepted > 0 || hc.nterm > 0) maybe_new = true;
+    if (out) {
+      out->n_terminated = hc.nterm; out->n_released = hc.naccepted; out->n_rejected = (int64_t)ncand - hc.naccepted;
+      out->numactiveparticles = (int64_t)hc.nactive + hc.naccepted; out->accmasst = accsum;
+    }
+    return 0;
+  }
+  int boundcond_domainfill(int itime, int64_t *numpart_io, int32_t *npc_io, fpx_domainfill_stats *out) override {
+    if (!dfl_on) return fail(FPX_ERR_STATE, "boundcond_domainfill: fpx_domainfill_init first");
+    if (comm_ranks > 1) return fail(FPX_ERR_UNSUPPORTED, "boundcond_domainfill: a communicator of several ranks -- the vacancies and the serial stream span the ranks");
+    if (!numpart_io || !npc_io) return fail(FPX_ERR_ARG, "boundcond_domainfill: numpart and numparticlecount are required");
+    if (*numpart_io < 0 || *numpart_io > P.cap) return fail(FPX_ERR_ARG, "boundcond_domainfill: numpart outside capacity");
+    if (out) memset(out, 0, sizeof(*out));
+    if (dfl_cfg.gdomainfill) return 0;                                     // :54
+    if (!height_set || !window_set || !slot_loaded[0] || !slot_loaded[1]) return fail(FPX_ERR_STATE, "boundcond_domainfill: height, both field slots and the wind-time window must be set first");
+    if (!diag_have[DG_PV] || !diag_have[DG_PV + 1]) return fail(FPX_ERR_STATE, "boundcond_domainfill: pv of both slots is needed (fpx_upload_diag_fields or fpx_verttransform_ecmwf)");
+    if (P.cap > 0x7fffffffll) return fail(FPX_ERR_UNSUPPORTED, "boundcond_domainfill: more than 2^31 - 1 storage spaces");
+    return cfg.host_real_bytes == 4 ? boundcond_t<float>(itime, numpart_io, npc_io, out) : boundcond_t<double>(itime, numpart_io, npc_io, out);
+  }
+  int domainfill_acc(void *we, void *sn, const void *we_in, const void *sn_in) override {
+    if (!dfl_on) return fail(FPX_ERR_STATE, "domainfill_acc: fpx_domainfill_init first");
+    void *out[2] = {we, sn};
+    const void *in[2] = {we_in, sn_in};
+    for (int side = 0; side < 2; side++) {
+      if (out[side]) HIPCHK(hipMemcpyAsync(out[side], dfl_d_acc[dfl_cur][side].as(), dfl_acc_bytes(side), hipMemcpyDeviceToHost, stream));
+      if (in[side]) HIPCHK(hipMemcpyAsync(dfl_d_acc[dfl_cur][side].as(), in[side], dfl_acc_bytes(side), hipMemcpyHostToDevice, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  int boundcond_output(const char *path) override {
+    if (!dfl_on) return fail(FPX_ERR_STATE, "boundcond_output: fpx_domainfill_init first");
+    if (!path) return fail(FPX_ERR_ARG, "boundcond_output: path is required");
+    std::vector<unsigned char> acc[2];
+    for (int side = 0; side < 2; side++) acc[side].resize(dfl_acc_bytes(side));
+    int rc = domainfill_acc(acc[0].data(), acc[1].data(), nullptr, nullptr);
+    if (rc) return rc;
+    const size_t total = (dfl_nc_we.size() + dfl_nc_sn.size()) * 4 + 2 * (dfl_acc_bytes(0) + dfl_acc_bytes(1));
+    if (total > 0x7fffffffull) return fail(FPX_ERR_UNSUPPORTED, "boundcond_output: the record exceeds 2 GiB (the reference's compiler would split it into subrecords)");
+    FILE *fh = fopen(path, "wb");
+    if (!fh) return fail(FPX_ERR_ARG, std::string("boundcond_output: cannot open ") + path);
+    FileCloser closer(fh);
+    const uint32_t marker = (uint32_t)total;               // :568-572, one sequential unformatted record
+    bool ok = fwrite(&marker, 4, 1, fh) == 1;
+    ok = ok && fwrite(dfl_nc_we.data(), 4, dfl_nc_we.size(), fh) == dfl_nc_we.size() && fwrite(dfl_nc_sn.data(), 4, dfl_nc_sn.size(), fh) == dfl_nc_sn.size();
+    ok = ok && fwrite(dfl_zc_we.data(), 1, dfl_zc_we.size(), fh) == dfl_zc_we.size() && fwrite(dfl_zc_sn.data(), 1, dfl_zc_sn.size(), fh) == dfl_zc_sn.size();
+    ok = ok && fwrite(acc[0].data(), 1, acc[0].size(), fh) == acc[0].size() && fwrite(acc[1].data(), 1, acc[1].size(), fh) == acc[1].size();
+    ok = ok && fwrite(&marker, 4, 1, fh) == 1;
+    ok = (closer.close() == 0) && ok;
+    if (!ok) return fail(FPX_ERR_ARG, std::string("boundcond_output: write error on ") + path);
+    return 0;
+  }
+  double domainfill_ms() override { return dfl_last_ms; }
+
   // ---- nested grids --------------------------------------------------------------
   int nest_nxmaxn = 0, nest_nymaxn = 0;
   bool nest_loaded[kMaxNests][2] = {};
@@ -6582,6 +6874,15 @@ int fpx_get_plumetraj(fpx_handle h, int32_t max_records, int32_t *jpoint, int32_
   FPX_GUARD(h);
   return h->impl->get_plumetraj(max_records, jpoint, npart, iterations, numb, values, ld);
 }
+int fpx_domainfill_init(fpx_handle h, const fpx_domainfill_cfg *c) { FPX_GUARD(h); return h->impl->domainfill_init(c); }
+int fpx_boundcond_domainfill(fpx_handle h, int32_t itime, int64_t *numpart, int32_t *numparticlecount, fpx_domainfill_stats *out) {
+  FPX_GUARD(h);
+  return h->impl->boundcond_domainfill(itime, numpart, numparticlecount, out);
+}
+int fpx_get_domainfill_acc(fpx_handle h, void *acc_mass_we, void *acc_mass_sn) { FPX_GUARD(h); return h->impl->domainfill_acc(acc_mass_we, acc_mass_sn, nullptr, nullptr); }
+int fpx_set_domainfill_acc(fpx_handle h, const void *acc_mass_we, const void *acc_mass_sn) { FPX_GUARD(h); return h->impl->domainfill_acc(nullptr, nullptr, acc_mass_we, acc_mass_sn); }
+int fpx_boundcond_output(fpx_handle h, const char *path) { FPX_GUARD(h); return h->impl->boundcond_output(path); }
+int fpx_domainfill_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_domainfill_time: null"); *ms = h->impl->domainfill_ms(); return FPX_OK; }
 int fpx_plumetraj_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_plumetraj_time: null"); *ms = h->impl->plumetraj_ms(); return FPX_OK; }
 int fpx_initcond_time(fpx_handle h, double *ms, int64_t *launches, int32_t reset) {
   FPX_GUARD(h);

@@ -623,6 +623,74 @@ class Engine:
         check(self.lib.fpx_plumetraj_time(self.h, C.byref(ms)), "fpx_plumetraj_time")
         return ms.value
 
+    # ---- boundary conditions of a domain-filling run (boundcond_domainfill.f90) ----
+    def _df_host(self, a, side, dtype):
+        """[j][row][k] (or [row][k]) compact -> the host's declared (2, 0:nymax-1 | 0:nxmax-1, maxcolumn) in memory order."""
+        a = np.asarray(a)
+        nrow = self.nymax if side == "we" else self.nxmax
+        out = np.zeros(((self.df_maxcolumn,) if a.ndim == 3 else ()) + (nrow, 2), dtype)
+        out[tuple(slice(0, n) for n in a.shape)] = a
+        return out
+
+    def domainfill_init(self, sc, maxcolumn=None, numparticlecount=None):
+        """fpx_domainfill_init from a scenario shaped like synthetic.domainfill_case(): nx_we, ny_sn, gdomainfill, nclassunc,
+        itsplit, xmassperparticle and numcolumn_*, zcolumn_*, acc_mass_* as compact [j][row][k] arrays, padded here to the
+        host's shapes with `maxcolumn` heights (default: the arrays' own)."""
+        from ._lib import FpxDomainfillCfg
+        rt = self.hreal
+        self.df_maxcolumn = int(maxcolumn or np.asarray(sc["zcolumn_we"]).shape[0])
+        keep = {}
+        for side in ("we", "sn"):
+            keep["numcolumn_" + side] = self._df_host(sc["numcolumn_" + side], side, np.int32)
+            for k in ("zcolumn_", "acc_mass_"):
+                keep[k + side] = self._df_host(np.asarray(sc[k + side]).astype(rt), side, rt)
+        c = FpxDomainfillCfg()
+        c.struct_bytes = C.sizeof(FpxDomainfillCfg)
+        for k in range(2):
+            c.nx_we[k], c.ny_sn[k] = int(sc["nx_we"][k]), int(sc["ny_sn"][k])
+        c.gdomainfill, c.maxcolumn = int(sc.get("gdomainfill", 0)), self.df_maxcolumn
+        c.nclassunc, c.itsplit, c.ipout = int(sc.get("nclassunc", 1)), int(sc.get("itsplit", 999999999)), int(sc.get("ipout_df", 0))
+        c.xmassperparticle = float(rt(sc["xmassperparticle"]))
+        for k, v in keep.items():
+            setattr(c, k, v.ctypes.data)
+        check(self.lib.fpx_domainfill_init(self.h, C.byref(c)), "fpx_domainfill_init")
+        self.numparticlecount = int(sc.get("numparticlecount", 0) if numparticlecount is None else numparticlecount)
+
+    def boundcond_domainfill(self, itime=None):
+        """fpx_boundcond_domainfill: `call boundcond_domainfill(itime, loutend)` on the device; self.n (numpart) and
+        self.numparticlecount follow.  Returns the statistics as a dict."""
+        from ._lib import FpxDomainfillStats
+        n = C.c_int64(self.n); npc = C.c_int32(self.numparticlecount); st = FpxDomainfillStats()
+        check(self.lib.fpx_boundcond_domainfill(self.h, int(self.itime if itime is None else itime), C.byref(n), C.byref(npc), C.byref(st)),
+              "fpx_boundcond_domainfill")
+        self.n, self.numparticlecount = int(n.value), int(npc.value)
+        return {k: getattr(st, k) for k, _ in FpxDomainfillStats._fields_}
+
+    def get_domainfill_acc(self, compact=None):
+        """fpx_get_domainfill_acc: (acc_mass_we, acc_mass_sn) in the host's shapes as [j][row][k]; compact = (ny, nx, heights)
+        cuts them back."""
+        rt = self.hreal
+        we = np.zeros((self.df_maxcolumn, self.nymax, 2), rt); sn = np.zeros((self.df_maxcolumn, self.nxmax, 2), rt)
+        check(self.lib.fpx_get_domainfill_acc(self.h, _vp(we), _vp(sn)), "fpx_get_domainfill_acc")
+        if compact:
+            we, sn = we[: compact[2], : compact[0]].copy(), sn[: compact[2], : compact[1]].copy()
+        return we, sn
+
+    def set_domainfill_acc(self, we, sn):
+        rt = self.hreal
+        we = self._df_host(np.asarray(we).astype(rt), "we", rt); sn = self._df_host(np.asarray(sn).astype(rt), "sn", rt)
+        check(self.lib.fpx_set_domainfill_acc(self.h, _vp(we), _vp(sn)), "fpx_set_domainfill_acc")
+
+    def boundcond_output(self, path):
+        """fpx_boundcond_output: boundcond.bin (boundcond_domainfill.f90:568-572)."""
+        check(self.lib.fpx_boundcond_output(self.h, str(path).encode()), "fpx_boundcond_output")
+
+    def domainfill_time(self):
+        """fpx_domainfill_time: device ms of the last fpx_boundcond_domainfill."""
+        ms = C.c_double(0)
+        check(self.lib.fpx_domainfill_time(self.h, C.byref(ms)), "fpx_domainfill_time")
+        return ms.value
+
     PARTAVG_SUMS = ("cartx", "carty", "cartz", "z", "topo", "pv", "qv", "tt", "uu", "vv", "rho", "tro", "hmix", "energy")
 
     def get_partavg(self, first=0, count=None):

@@ -38,6 +38,7 @@ module flexgpu_mod
             flexgpu_partoutput_average, flexgpu_get_partavg, &
             flexgpu_initcond_finish, flexgpu_get_initcond, flexgpu_initial_cond_output, &
             flexgpu_plumetraj_init, flexgpu_plumetraj, &
+            flexgpu_domainfill_init, flexgpu_boundcond_domainfill, flexgpu_boundcond_output, &
             flexgpu_concoutput, flexgpu_abi_sizes, flexgpu_comm_init_host, flexgpu_count_particles, flexgpu_set_option, flexgpu_get_info, &
             flexgpu_release_init, flexgpu_releaseparticles, flexgpu_split_particles, flexgpu_calcpar, &
             flexgpu_getvdep_init, flexgpu_getvdep, &
@@ -139,6 +140,19 @@ module flexgpu_mod
     integer(c_int32_t) :: struct_bytes, numpoint, ncluster, reserved
     type(c_ptr) :: ireleasestart, ireleaseend
   end type fpx_plumetraj_cfg
+
+  type, bind(C) :: fpx_domainfill_cfg
+    integer(c_int32_t) :: struct_bytes
+    integer(c_int32_t) :: nx_we(2), ny_sn(2)
+    integer(c_int32_t) :: gdomainfill, maxcolumn, nclassunc, itsplit, ipout
+    real(c_double) :: xmassperparticle
+    type(c_ptr) :: numcolumn_we, numcolumn_sn, zcolumn_we, zcolumn_sn, acc_mass_we, acc_mass_sn
+  end type fpx_domainfill_cfg
+
+  type, bind(C) :: fpx_domainfill_stats
+    integer(c_int64_t) :: n_terminated, n_released, n_rejected, numactiveparticles
+    real(c_double) :: accmasst
+  end type fpx_domainfill_stats
 
   integer, parameter :: FPX_MAXNESTS = 4
   type, bind(C) :: fpx_nests
@@ -392,6 +406,24 @@ module flexgpu_mod
       character(kind=c_char), intent(in) :: path(*)
       integer(c_int32_t), intent(out) :: nrecords
     end function fpx_plumetraj
+    integer(c_int) function fpx_domainfill_init(h, c) bind(C, name='fpx_domainfill_init')
+      import :: c_ptr, c_int, fpx_domainfill_cfg
+      type(c_ptr), value :: h
+      type(fpx_domainfill_cfg), intent(in) :: c
+    end function fpx_domainfill_init
+    integer(c_int) function fpx_boundcond_domainfill(h, itime, numpart, numparticlecount, stats) bind(C, name='fpx_boundcond_domainfill')
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, fpx_domainfill_stats
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: itime
+      integer(c_int64_t), intent(inout) :: numpart
+      integer(c_int32_t), intent(inout) :: numparticlecount
+      type(fpx_domainfill_stats), intent(out) :: stats
+    end function fpx_boundcond_domainfill
+    integer(c_int) function fpx_boundcond_output(h, path) bind(C, name='fpx_boundcond_output')
+      import :: c_ptr, c_int, c_char
+      type(c_ptr), value :: h
+      character(kind=c_char), intent(in) :: path(*)
+    end function fpx_boundcond_output
     integer(c_int) function fpx_initcond_time(h, ms, launches, reset) bind(C, name='fpx_initcond_time')
       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
       type(c_ptr), value :: h
@@ -1166,6 +1198,43 @@ contains
     ierr = fpx_plumetraj(flexgpu_handle, int(itime, c_int32_t), path(2)(1:length(2)) // 'trajectories.txt' // c_null_char, nrec)
     if (present(nrecords)) nrecords = nrec
   end subroutine flexgpu_plumetraj
+
+  ! mdomainfill >= 1, once, after init_domainfill (which stays with the host; its particles go up with
+  ! flexgpu_upload_particles): the boundary columns and the accumulated masses of com_mod for flexgpu_boundcond_domainfill.
+  subroutine flexgpu_domainfill_init(ierr)
+    integer, intent(out) :: ierr
+    type(fpx_domainfill_cfg) :: c
+    c%struct_bytes = int(c_sizeof(c), c_int32_t)
+    c%nx_we = nx_we; c%ny_sn = ny_sn
+    c%gdomainfill = merge(1, 0, gdomainfill); c%maxcolumn = maxcolumn
+    c%nclassunc = nclassunc; c%itsplit = itsplit; c%ipout = ipout
+    c%xmassperparticle = real(xmassperparticle, c_double)
+    c%numcolumn_we = loc_i(numcolumn_we); c%numcolumn_sn = loc_i(numcolumn_sn)
+    c%zcolumn_we = loc_r(zcolumn_we); c%zcolumn_sn = loc_r(zcolumn_sn)
+    c%acc_mass_we = loc_r(acc_mass_we); c%acc_mass_sn = loc_r(acc_mass_sn)
+    ierr = fpx_domainfill_init(flexgpu_handle, c)
+  end subroutine flexgpu_domainfill_init
+
+  ! Replaces `call boundcond_domainfill(itime, loutend)` (timemanager.f90:240): numpart and numparticlecount of com_mod
+  ! follow; where the reference writes boundcond.bin (:567-573) the routine calls flexgpu_boundcond_output.
+  subroutine flexgpu_boundcond_domainfill(itime, loutend, ierr)
+    integer, intent(in) :: itime, loutend
+    integer, intent(out) :: ierr
+    type(fpx_domainfill_stats) :: st
+    integer(c_int64_t) :: n
+    integer(c_int32_t) :: npc
+    n = int(numpart, c_int64_t); npc = int(numparticlecount, c_int32_t)
+    ierr = fpx_boundcond_domainfill(flexgpu_handle, int(itime, c_int32_t), n, npc, st)
+    if (ierr /= 0) return
+    numpart = int(n); numparticlecount = int(npc)
+    if ((ipout > 0) .and. (itime == loutend) .and. (.not. gdomainfill)) call flexgpu_boundcond_output(ierr)
+  end subroutine flexgpu_boundcond_domainfill
+
+  ! boundcond.bin in path(2), the record of boundcond_domainfill.f90:568-572
+  subroutine flexgpu_boundcond_output(ierr)
+    integer, intent(out) :: ierr
+    ierr = fpx_boundcond_output(flexgpu_handle, path(2)(1:length(2)) // 'boundcond.bin' // c_null_char)
+  end subroutine flexgpu_boundcond_output
 
   ! one time slot of the com_mod fields (slot = the value found in memind(k))
   subroutine flexgpu_upload_fields(slot, ierr)

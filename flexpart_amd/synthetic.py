@@ -1312,3 +1312,101 @@ def plumetraj_case(variant="blobs"):
     sc.update(xtra1=x, ytra1=y, ztra1=z, npoint=npoint, itra1=itra1, itime=0)
     assert x[live].min() > 0.5 and x[live].max() < 38.5 and y[live].min() > 0.5 and y[live].max() < 22.5
     return sc
+
+
+DF_VARIANTS = ("fill1", "fill2", "xglobal", "gdomainfill", "full")
+DF_CALLS = 4
+DF_NUMCOLUMN = (0, 1, 3, 4, 6)                       # never 2: boundcond_domainfill.f90:117 would read zcolumn(.., 0)
+DF_MAXCOLUMN = 6
+
+
+def domainfill_case(name="fill1"):
+    """A scenario for boundcond_domainfill.f90 (mdomainfill = 1, 2), from integer hashes and IEEE-exact operations only, so
+    that the tests regenerate the fixture's inputs bit for bit.  Met grid 12 x 10 x 8, one degree in y from -4.5: the filling
+    box nx_we = (2, 9), ny_sn = (1, 8) straddles the equator (rows -3.5 .. 3.5 degrees).  memind = (2, 1); winds of both
+    signs on every boundary; PV in pvu, signed like the latitude in most columns and against it in some, |PV| passing 2
+    near 7 km.  The columns of release heights hold 0, 1, 3, 4 or 6 heights between 400 m and 16 km (numcolumn, zcolumn and
+    acc_mass as [j][row][k], the host's (k, row, j) in memory order, compact: DF_MAXCOLUMN heights, nx | ny rows).  200
+    storage spaces, about 150 live particles (itra1 = itime), vacancies in the middle (terminated, or born later), and live
+    particles outside each of the four edges.  DF_CALLS calls at itime = 0, 900, ..: between two calls the caller moves
+    itra1 of the live particles on by lsynctime, as the particle loop would (positions stay).
+      fill1        mdomainfill = 1
+      fill2        mdomainfill = 2: candidates rejected for z <= 3000, for pv <= pvcrit, and accepted
+      xglobal      mdomainfill = 1, xglobal with nx_we = (0, nx-2): no termination in x
+      gdomainfill  the routine returns at once
+      full         mdomainfill = 1 with 10 vacancies only: the first call needs more"""
+    if name not in DF_VARIANTS:
+        raise ValueError(name)
+    nx, ny, nz, cap = 12, 10, 8, 200
+    xg = name == "xglobal"
+    height = make_height(nz, top=30000.0, lin=0.15)
+    f = make_fields(nx, ny, nz, height)
+    i = np.arange(nx, dtype=np.int64)[None, None, :]
+    j = np.arange(ny, dtype=np.int64)[None, :, None]
+    k = np.arange(nz, dtype=np.int64)[:, None, None]
+    z = height[:, None, None]
+    pv = np.empty((2, nz, ny, nx))
+    for m in range(2):
+        f["uu"][m] = 6.0 * _wave(3 * j + 2 * k + 5 * m + 0 * i, 13) + 2.0 * _wave(i + m, 7)
+        f["vv"][m] = 5.0 * _wave(2 * i + 3 * k + 4 * m + 0 * j, 11) + 1.5 * _wave(j + 2 * m, 5)
+        sign = np.where(2 * j - 9 > 0, 1.0, -1.0) * np.where((i + 2 * j) % 7 == 3, -1.0, 1.0)
+        pv[m] = sign * (0.25 + z / 4000.0) * (1.0 + 0.25 * _wave(i + 3 * j + k + 2 * m, 9))
+    sc = dict(
+        grid=np.array([nx, ny, nz], np.int32),
+        geom=np.array([360.0 / (nx - 1) if xg else 1.0, 1.0, -180.0 if xg else -6.0, -4.5], np.float64),
+        globalflags=np.array([int(xg), 0, 0], np.int32), height=height, nmixz=nmixz_from_height(height),
+        memtime=np.array([-1800, 9000], np.int32), memind=np.array([2, 1], np.int32),
+        ldirect=1, lsynctime=900, method=1, mintime=225, ctl=5.0, ifine=4, turbswitch=1, cblflag=0,
+        mdomainfill=2 if name == "fill2" else 1, lsettling=0, nspec=1, drydep=0, drydepspec=np.zeros(1, np.int32),
+        density=np.zeros(1), dquer=np.zeros(1), vsetaver=np.zeros(1), cunningham=np.ones(1), decay=np.zeros(1),
+        turbpar=np.array([50.0, 0.1, 0.16]), lage=np.array([999999999], np.int32), nsteps=1, itime0=0, itime=0,
+        par_nxmax=361, npart=cap)
+    sc.update(f)
+    sc["pv"] = pv
+    sc["qv"] = 0.0 * pv + 0.001
+    sc["oro"] = np.zeros((ny, nx))
+    sc["nx_we"] = np.array([0, nx - 2] if xg else [2, 9], np.int32)
+    sc["ny_sn"] = np.array([1, 8], np.int32)
+    sc["gdomainfill"] = int(name == "gdomainfill")
+    sc["nclassunc"], sc["itsplit"], sc["ipout_df"] = 1, 7200, 1
+    sc["xmassperparticle"] = 3.0e13 if xg else 2.5e12
+    mc = DF_MAXCOLUMN
+    for side, nrow in (("we", ny), ("sn", nx)):
+        r = np.arange(nrow, dtype=np.int64)[:, None]
+        kk = np.arange(2, dtype=np.int64)[None, :]
+        ncol = np.array(DF_NUMCOLUMN, np.int64)[(2 * r + kk + (1 if side == "sn" else 0)) % 5]
+        jj = np.arange(1, mc + 1, dtype=np.int64)[:, None, None]
+        zc = 400.0 + (jj - 1) * np.floor(15600.0 / np.maximum(ncol[None], 1)) + 16.0 * ((3 * r[None] + 5 * kk[None] + 7 * jj) % 9)
+        zc = np.where(jj <= ncol[None], zc, 0.0)
+        h = _uniform01(mc * nrow * 2, 0xD0F1 + (side == "sn")).reshape(mc, nrow, 2)
+        acc = np.where(jj <= ncol[None], np.floor(h * h * 3.6e12 / 1.0e6) * 1.0e6, 0.0)
+        sc["numcolumn_" + side], sc["zcolumn_" + side], sc["acc_mass_" + side] = ncol.astype(np.int32), zc, acc
+    # particles
+    n = cap
+    u1, u2, u3 = _uniform01(n, 0xD0F3), _uniform01(n, 0xD0F4), _uniform01(n, 0xD0F5)
+    x0, x1 = float(sc["nx_we"][0]), float(sc["nx_we"][1])
+    x = np.floor((x0 + 0.1 + (x1 - x0 - 0.2) * u1) * 1024.0) / 1024.0
+    y = np.floor((1.1 + 6.8 * u2) * 1024.0) / 1024.0
+    zt = np.floor(12000.0 * u3 * u3 * 64.0) / 64.0 + 10.0
+    idx = np.arange(n)
+    itra1 = np.zeros(n, np.int32)
+    if name == "full":
+        itra1[idx % 50 == 4] = DEAD                    # 4 vacancies, and 6 more by termination
+    else:
+        itra1[(idx % 5 == 2) & (idx > 40) & (idx < 170)] = DEAD
+        itra1[(idx % 11 == 3)] = 900                   # born later: vacant at itime = 0, live at the second call
+        itra1[190:] = DEAD
+    out = {7: (x0 - 0.25, None), 23: (x1 + 0.5, None), 57: (None, 0.75), 88: (None, 8.125), 121: (x0 - 1.0, 8.5), 150: (x1 + 0.125, 4.0),
+           13: (x0, 1.0), 14: (x1, 8.0)}              # the last two sit exactly on the edges: they stay
+    for p, (px, py) in out.items():
+        itra1[p] = 0
+        if px is not None:
+            x[p] = px
+        if py is not None:
+            y[p] = py
+    h = _splitmix64(n, 0xD0F6)
+    sc.update(xtra1=x, ytra1=y, ztra1=zt, itra1=itra1, itramem=np.where(itra1 == DEAD, 0, itra1).astype(np.int32),
+              npoint=(idx + 1).astype(np.int32), nclass=np.ones(n, np.int32), idt=np.full(n, 225, np.int32),
+              itrasplit=np.full(n, 7200, np.int32), xmass1=((1.0 + (h % np.uint64(64)).astype(np.float64)) * 1.0e10)[None, :],
+              numpart=190 if name != "full" else 200, numparticlecount=n)
+    return sc

@@ -774,6 +774,61 @@ int fpx_get_plumetraj(fpx_handle h, int32_t max_records, int32_t *jpoint, int32_
                       int32_t *numb, void *values, int32_t ld);
 /* device time (ms) of the last fpx_plumetraj, by events of its own */
 int fpx_plumetraj_time(fpx_handle h, double *ms);
+/* ---- boundary conditions of a domain-filling run (mdomainfill = 1, 2) ----------------------------------------------
+ * fpx_boundcond_domainfill replaces `call boundcond_domainfill(itime, loutend)` (timemanager.f90:240; the routine:
+ * boundcond_domainfill.f90:54-573 with com_mod.f90:135,245-252, pvcrit and ozonescale of par_mod.f90:101 and ran1,
+ * random_mod.f90:12-42), which a domain-filling run calls every time step in place of releaseparticles, without moving a
+ * particle to the host: it terminates the particles that left the filling box (:63-73), integrates the mass flux through
+ * the four lateral boundaries (:95-205, :328-439) and creates new particles where enough mass has accumulated.
+ * init_domainfill.f90 (once, at itime = 0) stays with the host, which hands its result over with fpx_upload_particles and
+ * fpx_domainfill_init.  The arrays are passed in the host's own shapes and real kind: numcolumn_we (2, 0:nymax-1),
+ * numcolumn_sn (2, 0:nxmax-1), zcolumn_we and acc_mass_we (2, 0:nymax-1, maxcolumn), zcolumn_sn and acc_mass_sn
+ * (2, 0:nxmax-1, maxcolumn), all copied.  mdomainfill, ldirect, lsynctime, mintime, the grid, xglobal and height come from
+ * the engine.
+ * FPX_ERR_ARG: mdomainfill = 0; xmassperparticle not positive; nx_we / ny_sn not ascending inside 0 .. nx-2 / 0 .. ny-2; maxcolumn < 2; a column with more
+ * heights than maxcolumn, whose top release height reaches height(nz), or of exactly two release heights (there the
+ * reference reads zcolumn(.., 0), outside its array; one height is defined and allowed).  FPX_ERR_STATE before
+ * fpx_set_height.  FPX_ERR_UNSUPPORTED on a handle whose communicator has more than one rank.  A handle that never calls
+ * fpx_domainfill_init allocates nothing for it. */
+typedef struct {
+  int32_t struct_bytes;
+  int32_t nx_we[2], ny_sn[2];       /* com_mod.f90:245 */
+  int32_t gdomainfill;              /* com_mod.f90:135 */
+  int32_t maxcolumn;                /* par_mod's, the third extent of the arrays below */
+  int32_t nclassunc, itsplit, ipout;
+  double xmassperparticle;          /* com_mod.f90:250, the value of the host's real */
+  const int32_t *numcolumn_we, *numcolumn_sn;
+  const void *zcolumn_we, *zcolumn_sn, *acc_mass_we, *acc_mass_sn;
+} fpx_domainfill_cfg;
+int fpx_domainfill_init(fpx_handle h, const fpx_domainfill_cfg *c);
+typedef struct {
+  int64_t n_terminated, n_released;
+  int64_t n_rejected;               /* candidates of mdomainfill = 2 that fail the stratosphere test (:281-282) */
+  int64_t numactiveparticles;       /* :57,71-72,285 */
+  double accmasst;                  /* :191,425, summed in fp64 in a fixed order of its own (the reference never uses it) */
+} fpx_domainfill_stats;
+/* *numpart and *numparticlecount (com_mod.f90:676) in and out; `out` may be NULL.  Needs the wind-time window
+ * (fpx_set_windtime), both field slots and pv of both slots (fpx_upload_diag_fields, or retained by
+ * fpx_verttransform_ecmwf), else FPX_ERR_STATE; FPX_ERR_STATE before fpx_domainfill_init.  With gdomainfill set it returns
+ * at once and touches nothing (:54).  More particles needed than there are vacant storage spaces (the reference stops,
+ * :307-310): FPX_ERR_NOMEM, and the particles, acc_mass_*, *numpart, *numparticlecount and the random stream stay exactly
+ * as they were -- the contract of fpx_releaseparticles.
+ * Uniforms.  A candidate draws one for its free horizontal coordinate, one for z only at an interior height of its
+ * column, one for nclass only if it is accepted.  FPX_RNG_TABLE_SEQ: the reference's serial ran1 stream (idummy = -11,
+ * kept between calls), replayed on the host.  The counter modes: three uniforms per candidate from Philox keyed on (seed,
+ * location, m, itime), independent of acceptance and of fpx_sort_particles. */
+int fpx_boundcond_domainfill(fpx_handle h, int32_t itime, int64_t *numpart, int32_t *numparticlecount, fpx_domainfill_stats *out);
+/* acc_mass_we, acc_mass_sn in the host's shapes and real kind (either may be NULL); set: a warm start that has read
+ * boundcond.bin. */
+int fpx_get_domainfill_acc(fpx_handle h, void *acc_mass_we, void *acc_mass_sn);
+int fpx_set_domainfill_acc(fpx_handle h, const void *acc_mass_we, const void *acc_mass_sn);
+/* boundcond.bin, the one unformatted record of :568-572: numcolumn_we, numcolumn_sn, zcolumn_we, zcolumn_sn, acc_mass_we,
+ * acc_mass_sn in the host's declared shapes, byte for byte.  The host calls it where ipout > 0 .and. itime == loutend. */
+int fpx_boundcond_output(fpx_handle h, const char *path);
+/* device time (ms) of the kernels of the last fpx_boundcond_domainfill, by events of its own.  Its split is read with
+ * fpx_get_info: "domainfill_flux_us" (flux, the scan of mmass), "domainfill_stage1_us" (terminate-and-flag with its scan),
+ * "domainfill_cand_us" (candidates), "domainfill_place_us" (decide, commit, place), "domainfill_candidates". */
+int fpx_domainfill_time(fpx_handle h, double *ms);
 /* Communicator for the grid reduction, one of:
  * (a) RCCL: rank 0 obtains an id (128 bytes), the host distributes it (MPI_Bcast / torch.distributed / a file), every
  *     rank calls fpx_comm_init; the reduction then runs device to device on the handle's stream. */
