@@ -22,6 +22,7 @@
 // in the reference's order of operations; only libm (exp, log, pow) can differ from the CPU result.
 #pragma once
 #include "fpx_tu.hpp"
+#include "fpx_device.hpp"
 #include <hip/hip_runtime.h>
 
 #include "fpx_calcpar.hpp"
@@ -1540,5 +1541,21 @@ __global__ void k_conv_redist(const int *__restrict__ pcol, const int4 *__restri
 #undef I_MIN
 
 }  // namespace conv
+
+// the random-number sources of redist (one uniform number per particle of a convective column)
+template <typename H>
+struct ConvRngSeq {     // the number the host drew for this particle from the serial ran3 stream
+  const H *rn; const unsigned int *pid;
+  __device__ H operator()(long long s) const { return rn[pid[s]]; }
+};
+template <typename R, typename H>
+struct ConvRngCtr {     // counter generator: (seed, global particle number, step, stream of redist)
+  View<R> V; const unsigned int *pid; unsigned int step;
+  __device__ H operator()(long long s) const {
+    Rng<R> G;
+    make_rng(V, pid[s], step | 0x40000000u, G);
+    return (H)(((float)(G.bits(3) >> 8) + 0.5f) * (1.0f / 16777216.0f));
+  }
+};
 FPX_TU_CLOSE
 }  // namespace fpx

@@ -2497,7 +2497,7 @@ FPX_DEV void fetch_level_pair(const View<R> &V, const Fld<R> &F, const TimeW<R> 
   }
 }
 
-// What a Langevin pass reads from the particle's hand-over record itself (PblRecord, fpx_engine.hip, which asserts the two
+// What a Langevin pass reads from the particle's hand-over record itself (PblRecord, fpx_step_common.hpp, which asserts the two
 // constants against its layout): wst, on the cold path of cbl() and in hanna1.  The asm keeps the address arithmetic where the
 // value is read -- hoisted out of the fine loop it would hold two registers through every sub-step.
 constexpr int kRecStride = 16, kRecWst = 9;   // values of R per record; index of wst in PblRecord::v

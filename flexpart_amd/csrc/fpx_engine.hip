@@ -1,8 +1,10 @@
-// fpx_engine.hip -- HIP kernels (gfx950) and the C ABI of include/flexpart_amd.h.
-//
-// One process drives one GPU through one handle.  All particle state and all
-// met fields stay resident in HBM between calls; a step is a single launch of
-// k_advance (one thread per particle slot) on the handle's stream.
+// fpx_engine.hip -- the host side of the library: EngineBase, Engine<R> (one process drives one GPU through one handle; all
+// particle state and all met fields stay resident in HBM between calls), the factory of the fp32 engine, the dispatchers
+// to the step kernels' tables, and the C ABI of include/flexpart_amd.h.  No device code lives here: every kernel sits in
+// the header of its feature (fpx_fields.hpp, fpx_sort.hpp, fpx_particles.hpp, fpx_outgrid.hpp, fpx_probes.hpp, the
+// headers of the newer features), and the three kernels of the particle step are translation units of their own
+// (fpx_step_prep.hip, fpx_step_loop.hip; fpx_tu.hpp).
+#define FPX_TU_PART 0
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstring>
@@ -33,19 +35,24 @@
 #include "fpx_plumetraj.hpp"
 #include "fpx_domainfill.hpp"
 #include "fpx_convect.hpp"
+#include "fpx_step_common.hpp"
+#include "fpx_fields.hpp"
+#include "fpx_sort.hpp"
+#include "fpx_particles.hpp"
+#include "fpx_outgrid.hpp"
+#include "fpx_probes.hpp"
 #include "fpx_rng_host.hpp"
 #include "fpx_host_res.hpp"
 
 namespace fpx {
 
 // shared by the translation units (fpx_tu.hpp): the message behind fpx_last_error()
-#if FPX_TU_REAL == 4 || FPX_TU_PART > 0
+#if FPX_TU_REAL == 4
 extern thread_local std::string g_err;
 #else
 thread_local std::string g_err;
 #endif
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-FPX_TU_OPEN
 
 #define HIPCHK(expr)                                                                      \
   do {                                                                                    \
@@ -54,1978 +61,10 @@ FPX_TU_OPEN
       return fail(FPX_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
   } while (0)
 
-constexpr int kBlock = 256;
-// The big kernels read the fields of their first argument, the View, THROUGH the kernel-argument segment instead of from the
-// by-value parameter.  A by-value aggregate is a private copy that the optimiser splits into one scalar per field, all loaded at the
-// kernel's entry: in k_prep that is 40 scalar loads whose results do not fit the scalar file and travel as lanes of a vector
-// register (800-1300 v_readlane per kernel; polar k_prep 0.78 instead of 0.71 ms) -- and as soon as ONE access has an address
-// the optimiser cannot resolve (a per-lane subscript, a select between two fields' addresses) the whole copy lives in scratch
-// (576-816 B per lane in three instance families before this).  Read in place, every field is a scalar load from constant memory
-// next to its use, re-loaded rather than spilled, and no copy exists that could end up in scratch.  The View must be the kernel's
-// FIRST parameter (offset 0 of the segment).
-#ifndef FPX_VIEW_BY_VALUE
-#define FPX_VIEW_FROM_KERNARG(V, V_arg) const View<R> &V = *(const View<R> *)(const void *)__builtin_amdgcn_kernarg_segment_ptr(); (void)V_arg
-#else
-#define FPX_VIEW_FROM_KERNARG(V, V_arg) const View<R> &V = V_arg
-#endif
-#ifndef FPX_PREP_WAVES
-#define FPX_PREP_WAVES 3   // register budget (waves per SIMD) of k_prep (<= 168 VGPRs)
-#endif
-#ifndef FPX_INIT_PREP_3WAVES
-#define FPX_INIT_PREP_3WAVES 1    // the INIT instance of k_prep at the three-wave budget too: its initialize() body runs only in waves that hold a new particle
-#endif
-#ifndef FPX_PREP_TWO_WAVES   // which instances of k_prep keep the two-wave register budget: none since the arguments are read in place (the nest
-// instances fit 168 VGPRs without a spill, the ones with dry deposition spill 6-12 registers; round 3: every INIT / POLAR / NEST / DRYDEP instance at two waves)
-#define FPX_PREP_TWO_WAVES(INIT, POLAR, NEST, DRYDEP) ((INIT && !FPX_INIT_PREP_3WAVES) || (POLAR && !FPX_POLAR_PREP_3WAVES))
-#endif
-#ifndef FPX_POLAR_PREP_3WAVES
-#define FPX_POLAR_PREP_3WAVES 1   // the polar instance of k_prep at the three-wave register budget (the polar move is out of line: polar_move)
-#endif
-#ifndef FPX_FINISH_WAVES
-#define FPX_FINISH_WAVES 2 // register budget of k_pbl_finish
-#endif
-#ifndef FPX_LOOP_WAVES_F32
-#define FPX_LOOP_WAVES_F32 4   // the f32 instances fit 128 VGPRs: four waves per SIMD (measured: 168 -> 184 ms at 1e8 when they slipped to three)
-#endif
-#ifndef FPX_LOOP_WAVES
-#define FPX_LOOP_WAVES 3   // waves per SIMD the Langevin kernel is register-budgeted for (<= 168 VGPRs)
-#endif
-#ifndef FPX_COST_BUCKETS
-#define FPX_COST_BUCKETS -1  // the work list orders each class by the expected number of passes, longest first (k_prep): -1 = for clouds below 5e7 particles
-#endif
-#ifndef FPX_SLICE_SCHEDULE
-#define FPX_SLICE_SCHEDULE 0   // pass budgets of the successive launches of the Langevin kernel, 0 = none; one entry = ONE launch (measured best)
-#endif
-#ifndef FPX_DRAIN_LANES
-#define FPX_DRAIN_LANES 32   // a wave of a non-final launch whose list is used up hands its particles on when fewer lanes than this hold one
-#endif
-constexpr int kMaxNz = 512;
-constexpr unsigned char kKeyDone = 32, kKeyNotDue = 33;   // keys of the work-list sort (6 bits); 0..31: PBL particles, class-major (k_prep)
-
-// ---------------------------------------------------------------------------
-// field repacking kernels
-// ---------------------------------------------------------------------------
-// 3-D field (x fastest, strides nxmax,nymax) -> out[((jy*nx+ix)*nz + k)*stride + off]
-// (z fastest).  32x32 LDS tile transposes x<->z so both sides move whole rows.
-template <typename H, typename R>
-__global__ void k_pack3(const H *__restrict__ in, R *__restrict__ out, int nx, int ny, int nz, int nxmax, int nymax,
-                        int stride, int off) {
-  __shared__ R tile[32][33];
-  const int jy = blockIdx.z;
-  const int x0 = blockIdx.x * 32, z0 = blockIdx.y * 32;
-  for (int r = threadIdx.y; r < 32; r += blockDim.y) {
-    int x = x0 + threadIdx.x, z = z0 + r;
-    if (x < nx && z < nz) tile[r][threadIdx.x] = (R)in[(size_t)x + (size_t)nxmax * ((size_t)jy + (size_t)nymax * z)];
-  }
-  __syncthreads();
-  for (int r = threadIdx.y; r < 32; r += blockDim.y) {
-    int x = x0 + r, z = z0 + threadIdx.x;
-    if (x < nx && z < nz) out[(((size_t)jy * nx + x) * nz + z) * stride + off] = tile[threadIdx.x][r];
-  }
-}
-
-template <typename H, typename R>
-__global__ void k_pack2(const H *__restrict__ in, R *__restrict__ out, int nx, int ny, int nxmax, int stride, int off) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nx * ny) return;
-  int ix = i % nx, jy = i / nx;
-  out[(size_t)i * stride + off] = (R)in[(size_t)ix + (size_t)nxmax * jy];
-}
-
-// hcell[jy][ix] = max of hmix over the cell's corners and both slots: the loop of
-// advance.f90:238-252 (start value 0, jyp clamp of :228-231) == initialize.f90:83-90
-template <typename R>
-__global__ void k_hcell(const R *__restrict__ sfc, R *__restrict__ hcell, int nx, int ny) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nx * ny) return;
-  int ix = i % nx, jy = i / nx;
-  int ixp = min(ix + 1, nx - 1), jyp = min(jy + 1, ny - 1);
-  R h = (R)0;
-  for (int s = 0; s < 2; s++) {
-    h = fmax(h, sfc[(((size_t)jy * nx + ix) * 2 + s) * 4 + 3]);
-    h = fmax(h, sfc[(((size_t)jy * nx + ixp) * 2 + s) * 4 + 3]);
-    h = fmax(h, sfc[(((size_t)jyp * nx + ix) * 2 + s) * 4 + 3]);
-    h = fmax(h, sfc[(((size_t)jyp * nx + ixp) * 2 + s) * 4 + 3]);
-  }
-  hcell[i] = h;
-}
-
-// ---------------------------------------------------------------------------
-// particle I/O kernels: host order (pid) <-> device slots
-// ---------------------------------------------------------------------------
-template <typename S, typename D>
-__global__ void k_scatter_in(const S *__restrict__ src, D *__restrict__ dst, const unsigned int *__restrict__ slot_of_pid,
-                             long long first, long long count) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  long long slot = slot_of_pid ? (long long)slot_of_pid[first + i] : first + i;
-  dst[slot] = (D)src[i];
-}
-template <typename S, typename D>
-__global__ void k_gather_out(const S *__restrict__ src, D *__restrict__ dst, const unsigned int *__restrict__ slot_of_pid,
-                             long long first, long long count) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  long long slot = slot_of_pid ? (long long)slot_of_pid[first + i] : first + i;
-  dst[i] = (D)src[slot];
-}
-template <typename D>
-__global__ void k_fill(D *__restrict__ dst, D val, long long first, long long count, const unsigned int *__restrict__ slot_of_pid) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  long long slot = slot_of_pid ? (long long)slot_of_pid[first + i] : first + i;
-  dst[slot] = val;
-}
-__global__ void k_iota_pid(unsigned int *__restrict__ pid, long long first, long long count) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  pid[first + i] = (unsigned int)(first + i);
-}
-
-// ---------------------------------------------------------------------------
-// locality sort: key = (jy, ix, level), the order in which the packed fields lie in
-// HBM; dead particles sort to the end.  Keeps waves homogeneous (same cell => same
-// mixing height, stability regime and similar sub-step counts) and turns the field
-// gathers of a wave into a few shared cache lines.
-// ---------------------------------------------------------------------------
-template <typename R>
-__global__ void k_sort_keys(View<R> V, Parts<R> P, long long n, unsigned int *__restrict__ keys, unsigned int *__restrict__ vals,
-                            unsigned int dead_key) {
-  __shared__ R hgt[kMaxNz];
-  for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
-  __syncthreads();
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  unsigned int key = dead_key;
-  if (P.itra1[i] != kDead) {
-    double xt = P.xt[i], yt = P.yt[i];
-    if (xt >= 0. && xt <= (double)V.nxmin1 && yt >= 0. && yt <= (double)V.nymin1) {
-      int ix = min((int)xt, V.nx - 1), jy = min((int)yt, V.ny - 1);
-      int lev = find_level(hgt, V.nz, P.zt[i]);   // 1 .. nz-1
-      key = ((unsigned int)jy * V.nx + ix) * (unsigned int)V.nz + (unsigned int)lev;
-    }
-  }
-  keys[i] = key;
-  vals[i] = (unsigned int)i;
-}
-
-// keys of the inverse operation: the particle number, so that the sort puts every particle back into the storage space
-// of its number (slot = pid)
-__global__ void k_sort_keys_pid(const unsigned int *__restrict__ pid, long long n, unsigned int *__restrict__ keys, unsigned int *__restrict__ vals) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  keys[i] = pid[i];
-  vals[i] = (unsigned int)i;
-}
-
-// out[i] = in[perm[i]] for every particle array at once.  Between two re-sorts a particle stays in or next to its grid
-// column, so the sources of neighbouring destination blocks share cache lines: workgroups are dealt to the eight XCDs
-// round-robin, therefore block b takes tile (b % 8) * tiles_per_xcd + b / 8 -- each XCD's L2 then sees one contiguous
-// eighth of the destination range and every source line is fetched from HBM by one XCD instead of by up to eight.
-// The arrays go in four groups, one launch each: the source lines a workgroup touches are shared with its neighbours
-// (a grid column's particles are re-shuffled among its levels), and only with a few arrays in flight does that
-// working set stay in the 4 MB L2 of an XCD until the neighbours have used it (all 18 arrays in one launch: twice the
-// compulsory reads).
-template <typename R, int GROUP>
-__global__ void k_permute(Parts<R> A, Parts<R> B, const unsigned int *__restrict__ perm, long long n, int nspec, int tiles_per_xcd) {
-  const long long tile = (long long)(blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);
-  long long i = tile * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const unsigned int j = perm[i];
-  if (GROUP == 0) { B.xt[i] = A.xt[j]; B.yt[i] = A.yt[j]; B.zt[i] = A.zt[j]; B.idt[i] = A.idt[j]; }
-  if (GROUP == 1) { B.up[i] = A.up[j]; B.vp[i] = A.vp[j]; B.wp[i] = A.wp[j]; B.itra1[i] = A.itra1[j]; }
-  if (GROUP == 2) { B.us[i] = A.us[j]; B.vs[i] = A.vs[j]; B.ws[i] = A.ws[j]; B.itramem[i] = A.itramem[j]; }
-  if (GROUP == 3) {
-    B.npoint[i] = A.npoint[j]; B.nclass[i] = A.nclass[j]; B.cbt[i] = A.cbt[j]; B.itrasplit[i] = A.itrasplit[j];
-    B.pid[i] = A.pid[j];
-    for (int ks = 0; ks < nspec; ks++) B.xmass1[(size_t)ks * B.cap + i] = A.xmass1[(size_t)ks * A.cap + j];
-    if (A.xscav) for (int ks = 0; ks < nspec; ks++) B.xscav[(size_t)ks * B.cap + i] = A.xscav[(size_t)ks * A.cap + j];
-  }
-}
-
-// ---- convection (fpx_convect.hpp): small kernels and the random-number sources of redist ---------------------------
-template <typename S, typename D>
-__global__ void k_conv_pack(const S *__restrict__ src, D *__restrict__ dst, int nx, int ny, int nlev, int nxmax, int nymax) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, n2 = (long long)nx * ny;
-  if (i >= n2 * nlev) return;
-  const int k = (int)(i / n2), r = (int)(i % n2), jy = r / nx, ix = r % nx;
-  dst[i] = (D)src[(size_t)ix + (size_t)nxmax * ((size_t)jy + (size_t)nymax * k)];
-}
-template <typename H>
-struct ConvRngSeq {     // the number the host drew for this particle from the serial ran3 stream
-  const H *rn; const unsigned int *pid;
-  __device__ H operator()(long long s) const { return rn[pid[s]]; }
-};
-template <typename R, typename H>
-struct ConvRngCtr {     // counter generator: (seed, global particle number, step, stream of redist)
-  View<R> V; const unsigned int *pid; unsigned int step;
-  __device__ H operator()(long long s) const {
-    Rng<R> G;
-    make_rng(V, pid[s], step | 0x40000000u, G);
-    return (H)(((float)(G.bits(3) >> 8) + 0.5f) * (1.0f / 16777216.0f));
-  }
-};
-
-// A permutation without locality (the first sort of a freshly seeded or uploaded cloud) would fetch one memory
-// transaction per 8-byte element through the direct gather (18 arrays: > 1 kB per particle).  Such a permutation goes
-// through one 128-byte record per particle instead: pack (coalesced reads, whole-line writes), then gather whole
-// lines and store coalesced.  Species beyond the first keep the direct gather.
-template <typename R>
-struct alignas(128) SortRecord {
-  double xt, yt;
-  R v[8];                // zt up vp wp us vs ws xmass1(1)
-  int i[6];              // idt itra1 itramem npoint nclass itrasplit
-  unsigned int pid;
-  int cbt;
-};
-template <typename R>
-__global__ void k_permute_pack(Parts<R> A, SortRecord<R> *__restrict__ rec, long long n) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  SortRecord<R> r;
-  r.xt = A.xt[i]; r.yt = A.yt[i];
-  r.v[0] = A.zt[i]; r.v[1] = A.up[i]; r.v[2] = A.vp[i]; r.v[3] = A.wp[i]; r.v[4] = A.us[i]; r.v[5] = A.vs[i]; r.v[6] = A.ws[i];
-  r.v[7] = A.xmass1[i];
-  r.i[0] = A.idt[i]; r.i[1] = A.itra1[i]; r.i[2] = A.itramem[i]; r.i[3] = A.npoint[i]; r.i[4] = A.nclass[i]; r.i[5] = A.itrasplit[i];
-  r.pid = A.pid[i]; r.cbt = A.cbt[i];
-  rec[i] = r;
-}
-template <typename R>
-__global__ void k_permute_unpack(const SortRecord<R> *__restrict__ rec, Parts<R> A, Parts<R> B, const unsigned int *__restrict__ perm,
-                                 long long n, int nspec) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const unsigned int j = perm[i];
-  const SortRecord<R> r = rec[j];
-  B.xt[i] = r.xt; B.yt[i] = r.yt;
-  B.zt[i] = r.v[0]; B.up[i] = r.v[1]; B.vp[i] = r.v[2]; B.wp[i] = r.v[3]; B.us[i] = r.v[4]; B.vs[i] = r.v[5]; B.ws[i] = r.v[6];
-  B.xmass1[i] = r.v[7];
-  B.idt[i] = r.i[0]; B.itra1[i] = r.i[1]; B.itramem[i] = r.i[2]; B.npoint[i] = r.i[3]; B.nclass[i] = r.i[4]; B.itrasplit[i] = r.i[5];
-  B.pid[i] = r.pid; B.cbt[i] = (short)r.cbt;
-  for (int ks = 1; ks < nspec; ks++) B.xmass1[(size_t)ks * B.cap + i] = A.xmass1[(size_t)ks * A.cap + j];
-  if (A.xscav) for (int ks = 0; ks < nspec; ks++) B.xscav[(size_t)ks * B.cap + i] = A.xscav[(size_t)ks * A.cap + j];
-}
-// number of neighbours in the new order whose sources lie more than `window` storage spaces apart
-__global__ void k_perm_disorder(const unsigned int *__restrict__ perm, long long n, unsigned int window, unsigned long long *__restrict__ count) {
-  __shared__ unsigned int part[kBlock / 64];
-  unsigned int mine = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    if (i > 0) {
-      const long long d = (long long)perm[i] - (long long)perm[i - 1];
-      mine += (d < 0 ? -d : d) > (long long)window;
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); k++) t += part[k];
-    if (t) atomicAdd(count, t);
-  }
-}
-
-// particle number -> storage space; built on demand (release, splitting, up/download by particle number), not by
-// every re-sort: a random 4-byte scatter costs a whole memory transaction per particle
-__global__ void k_slot_map(const unsigned int *__restrict__ pid, long long cap, unsigned int *__restrict__ slot_of_pid) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < cap) slot_of_pid[pid[i]] = (unsigned int)i;
-}
-
-// ---------------------------------------------------------------------------
-// synthetic cloud on the device (benchmarks): same SplitMix64 counters and the
-// same arithmetic as flexpart_amd/synthetic.py:make_particles
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ double splitmix_u01(unsigned long long idx1, unsigned long long seed) {
-  unsigned long long z = idx1 * 0x9E3779B97F4A7C15ull + seed;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-template <typename R>
-__global__ void k_seed(View<R> V, Parts<R> P, long long n, unsigned long long seed, double frac_pbl, double zmax,
-                       double lat_margin, int itime0) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  {
-#pragma clang fp contract(off)
-  const unsigned long long gi = (unsigned long long)i + V.pid_base + 1ull;   // number in the global cloud
-  double ux = splitmix_u01(gi, seed + 1), uy = splitmix_u01(gi, seed + 2);
-  double uz = splitmix_u01(gi, seed + 3), us = splitmix_u01(gi, seed + 4);
-  const double eps = 361.0 / 3.0e5;
-  double x = eps + ux * ((double)(V.nx - 1) - 2.0 * eps);
-  double y = lat_margin + uy * ((double)(V.ny - 1) - 2.0 * lat_margin);
-  int ix = min((int)x, V.nx - 2), jy = min((int)y, V.ny - 2);
-  double hloc = (double)V.hcell[(size_t)jy * V.nx + ix];
-  double z = us < frac_pbl ? 10.0 + uz * fmax(hloc - 20.0, 1.0) : hloc + 10.0 + uz * (zmax - hloc - 10.0);
-  P.xt[i] = x; P.yt[i] = y; P.zt[i] = (R)z;
-  P.up[i] = 0; P.vp[i] = 0; P.wp[i] = 0; P.us[i] = 0; P.vs[i] = 0; P.ws[i] = 0;
-  P.idt[i] = 0; P.itra1[i] = itime0; P.itramem[i] = itime0; P.npoint[i] = 1; P.nclass[i] = 1; P.itrasplit[i] = V.ldirect * 999999999;   // "never", signed like itra1 + ldirect*itsplit (releaseparticles.f90:181)
-  P.cbt[i] = 1; P.pid[i] = (unsigned int)i;
-  for (int ks = 0; ks < V.nspec; ks++) P.xmass1[(size_t)ks * P.cap + i] = (R)1;
-  if (P.xscav) for (int ks = 0; ks < V.nspec; ks++) P.xscav[(size_t)ks * P.cap + i] = (R)-1;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// TABLE_SEQ helper: which particles are due / new / take initialize()'s CBL draw
-// ---------------------------------------------------------------------------
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_classify(View<R> V, Parts<R> P, long long numpart, int itime, unsigned char *__restrict__ flags) {
-  __shared__ R hgt[kMaxNz];
-  for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
-  __syncthreads();
-  long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= numpart) return;
-  unsigned char f = 0;
-  if (P.itra1[s] == itime) {
-    f |= 1;
-    if (P.itramem[s] == itime || itime == 0) {
-      f |= 2;
-      double xt = P.xt[s], yt = P.yt[s];
-      if (xt >= 0. && xt <= (double)V.nxmin1 && yt >= 0. && yt <= (double)V.nymin1)
-        if (initialize_needs_cbl_draws(V, hgt, itime, xt, yt, P.zt[s])) f |= 4;
-    }
-  }
-  flags[P.pid[s]] = f;
-}
-
-// ---------------------------------------------------------------------------
-// the hot kernels: one pass of the particle loop timemanager.f90:531-712
-//
-//   k_prep : every due particle -- initialize() if newly released, grid/cell/PBL test;
-//            particles above the PBL finish here (one interpol_wind step + Petterssen:
-//            gather/stream bound); PBL particles are appended to a work list.
-//   k_pbl  : persistent waves over the work list.  Each lane owns one PBL particle and runs
-//            passes of the Langevin loop; a lane whose particle has finished its lsynctime
-//            immediately refills from the list, so lanes never idle on the data-dependent
-//            trip count (15-150 passes per particle).
-// ---------------------------------------------------------------------------
-template <typename R, typename RNG>
-__device__ __forceinline__ void make_rng(const View<R> &V, unsigned int pid, unsigned int step, RNG &G) {
-  G.tab = V.rannumb; G.maxrand = V.maxrand; G.mode = V.rng_mode;
-  G.pid = pid + V.pid_base; G.step = step;
-  G.k0 = (unsigned int)V.seed; G.k1 = (unsigned int)(V.seed >> 32);
-  G.cblk = 0xffffffffu;
-}
-
-template <typename R>
-__device__ __forceinline__ int advance_start_index(const View<R> &V, const SeqRng &S, const Rng<R> &G, unsigned int pid) {
-  if (V.rng_mode == 0) return S.nrand_adv[pid];      // advance.f90:153, serial stream replayed by the host
-  if (V.rng_mode == 1) return G.start_index(0);
-  return 1;
-}
-
-// epilogue timemanager.f90:630-708 + write-back of the particle
-// TURB: also write up, vp, cbt -- changed only by initialize() and by the Langevin loop; a particle that
-// was above the mixing layer for the whole step keeps them (advance.f90:629-708 does not touch them)
-// What the epilogue reads of the particle itself (release point, masses): fetched by the caller together with its last
-// gather (EpiPre::load inside a `late` hook), so that the epilogue starts with them instead of with two more dependent
-// memory round trips at the tail of a latency-bound kernel.
-// (the release point and the first species' mass: three registers; the kernels have none to spare for more)
-template <typename R>
-struct EpiPre {
-  int npoint;
-  R xm0;
-  template <bool DRYDEP>
-  __device__ __forceinline__ void load(const View<R> &V, const GridP<R> &Gp, const Parts<R> &P, long long s) {
-    const bool massfract = V.mdomainfill == 0 && V.mquasilag == 0;
-    npoint = ((massfract && V.numpoint > 1) || (DRYDEP && Gp.on)) ? P.npoint[s] : 1;
-    xm0 = P.xmass1[s];
-  }
-};
-
-// the dry deposition of one particle's step, handed back to a caller that scatters it where its wave is convergent again
-// (k_pbl_finish: the neighbourhood sums of wave_kernel_add need every lane of the wave)
-template <typename R>
-struct DryDep {
-  float dep[kMaxSpec];   // drydeposit(ks), timemanager.f90:650-656,690-693 (0: nothing)
-  R x, y;                // the particle's position the kernel is centred on (xtra1, ytra1 after the step)
-  int nage, kp, nclass;
-};
-
-template <typename R, bool DRYDEP, bool TURB = true>
-__device__ __forceinline__ void epilogue_store(const View<R> &V, const GridP<R> &Gp, Parts<R> &P, long long s, int itime, int itramem,
-                                               int nstop, const PState<R> &ps, const R *prob, Stats *st, const EpiPre<R> *pre = nullptr,
-                                               DryDep<R> *defer = nullptr) {
-  int itra1;
-  if (nstop > 1) {
-    itra1 = kDead;
-    atomicAdd(&st->n_left, 1ull);
-  } else {
-    itra1 = itime + V.lsynctime;
-    R xmassfract = (R)0;
-    // release point of the particle: xmass(npoint(j),ks), npart(npoint(j)), timemanager.f90:663-666
-    const bool massfract = V.mdomainfill == 0 && V.mquasilag == 0;
-    // (with one release point every index into the point tables is clamped to it: npoint(j) is not needed, and the
-    // table loads below do not wait for it)
-    const int npoint = pre ? pre->npoint : ((massfract && V.numpoint > 1) || (DRYDEP && Gp.on)) ? P.npoint[s] : 1;
-    const int kr = release_index(V, npoint);
-    // everything the species loop reads -- the release point's table entries and the particle's masses -- in ONE round
-    // trip (the asm ties the loads together; otherwise each is issued where it is first needed: three dependent trips)
-    int npart_i = massfract ? V.rel_npart[kr] : 0;
-    R xmr_all[kMaxSpec], xm_all[kMaxSpec];
-#pragma unroll
-    for (int ks = 0; ks < kMaxSpec; ks++) {
-      xmr_all[ks] = (massfract && ks < V.nspec) ? V.rel_xmass[(size_t)ks * V.numpoint + kr] : (R)0;
-      xm_all[ks] = ks < V.nspec ? ((pre && ks == 0) ? pre->xm0 : P.xmass1[(size_t)ks * P.cap + s]) : (R)0;
-    }
-    static_assert(kMaxSpec == 5, "the tie below names five species");
-    asm volatile("" : "+v"(npart_i), "+v"(xmr_all[0]), "+v"(xmr_all[1]), "+v"(xmr_all[2]), "+v"(xmr_all[3]), "+v"(xmr_all[4]),
-                      "+v"(xm_all[0]), "+v"(xm_all[1]), "+v"(xm_all[2]), "+v"(xm_all[3]), "+v"(xm_all[4]));
-    const R npart_r = (R)npart_i;
-#pragma unroll
-    for (int ks = 0; ks < kMaxSpec; ks++) {
-      if (ks < V.nspec) {
-        R decfact = V.decay[ks] > (R)0 ? m_exp(-(R)abs(V.lsynctime) * V.decay[ks]) : (R)1;
-        R xm = xm_all[ks];
-        if (DRYDEP && V.drydepspec[ks]) {
-          // timemanager.f90:650-656; drydeposit is real(dep_prec): 4 bytes in every build
-          float drydeposit = (float)(xm * prob[ks] * decfact);
-          xm = xm * ((R)1 - prob[ks]) * decfact;
-          if (Gp.on && V.ldirect == 1) {   // timemanager.f90:690-696
-            if (V.decay[ks] > (R)0) {
-              const int ldeltat = itime < Gp.loutnext ? itime - (Gp.loutnext - Gp.loutstep) : itime - Gp.loutnext;   // :513-517
-              drydeposit = (float)((R)drydeposit * m_exp((R)abs(ldeltat) * V.decay[ks]));
-            }
-            const int nage = ageclass(Gp, abs(itime - itramem));
-            const int kp = Gp.ioutputforeachrelease == 1 ? npoint : 1;
-            if (defer) {
-              defer->dep[ks] = drydeposit; defer->x = (R)ps.xt; defer->y = (R)ps.yt; defer->nage = nage; defer->kp = kp; defer->nclass = P.nclass[s];
-            } else {
-              drydepo_particle(V, Gp, P.nclass[s], drydeposit, ks, (R)ps.xt, (R)ps.yt, nage, kp);
-              if (Gp.nested) drydepo_particle(V, Gp, P.nclass[s], drydeposit, ks, (R)ps.xt, (R)ps.yt, nage, kp, true);   // timemanager.f90:694-696
-            }
-          }
-        } else xm = xm * decfact;
-        if (DRYDEP || V.decay[ks] > (R)0) P.xmass1[(size_t)ks * P.cap + s] = xm;
-        if (massfract) {   // timemanager.f90:663-666
-          const R xmr = xmr_all[ks];
-          if (xmr > (R)0) xmassfract = m_max(xmassfract, npart_r * xm / xmr);
-        } else {
-          xmassfract = (R)1;
-        }
-      }
-    }
-    if (xmassfract < (R)0.0001) {   // minmass, par_mod.f90:213
-      itra1 = kDead;
-      atomicAdd(&st->n_minmass, 1ull);
-    } else if (abs(itra1 - itramem) >= V.lage_last) {
-      itra1 = kDead;
-      atomicAdd(&st->n_maxage, 1ull);
-    }
-  }
-  P.xt[s] = ps.xt; P.yt[s] = ps.yt; P.zt[s] = ps.zt;
-  if (TURB) { P.up[s] = ps.up; P.vp[s] = ps.vp; P.cbt[s] = ps.icbt; }
-  P.wp[s] = ps.wp;
-  P.us[s] = ps.usigold; P.vs[s] = ps.vsigold; P.ws[s] = ps.wsigold;
-  P.idt[s] = ps.ldt; P.itra1[s] = itra1;
-}
-
-// Per-slot hand-over record between the three PBL kernels: ONE contiguous, aligned record per particle (128 bytes in the
-// fp64 build = one cache line, 64 bytes in f32), so that a lane that retires its particle in the Langevin kernel -- about
-// two lanes of a wave per pass -- writes one line instead of a sector in each of sixteen arrays, and a refilling lane
-// reads one.  k_prep fills the surface-layer part (FRESH), k_pbl_loop writes the particle's state at the end of its last
-// pass (DONE / ESCAPED) -- or, when the launch's pass budget is used up (time slices, see k_pbl_loop), the state a later
-// launch continues from (CONTINUE); k_pbl_finish reads it and writes the particle arrays, coalesced.
-enum { PBL_FRESH = 3 };   // fourth value of the record's state next to PBL_CONTINUE / PBL_DONE / PBL_ESCAPED
-template <typename R>
-struct alignas(16 * sizeof(R)) PblRecord {
-  // v[0..3]  = dxsave, dysave, dawsave, dcwsave                                  (CONTINUE, DONE, ESCAPED)
-  // v[4..7]  = zt, up, vp, wp                                                    (CONTINUE, DONE, ESCAPED)
-  // v[0..2]  = the step's invariants 1/ust | 1/ol, sigu, 1/tlu as StashInv holds them  (FRESH; read by the one-launch kernel only)
-  // v[8..10] = ust, wst, ol (interpol_all.f90:80-107; ust as hanna.f90:43 floored it)  (FRESH, CONTINUE)
-  //          | interpol_mod u, v, w of the last pass                             (DONE, ESCAPED)
-  // v[11]    = CBL transition (cbl.f90:79-81), v[12] = mixing height of the cell (advance.f90:236-262): written by k_prep only
-  // i[0] = nrand, i[1] = ldt, i[2] = state | icbt < 0 | indz | ngrid | |itimec - itime|  (pbl_pack)
-  R v[13];
-  int i[3];
-};
-static_assert(sizeof(PblRecord<double>) == 128 && sizeof(PblRecord<float>) == 64, "one cache line / half a line per record");
-static_assert(sizeof(PblRecord<double>) == kRecStride * sizeof(double) && sizeof(PblRecord<float>) == kRecStride * sizeof(float) &&
-              offsetof(PblRecord<double>, v) == 0 && offsetof(PblRecord<float>, v) == 0 && kRecWst < 13, "RecCold (fpx_device.hpp) indexes the records by these");
-// state: bits 0-1, icbt = -1: bit 2, indz (<= 511): bits 3-11, ngrid + 2 (-2 .. kMaxNests): bits 12-14, |itimec - itime| (<= |lsynctime| <= 65535): bits 15-30
-__device__ __forceinline__ int pbl_pack(int state, int icbt, int indz, int ngrid, int elapsed) {
-  return state | (icbt < 0 ? 4 : 0) | (indz << 3) | ((ngrid + 2) << 12) | (elapsed << 15);
-}
-__device__ __forceinline__ int pbl_state(int pk) { return pk & 3; }
-__device__ __forceinline__ int pbl_icbt(int pk) { return (pk & 4) ? -1 : 1; }
-__device__ __forceinline__ int pbl_indz(int pk) { return (pk >> 3) & 511; }
-__device__ __forceinline__ int pbl_ngrid(int pk) { return ((pk >> 12) & 7) - 2; }
-__device__ __forceinline__ int pbl_elapsed(int pk) { return (pk >> 15) & 65535; }
-static_assert(kMaxNz <= 512 && kMaxNests + 2 <= 7, "pbl_pack field widths");
-template <typename R>
-struct PblRec {
-  PblRecord<R> *rec;       // [cap]
-  R *tdep;                 // [cap], DRYDEP only: seconds of the step the particle spent below 2*href (advance.f90:582-599, see pbl_pass)
-};
-
-// Register budget: the steady-state kernel of a run on the mother lat-lon grid is built for FPX_PREP_WAVES waves per SIMD
-// (<= 168 VGPRs, no scratch); the variants that also carry initialize(), the polar maps or the nest table would spill at
-// that budget and keep two waves.
-// The particle's step from the point where it is known to be due and inside the grid: initialize() if new, the boundary-layer
-// test, the set-up of a boundary-layer particle or the whole step of one above it.  A function of its own so that k_prep can
-// hold two instances: on a grid with polar caps (POLAR) the waves none of whose particles sits in a cap run the mother-grid
-// instance (POLAR = false: compile-time ngrid = 0, field pointers in scalar registers, no stereographic code) with CAPCHECK
-// (the test of advance.f90:843 still sees a particle that has moved INTO a cap); only the waves of the caps run the polar one.
-template <typename R, bool DRYDEP, bool INIT, bool POLAR, bool NEST, bool CAPCHECK>
-__device__ __forceinline__ void prep_body(const View<R> &V, const GridP<R> &Gp, Parts<R> &P, const SeqRng &S, const PblRec<R> &Q, long long s, int itime,
-                                          unsigned int step, Stats *st, unsigned char *__restrict__ pbl_flag, const R *hgt,
-                                          PState<R> &ps, int itramem, unsigned int pid) {
-  constexpr bool MOTHER = !POLAR && !NEST;
-  Rng<R> G;
-  make_rng(V, pid, step, G);
-  const bool is_new = INIT && ((itramem == itime) || (itime == 0));   // timemanager.f90:553
-  if (is_new) {
-    int nrand_i;
-    R dcas = (R)0, dcas1 = (R)0;
-    Rng<R> Gi = G;
-    if (V.rng_mode == 0) {
-      nrand_i = S.nrand_init[pid];
-      if (sizeof(R) == 4) { dcas = (R)S.cbl_dcas[pid]; dcas1 = (R)S.cbl_dcas1[pid]; }
-      else { dcas = (R)S.cbl_dcas_d[pid]; dcas1 = (R)S.cbl_dcas1_d[pid]; }
-    } else {
-      Gi.step = step | 0x80000000u;           // a stream of its own for initialize()
-      nrand_i = V.rng_mode == 1 ? Gi.start_index(0) : 1;
-      dcas = (R)(((float)(Gi.bits(1) >> 8) + 0.5f) * (1.0f / 16777216.0f));
-      Rng<R> Gn = Gi;
-      Gn.mode = 2;
-      dcas1 = Gn.at(7);
-    }
-    initialize_particle(V, hgt, Gi, nrand_i, itime, ps, dcas, dcas1);
-    atomicAdd(&st->n_init, 1ull);
-  }
-
-  AdvCtx<R> A;
-  const TimeW<R> W = time_weights(V, itime);
-  const bool in_pbl = adv_begin<R, MOTHER, true>(V, ps.xt, ps.yt, ps.zt, itime, advance_start_index(V, S, G, pid), A);
-  if (V.lsettling) A.nsp = settling_species(V, P.npoint[s]);   // advance.f90:518-524 with nrelpoint = npoint(j)
-  if (in_pbl) {
-    if (is_new) {   // the PBL kernels read the state from HBM (an old particle's is there already)
-      P.up[s] = ps.up; P.vp[s] = ps.vp; P.wp[s] = ps.wp;
-      P.us[s] = ps.usigold; P.vs[s] = ps.vsigold; P.ws[s] = ps.wsigold;
-      P.idt[s] = ps.ldt; P.cbt[s] = ps.icbt;
-    }
-    // first-pass set-up of interpol_all (ust, wst, ol: interpol_all.f90:80-107) done here, where
-    // the lanes are convergent; the Langevin kernel then starts from five numbers per particle
-    PblCtx<R> B;
-    pbl_begin(V, ps.xt, ps.yt, W, A, B);
-    // ... and what the turbulence scheme derives from them and the mixing height alone: fixed for the whole step, taken here
-    // once instead of in each of the particle's 15 to 150 passes (step_invariants)
-    const StepInv<R> I = step_invariants(A.h, B.ol, B.ust, B.wst, PlainMath());
-    {
-      PblRecord<R> &r = Q.rec[s];
-      r.v[8] = I.ust; r.v[kRecWst] = B.wst; r.v[10] = B.ol; r.v[11] = B.transition;
-      r.v[12] = A.h;
-      r.v[0] = I.iaux; r.v[1] = I.sigu; r.v[2] = inv_pack_itlu(I);   // as the Langevin kernel's stash holds them (StashInv)
-      // (the level of the particle's height travels with it: the Langevin kernel's first level search starts there, find_level_from)
-      r.i[0] = A.nrand; r.i[2] = pbl_pack(PBL_FRESH, 1, find_level(hgt, V.nz, ps.zt), A.ngrid, 0);
-    }
-    // Regime class of the particle's PBL passes (hanna.f90:42,59,91 and advance.f90:405-406).  The
-    // work list is the slots stably sorted by this 3-bit key: class by class, each class in slot
-    // (= cell) order, so the lanes of a wave run the same branch of the turbulence scheme.
-    unsigned char cls;
-    if (V.cblflag == 1 && V.turbswitch && (I.flags & INV_DEEP)) cls = 1;      // skewed CBL scheme
-    else if ((I.flags & INV_REGIME) == 0) cls = 3;                            // neutral
-    else if ((I.flags & INV_REGIME) == 1) cls = 2;                                            // unstable, Gaussian: next to the CBL class, whose
-                                                                              // hanna_short branch it shares (waves at a class boundary run both classes)
-    else cls = 4;                                                             // stable
-    // (measured and not kept: the reverse order -- 297.3 instead of 293.7 ms at 1e8, 47.9 instead of 42.2 ms at an eighth
-    // of the cloud: the launch must not END on the CBL class, whose particles make the most passes; a cursor per class
-    // with the waves dealt to the classes by their work -- 46.7 ms at an eighth: every class then ends at the end of the
-    // launch; a cost bucket (octaves of (ustar+wstar)/h) below the class in the key: no measurable change)
-    // Below the class: a cost bucket, the most expensive first.  The number of passes a particle makes is about |lsynctime| /
-    // (its time step); its last time step of the previous step (idt) predicts that well where the time step is set by the
-    // cell (ust, ol, h: the stable class keeps one value for the whole step).  With the long particles of a class at the head
-    // of its segment, what the waves still hold when the cursor leaves the class -- and at the end of the launch -- are short
-    // particles: less of the launch runs with half-empty or two-class waves.  Each bucket stays in slot (= cell) order.
-    unsigned char bucket = 0;
-    if (V.pbl_cost_buckets) {
-      const int idt = is_new ? ps.ldt : P.idt[s];
-      const int est = abs(V.lsynctime) / max(idt, 1);          // passes, if the time step stayed
-      if (V.pbl_cost_buckets == 1) bucket = est >= 128 ? 3 : est >= 64 ? 2 : est >= 32 ? 1 : 0;
-      else if (V.pbl_cost_buckets == 2) bucket = est >= 64 ? 1 : 0;
-      else bucket = est >= 256 ? 7 : est >= 128 ? 6 : est >= 96 ? 5 : est >= 64 ? 4 : est >= 48 ? 3 : est >= 32 ? 2 : est >= 16 ? 1 : 0;
-    }
-    pbl_flag[s] = (unsigned char)((cls - 1) * 8 + (7 - bucket));
-    return;
-  }
-  // Above the mixing layer for the whole step (advance.f90:629-708 -> 99): wp and ldt are set, not read; up, vp and cbt
-  // are not touched; the mesoscale velocities are fetched with the last column of the 48-value gather (same round
-  // trip, not live across the gather: the asm ties the loads to that point of the program).
-  R usig, vsig, wsig;
-  pbl_flag[s] = kKeyDone;
-  auto late = [&]() {
-    if (!is_new) {
-      asm volatile("" : "+v"(s));
-      ps.usigold = P.us[s]; ps.vsigold = P.vs[s]; ps.wsigold = P.ws[s];
-    }
-  };
-  above_step<R, Rng<R>, true>(V, hgt, G, W, itime, ps.xt, ps.yt, ps.zt, ps.wp, ps.ldt, A, usig, vsig, wsig, late);
-  // (fetching the epilogue's npoint / xmass1 with the Petterssen gather was tried here: the three registers spill at the
-  // three-wave budget of this kernel; k_pbl_finish has them)
-  const int nstop = adv_finish<R, Rng<R>, POLAR, MOTHER, NoLate, CAPCHECK>(V, hgt, G, itime, ps, A, usig, vsig, wsig);
-  R prob[kMaxSpec];
-#pragma unroll
-  for (int ks = 0; ks < kMaxSpec; ks++) prob[ks] = (R)0;
-  if (is_new) epilogue_store<R, DRYDEP, true>(V, Gp, P, s, itime, itramem, nstop, ps, prob, st);
-  else epilogue_store<R, DRYDEP, false>(V, Gp, P, s, itime, itramem, nstop, ps, prob, st);
-}
-
-template <typename R, bool DRYDEP, bool INIT, bool POLAR, bool NEST>
-__global__ void __launch_bounds__(kBlock, FPX_PREP_TWO_WAVES(INIT, POLAR, NEST, DRYDEP) ? 2 : FPX_PREP_WAVES) k_prep(View<R> V_arg, GridP<R> Gp_arg, Parts<R> P_arg, SeqRng S_arg, PblRec<R> Q_arg, long long numpart, int itime,
-                                                 unsigned int step, Stats *st, unsigned char *__restrict__ pbl_flag,
-                                                 unsigned int *__restrict__ pbl_count) {
-#ifndef FPX_VIEW_BY_VALUE
-  struct KArgs { View<R> V; GridP<R> Gp; Parts<R> P; SeqRng S; PblRec<R> Q; };   // the leading parameters as the segment holds them
-  const KArgs &ka = *(const KArgs *)(const void *)__builtin_amdgcn_kernarg_segment_ptr();
-  const View<R> &V = ka.V; const GridP<R> &Gp = ka.Gp; Parts<R> &P = const_cast<Parts<R> &>(ka.P); const SeqRng &S = ka.S; const PblRec<R> &Q = ka.Q;
-  (void)V_arg; (void)Gp_arg; (void)P_arg; (void)S_arg; (void)Q_arg;
-#else
-  const View<R> &V = V_arg; const GridP<R> &Gp = Gp_arg; Parts<R> &P = P_arg; const SeqRng &S = S_arg; const PblRec<R> &Q = Q_arg;
-#endif
-  __shared__ R hgt[kMaxNz];
-  for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
-  __syncthreads();
-  long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= numpart) return;
-  // the position travels in the same memory round trip as the due test (nearly every particle is due)
-  PState<R> ps;
-  const int itra1_in = P.itra1[s];
-  ps.xt = P.xt[s]; ps.yt = P.yt[s]; ps.zt = P.zt[s];
-  int itramem = P.itramem[s];
-  unsigned int pid = P.pid[s];
-  // ONE round trip: without this the compiler sinks each load into the branch that first needs it (itra1 -> wait -> xt ->
-  // wait -> yt -> wait -> zt ...: five dependent round trips at the head of a latency-bound kernel)
-  {
-    int due_key = itra1_in;
-    asm volatile("" : "+v"(due_key), "+v"(ps.xt), "+v"(ps.yt), "+v"(ps.zt), "+v"(itramem), "+v"(pid));
-    if (due_key != itime) { pbl_flag[s] = kKeyNotDue; return; }    // timemanager.f90:537
-  }
-  // key kKeyNotDue = not due; kKeyDone = due, finished in this kernel (above the PBL); 8 (c - 1) + 0..7 = PBL particle of regime
-  // class c = 1..4, cost bucket 7..0 (see below).
-  // The counts (particles due, length of the PBL work list) are read off the sorted keys by
-  // k_list_counts: one atomic per wave on a single address costs more than the whole kernel.
-
-  // a non-finite or out-of-grid position would index outside the fields (the reference
-  // would read arbitrary memory): terminate the particle instead
-  if (!(ps.xt >= 0. && ps.xt <= (double)V.nxmin1 && ps.yt >= 0. && ps.yt <= (double)V.nymin1) || !(ps.zt == ps.zt)) {
-    P.itra1[s] = kDead;
-    pbl_flag[s] = kKeyDone;
-    atomicAdd(&st->n_badpos, 1ull);
-    return;
-  }
-
-  // wave-uniform: is any particle of this wave new (timemanager.f90:553)?  The INIT instance runs whenever particles MAY have
-  // been released since the last step -- every step of a run with a continuous release -- but only the waves that do hold a
-  // new particle need the body with initialize() in it (a dynamically indexed array in scratch, more registers); the others
-  // run the steady-state body, so that the instance costs what the steady-state kernel costs.
-  if (INIT && __any((itramem == itime) || (itime == 0))) {
-    prep_body<R, DRYDEP, true, POLAR, NEST, false>(V, Gp, P, S, Q, s, itime, step, st, pbl_flag, hgt, ps, itramem, pid);
-    return;
-  }
-  if (POLAR && !NEST) {
-    // wave-uniform: does any particle of this wave start in a polar cap (advance.f90:161-164)?  The slots are cell-sorted, so
-    // five waves in six of a global run do not
-    if (!__any(pick_polar(V, ps.yt) != 0)) {
-      prep_body<R, DRYDEP, false, false, false, true>(V, Gp, P, S, Q, s, itime, step, st, pbl_flag, hgt, ps, itramem, pid);
-      return;
-    }
-  }
-  prep_body<R, DRYDEP, false, POLAR, NEST, false>(V, Gp, P, S, Q, s, itime, step, st, pbl_flag, hgt, ps, itramem, pid);
-}
-
-// ---------------------------------------------------------------------------
-// partoutput.f90:63-190 -- the binary particle dump.  The device builds the
-// record stream of the file (Fortran sequential unformatted: 4-byte length, payload, 4-byte
-// length) for the particles due at itime, in particle-number order, in the host's real kind H;
-// the host only streams the bytes to disk.  Arithmetic in H with FMA contraction off: the file
-// is byte-identical to the reference's.
-// ---------------------------------------------------------------------------
-// (DiagP and the interpolation itself, po_gather: fpx_partavg.hpp -- shared with the interval averages)
-
-// Both kernels run over the device slots (cell-sorted after a locality sort: coalesced state reads, gathers with
-// the locality of the particle step); the file order is the particle number, so the selection flag and the
-// record position are indexed by P.pid.
-template <typename R>
-__global__ void k_po_flags(Parts<R> P, long long n, int itime, unsigned int *__restrict__ flags) {
-  const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n) return;
-  flags[P.pid[s]] = P.itra1[s] == itime ? 1u : 0u;
-}
-
-__device__ __forceinline__ unsigned int *po_put(unsigned int *w, float v) { *w = __float_as_uint(v); return w + 1; }
-__device__ __forceinline__ unsigned int *po_put(unsigned int *w, double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  w[0] = (unsigned int)b; w[1] = (unsigned int)(b >> 32);
-  return w + 2;
-}
-
-template <typename R, typename H>
-__global__ void __launch_bounds__(kBlock) k_partoutput(View<R> V, Parts<R> P, DiagP<H> D, const unsigned int *__restrict__ recidx,
-                                                       long long n, int itime, unsigned int *__restrict__ out) {
-#pragma clang fp contract(off)
-  const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n || P.itra1[s] != itime) return;
-  const unsigned int pid = P.pid[s];
-  const int nspec = V.nspec;
-  const int reclen = 8 + (10 + nspec) * (int)sizeof(H);
-  const H zt = (H)P.zt[s];
-  PoVals<H> o;
-  po_gather<R, H, false>(V, D, itime, P.xt[s], P.yt[s], zt, o);
-  const H xlon = o.xlon, ylat = o.ylat, topo = o.topo, pvi = o.pvi, qvi = o.qvi, tti = o.tti, rhoi = o.rhoi, hmixi = o.hmixi, tri = o.tri;
-  // the record, :177-179 (32-bit words: the payload of an 8-byte build is only 4-byte aligned in the file)
-  unsigned int *w = out + (size_t)recidx[pid] * (size_t)(reclen / 4 + 2);
-  *w++ = (unsigned int)reclen;
-  *w++ = (unsigned int)P.npoint[s];
-  w = po_put(w, xlon); w = po_put(w, ylat); w = po_put(w, zt);
-  *w++ = (unsigned int)P.itramem[s];
-  w = po_put(w, topo); w = po_put(w, pvi); w = po_put(w, qvi); w = po_put(w, rhoi);
-  w = po_put(w, hmixi); w = po_put(w, tri); w = po_put(w, tti);
-  for (int ks = 0; ks < nspec; ks++) w = po_put(w, (H)P.xmass1[(size_t)ks * P.cap + s]);
-  *w++ = (unsigned int)reclen;
-}
-
-// ---------------------------------------------------------------------------
-// releaseparticles.f90:133-375 and the splitting block timemanager.f90:473-504
-// ---------------------------------------------------------------------------
-// per release point and call, prepared by the host in the host's real kind H (releaseparticles.f90:63-131)
-template <typename H>
-struct RelPoints {
-  const long long *first;    // [numpoint+1] exclusive prefix of numrel: particle k of this call belongs to point i with first[i] <= k < first[i+1]
-  const long long *gfirst;   // [numpoint] number, in the release count of the whole run over ALL ranks, of this rank's first particle of point i
-  const H *xp1, *xaux, *yp1, *yaux, *zp1, *zaux;   // [numpoint]
-  const H *mass;             // [nspec][numpoint]: xmass(i,k)/real(npart(i))*timecorrect(k)/average_timecorrect
-  const short *kindz;        // [numpoint]
-  int numpoint;
-};
-
-// free[pid] = the storage space of particle number pid+1 is vacant: itra1 /= itime (:135)
-template <typename R>
-__global__ void k_rel_flags(Parts<R> P, const unsigned int *__restrict__ slot_of_pid, long long cap, int itime, unsigned int *__restrict__ flags) {
-  const long long pid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pid >= cap) return;
-  const long long s = slot_of_pid ? (long long)slot_of_pid[pid] : pid;
-  flags[pid] = P.itra1[s] != itime ? 1u : 0u;
-}
-// target[k] = particle number (0-based) of the k-th vacant storage space
-__global__ void k_rel_targets(const unsigned int *__restrict__ flags, const unsigned int *__restrict__ rank, long long cap, long long ntotal,
-                              unsigned int *__restrict__ target) {
-  const long long pid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pid >= cap || !flags[pid]) return;
-  const unsigned int r = rank[pid];
-  if ((long long)r < ntotal) target[r] = (unsigned int)pid;
-}
-
-// a nested wind field as releaseparticles reads it (:196-226,231-341): orography and tt of time slot 2 in the host's real
-// kind, compact; rho of slot 2 from the nest's gather pack
-template <typename R, typename H>
-struct RelNests {
-  int n;
-  H eps;                              // nxmax/3.e5 (:61)
-  struct { int nx, ny; H xl, yl, xr, yr, xres, yres; const H *oro, *tt2; const R *r2; } g[kMaxNests];
-};
-
-template <typename R, typename H>
-__global__ void __launch_bounds__(kBlock) k_release(View<R> V, Parts<R> P, DiagP<H> D, RelNests<R, H> NS, RelPoints<H> RP, const unsigned int *__restrict__ target,
-                                                    const unsigned int *__restrict__ slot_of_pid, long long ntotal, int itime,
-                                                    const H *__restrict__ uniforms /* [4][ntotal] serial ran1 stream, or NULL: counter RNG */,
-                                                    int numparticlecount0, int mintime, int itsplit, int ind_rel, int nclassunc, int mquasilag,
-                                                    H *__restrict__ rho_rel, unsigned int *__restrict__ maxpid) {
-#pragma clang fp contract(off)
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= ntotal) return;
-  // release point of particle k: last i with first[i] <= k
-  int lo = 0, hi = RP.numpoint;
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (RP.first[mid] <= k) lo = mid; else hi = mid; }
-  const int i = lo;
-  const unsigned int pid = target[k];
-  const long long s = slot_of_pid ? (long long)slot_of_pid[pid] : (long long)pid;
-  H u[4];
-  if (uniforms) {
-#pragma unroll
-    for (int d = 0; d < 4; d++) u[d] = uniforms[(size_t)d * ntotal + k];
-  } else {   // four uniforms in [0,1) keyed on (seed, number of the particle in the run's release count over all ranks)
-    unsigned int o[4];
-    const unsigned long long gk = (unsigned long long)(RP.gfirst[i] + (k - RP.first[i]));
-    philox4x32((unsigned int)gk, 0x52454c45u /* "RELE" */, (unsigned int)(gk >> 32), 0u,
-               (unsigned int)V.seed, (unsigned int)(V.seed >> 32), o);
-#pragma unroll
-    for (int d = 0; d < 4; d++) u[d] = (H)((float)(o[d] >> 8) * (1.0f / 16777216.0f));
-  }
-  const int nx = V.nx, ny = V.ny, nz = V.nz;
-  double xt = (double)(RP.xp1[i] + u[0] * RP.xaux[i]);                       // :139
-  if (V.xglobal) {
-    if (xt > (double)(H)V.nxmin1) xt = xt - (double)(H)V.nxmin1;
-    if (xt < 0.) xt = xt + (double)(H)V.nxmin1;
-  }
-  const double yt = (double)(RP.yp1[i] + u[1] * RP.yaux[i]);                 // :146
-  int nc = (int)(u[2] * (H)nclassunc) + 1;                                   // :168-169
-  nc = nc < nclassunc ? nc : nclassunc;
-  H zt = RP.zp1[i] + u[3] * RP.zaux[i];                                      // :183
-  // the nest we are in (:196-206), grid coordinates and weights (:211-226)
-  int ngrid = 0;
-  for (int q = NS.n; q >= 1; q--)
-    if (xt > (double)(NS.g[q - 1].xl + NS.eps) && xt < (double)(NS.g[q - 1].xr - NS.eps) && yt > (double)(NS.g[q - 1].yl + NS.eps) &&
-        yt < (double)(NS.g[q - 1].yr - NS.eps)) { ngrid = q; break; }
-  int ix, jy, gnx = nx, gny = ny, gnxmax = D.nxmax, gnymax = D.nymax;
-  H ddx, ddy;
-  const H *g_oro = D.oro, *g_tt = nullptr;
-  const R *g_r2 = V.r2;
-  if (ngrid > 0) {
-    const auto &N = NS.g[ngrid - 1];
-    const H xtn = (H)((xt - (double)N.xl) * (double)N.xres), ytn = (H)((yt - (double)N.yl) * (double)N.yres);
-    ix = (int)xtn; jy = (int)ytn;
-    ddy = ytn - (H)jy; ddx = xtn - (H)ix;
-    gnx = N.nx; gny = N.ny; gnxmax = N.nx + 1; gnymax = N.ny + 1;      // one padding column / row reads as 0
-    g_oro = N.oro; g_tt = N.tt2; g_r2 = N.r2;
-  } else {
-    ix = (int)xt; jy = (int)yt;
-    ddy = (H)(yt - (double)(H)jy); ddx = (H)(xt - (double)(H)ix);
-  }
-  int ixp = ix + 1, jyp = jy + 1;
-  // guards (the reference would read outside its arrays): a position on the upper edges
-  ix = min(max(ix, 0), gnx - 1); jy = min(max(jy, 0), gny - 1); ixp = min(max(ixp, 0), gnxmax - 1); jyp = min(max(jyp, 0), gnymax - 1);
-  const H rddx = (H)1. - ddx, rddy = (H)1. - ddy;
-  const H p1 = rddx * rddy, p2 = ddx * rddy, p3 = rddx * ddy, p4 = ddx * ddy;
-  // mother: host layout with stride nxmax; nest: compact [nyn][nxn], the padding reads as 0
-  auto oro = [&](int a, int b) -> H {
-    if (ngrid > 0) return (a >= gnx || b >= gny) ? (H)0 : g_oro[(size_t)a + (size_t)gnx * (size_t)b];
-    return g_oro[(size_t)a + (size_t)D.nxmax * (size_t)b];
-  };
-  const H topo = p1 * oro(ix, jy) + p2 * oro(ixp, jy) + p3 * oro(ix, jyp) + p4 * oro(ixp, jyp);
-  // rho(.,.,kz,2): the r2 pack, physical slot 2; tt(.,.,kz,2): component 2 of the d3 pack (mother) / the nest's compact array
-  auto rho2 = [&](int a, int b, int kz) -> H { return (a >= gnx || b >= gny) ? (H)0 : (H)g_r2[(((size_t)b * gnx + a) * nz + (kz - 1)) * 4 + 2]; };
-  auto tt2 = [&](int a, int b, int kz) -> H {
-    if (a >= gnx || b >= gny) return (H)0;
-    if (ngrid > 0) return g_tt[(size_t)a + (size_t)gnx * ((size_t)b + (size_t)gny * (size_t)(kz - 1))];
-    return D.d3[((((size_t)b * nx + a) * nz + (kz - 1)) * 2 + 1) * 3 + 2];
-  };
-  const int kz3 = RP.kindz[i];
-  if (kz3 == 3) {                                                            // :231-273
-    const H presspart = zt;
-    H pressold = (H)0;
-    for (int kz = 1; kz <= nz; kz++) {
-      const H r = p1 * rho2(ix, jy, kz) + p2 * rho2(ixp, jy, kz) + p3 * rho2(ix, jyp, kz) + p4 * rho2(ixp, jyp, kz);
-      const H t = p1 * tt2(ix, jy, kz) + p2 * tt2(ixp, jy, kz) + p3 * tt2(ix, jyp, kz) + p4 * tt2(ixp, jyp, kz);
-      const H press = r * (H)287.05 * t / (H)100.;
-      if (kz == 1) pressold = press;
-      if (press < presspart) {
-        if (kz == 1) zt = (H)V.height[0] / (H)2.;
-        else {
-          const H dz1 = pressold - presspart, dz2 = presspart - press;
-          zt = ((H)V.height[kz - 2] * dz2 + (H)V.height[kz - 1] * dz1) / (dz1 + dz2);
-        }
-        break;
-      }
-      pressold = press;
-    }
-  }
-  if (kz3 == 2) zt = zt - topo;                                              // :278
-  if (zt < (H)1.e-6) zt = (H)1.e-6;
-  if (zt > (H)V.height[nz - 1] - (H)0.5) zt = (H)V.height[nz - 1] - (H)0.5;
-  H rhoout = (H)1.;
-  const bool dens = ind_rel == 1 || ind_rel == 3 || ind_rel == 4;
-  if (dens) {                                                                // :300-341
-    int indz = nz - 1, indzp = nz;
-    for (int ii = 2; ii <= nz; ii++)
-      if ((H)V.height[ii - 1] > zt) { indz = ii - 1; indzp = ii; break; }
-    const H dz1 = zt - (H)V.height[indz - 1], dz2 = (H)V.height[indzp - 1] - zt, dz = (H)1. / (dz1 + dz2);
-    H rhoaux[2];
-#pragma unroll
-    for (int n = 0; n < 2; n++)
-      rhoaux[n] = p1 * rho2(ix, jy, indz + n) + p2 * rho2(ixp, jy, indz + n) + p3 * rho2(ix, jyp, indz + n) + p4 * rho2(ixp, jyp, indz + n);
-    rhoout = (dz2 * rhoaux[0] + dz1 * rhoaux[1]) * dz;
-    if (rho_rel && k == RP.first[i + 1] - 1) rho_rel[i] = rhoout;            // rho_rel(i) keeps the last particle's value
-  }
-  for (int ks = 0; ks < V.nspec; ks++) {
-    H m = RP.mass[(size_t)ks * RP.numpoint + i];
-    if (dens) m = m * rhoout;
-    P.xmass1[(size_t)ks * P.cap + s] = (R)m;
-    if (P.xscav) P.xscav[(size_t)ks * P.cap + s] = (R)-1;      // releaseparticles.f90:167-171: not yet scavenged
-  }
-  P.xt[s] = xt; P.yt[s] = yt; P.zt[s] = (R)zt;
-  P.nclass[s] = nc;
-  P.npoint[s] = mquasilag == 0 ? i + 1 : (int)(numparticlecount0 + k + 1);   // :171-175
-  P.idt[s] = mintime; P.itra1[s] = itime; P.itramem[s] = itime;
-  P.itrasplit[s] = itime + V.ldirect * itsplit;
-  // the turbulent state of the storage space is whatever its last owner left; initialize() overwrites it
-  // before the first advance() (timemanager.f90:553), as in the reference
-  atomicMax(maxpid, pid);
-}
-
-// splitting, timemanager.f90:473-504
-template <typename R>
-__global__ void k_split_flags(Parts<R> P, const unsigned int *__restrict__ slot_of_pid, long long numpart, int itime, int ldirect,
-                              unsigned int *__restrict__ flags) {
-  const long long pid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pid >= numpart) return;
-  const long long s = slot_of_pid ? (long long)slot_of_pid[pid] : pid;
-  flags[pid] = (ldirect * itime >= ldirect * P.itrasplit[s]) ? 1u : 0u;
-}
-template <typename R>
-__global__ void k_split(Parts<R> P, const unsigned int *__restrict__ slot_of_pid, const unsigned int *__restrict__ flags,
-                        const unsigned int *__restrict__ rank, long long numpart, long long room, int nspec) {
-#pragma clang fp contract(off)
-  const long long pid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pid >= numpart || !flags[pid] || (long long)rank[pid] >= room) return;
-  const long long j = slot_of_pid ? (long long)slot_of_pid[pid] : pid;
-  const long long n = numpart + rank[pid];          // storage spaces behind numpart are identity-numbered
-  const int itm = P.itramem[j];
-  // itrasplit(j) = 2*(itrasplit(j)-itramem(j))+itramem(j), timemanager.f90:486 -- in 64 bits, saturated at the "never" value
-  // (the reference's default integer would overflow once the doubled interval passes 2^31 s)
-  long long its64 = 2ll * ((long long)P.itrasplit[j] - itm) + itm;
-  its64 = its64 > 999999999ll ? 999999999ll : (its64 < -999999999ll ? -999999999ll : its64);
-  const int its = (int)its64;
-  P.itrasplit[j] = its; P.itrasplit[n] = its;
-  P.itramem[n] = itm; P.itra1[n] = P.itra1[j]; P.idt[n] = P.idt[j]; P.npoint[n] = P.npoint[j]; P.nclass[n] = P.nclass[j];
-  P.xt[n] = P.xt[j]; P.yt[n] = P.yt[j]; P.zt[n] = P.zt[j];
-  P.up[n] = P.up[j]; P.vp[n] = P.vp[j]; P.wp[n] = P.wp[j];
-  P.us[n] = P.us[j]; P.vs[n] = P.vs[j]; P.ws[n] = P.ws[j];
-  P.cbt[n] = P.cbt[j];
-  for (int ks = 0; ks < nspec; ks++) {
-    const R m = P.xmass1[(size_t)ks * P.cap + j] / (R)2;
-    P.xmass1[(size_t)ks * P.cap + j] = m;
-    P.xmass1[(size_t)ks * P.cap + n] = m;
-    if (P.xscav) P.xscav[(size_t)ks * P.cap + n] = P.xscav[(size_t)ks * P.cap + j];   // the copy inherits the receptor's scavenged fraction
-  }
-}
-
-// Particle redistribution between ranks, mpi_mod.f90:661-856 (mpif_redist_part).  The message is what the reference sends,
-// in its order, as ONE buffer: nclass, npoint, itra1, idt, itramem, itrasplit (int32[n] each), xtra1, ytra1 (f64[n]), ztra1
-// (R[n]), xmass1 (R[nspec][n]).  As in the reference the turbulent velocities, cbt and xscav_frac1 do NOT travel.
-template <typename R>
-struct RedistBuf {
-  int *nclass, *npoint, *itra1, *idt, *itramem, *itrasplit;
-  double *xt, *yt;
-  R *zt, *xmass;   // xmass: [nspec][n]
-  long long n;
-  __host__ __device__ static size_t bytes(long long n, int nspec) { return (size_t)n * (6 * 4 + 2 * 8 + (size_t)(1 + nspec) * sizeof(R)); }
-  __host__ __device__ static RedistBuf at(void *base, long long n, int nspec) {
-    RedistBuf b;
-    unsigned char *q = (unsigned char *)base;
-    b.xt = (double *)q; q += (size_t)n * 8;            // the 8-byte arrays first: every array stays aligned for any n
-    b.yt = (double *)q; q += (size_t)n * 8;
-    b.zt = (R *)q; q += (size_t)n * sizeof(R);
-    b.xmass = (R *)q; q += (size_t)n * nspec * sizeof(R);
-    b.nclass = (int *)q; q += (size_t)n * 4;
-    b.npoint = (int *)q; q += (size_t)n * 4;
-    b.itra1 = (int *)q; q += (size_t)n * 4;
-    b.idt = (int *)q; q += (size_t)n * 4;
-    b.itramem = (int *)q; q += (size_t)n * 4;
-    b.itrasplit = (int *)q;
-    b.n = n;
-    return b;
-  }
-};
-// sender, :700-745: the storage spaces ll..ul = numpart-num_trans+1 .. numpart go into the message and are terminated
-template <typename R>
-__global__ void k_redist_pack(Parts<R> P, const unsigned int *__restrict__ slot_of_pid, long long first_pid, RedistBuf<R> B, int nspec) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B.n) return;
-  const long long pid = first_pid + i;
-  const long long s = slot_of_pid ? (long long)slot_of_pid[pid] : pid;
-  B.nclass[i] = P.nclass[s]; B.npoint[i] = P.npoint[s]; B.itra1[i] = P.itra1[s]; B.idt[i] = P.idt[s];
-  B.itramem[i] = P.itramem[s]; B.itrasplit[i] = P.itrasplit[s];
-  B.xt[i] = P.xt[s]; B.yt[i] = P.yt[s]; B.zt[i] = P.zt[s];
-  for (int ks = 0; ks < nspec; ks++) B.xmass[(size_t)ks * B.n + i] = P.xmass1[(size_t)ks * P.cap + s];
-  P.itra1[s] = kDead;                                  // :744
-}
-// receiver, :808-835: valid[i] = the i-th received particle is alive at itime ("we may have transferred invalid particles")
-__global__ void k_redist_valid(const int *__restrict__ itra1_tmp, long long n, int itime, unsigned int *__restrict__ valid) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) valid[i] = itra1_tmp[i] == itime ? 1u : 0u;
-}
-// the k-th valid received particle goes into the k-th storage space of 1..maxnumpart with itra1 /= itime (target[k], as
-// k_rel_targets builds it); everything else of that space stays what its last owner left
-template <typename R>
-__global__ void k_redist_unpack(Parts<R> P, const unsigned int *__restrict__ slot_of_pid, RedistBuf<R> B, int nspec, const unsigned int *__restrict__ valid,
-                                const unsigned int *__restrict__ vrank, const unsigned int *__restrict__ target, unsigned int *__restrict__ maxpid) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B.n || !valid[i]) return;
-  const unsigned int pid = target[vrank[i]];
-  const long long s = slot_of_pid ? (long long)slot_of_pid[pid] : (long long)pid;
-  P.itra1[s] = B.itra1[i]; P.npoint[s] = B.npoint[i]; P.nclass[s] = B.nclass[i]; P.idt[s] = B.idt[i];
-  P.itramem[s] = B.itramem[i]; P.itrasplit[s] = B.itrasplit[i];
-  P.xt[s] = B.xt[i]; P.yt[s] = B.yt[i]; P.zt[s] = B.zt[i];
-  for (int ks = 0; ks < nspec; ks++) P.xmass1[(size_t)ks * P.cap + s] = B.xmass[(size_t)ks * B.n + i];
-  atomicMax(maxpid, pid);
-}
-
-// readpartpositions.f90:115-148 -- warm start: the records of a dump (as partoutput writes them) -> particle SoA.
-// One lane per record; arithmetic of the coordinate conversion in the host's real kind H.
-template <typename R, typename H>
-__global__ void __launch_bounds__(kBlock) k_readpart(Parts<R> P, const unsigned int *__restrict__ raw, long long n, int nspec,
-                                                     H dx, H dy, H xlon0, H ylat0, double jul_header, double bdate, int mintime, int itrasplit0,
-                                                     const int *__restrict__ nclass_in, int *__restrict__ status /* [0] error, [1] max npoint */) {
-#pragma clang fp contract(off)
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int reclen = 8 + (10 + nspec) * (int)sizeof(H);
-  const unsigned int *w = raw + (size_t)i * (size_t)(reclen / 4 + 2);
-  auto get = [&](const unsigned int *q) -> H {
-    if (sizeof(H) == 4) return (H)__uint_as_float(q[0]);
-    return (H)__longlong_as_double((long long)(((unsigned long long)q[1] << 32) | (unsigned long long)q[0]));
-  };
-  const int hw = (int)sizeof(H) / 4;
-  if ((int)w[0] != reclen || (int)w[reclen / 4 + 1] != reclen) { atomicExch(&status[0], 1); return; }
-  const int npoint = (int)w[1];
-  const H xlonin = get(w + 2), ylatin = get(w + 2 + hw), zin = get(w + 2 + 2 * hw);
-  const int itramem_in = (int)w[2 + 3 * hw];
-  if (xlonin == (H)-9999.9) { atomicExch(&status[0], 2); return; }     // a closing record inside the file: several dumps
-  P.xt[i] = (double)((xlonin - xlon0) / dx);                              // :121-122
-  P.yt[i] = (double)((ylatin - ylat0) / dy);
-  P.zt[i] = (R)zin;
-  P.npoint[i] = npoint;
-  atomicMax(&status[1], npoint);                                          // numparticlecount, :123
-  const double julpartin = jul_header + (double)itramem_in / 86400.;      // :140-147
-  P.itramem[i] = (int)llround((julpartin - bdate) * (double)(H)86400.);
-  P.idt[i] = mintime;
-  P.itrasplit[i] = itrasplit0;                                            // :117
-  P.itra1[i] = 0;
-  P.nclass[i] = nclass_in ? nclass_in[i] : 1;
-  P.up[i] = (R)0; P.vp[i] = (R)0; P.wp[i] = (R)0; P.us[i] = (R)0; P.vs[i] = (R)0; P.ws[i] = (R)0;
-  P.cbt[i] = 1; P.pid[i] = (unsigned int)i;
-  const unsigned int *x = w + 3 + 3 * hw + 7 * hw;
-  for (int ks = 0; ks < nspec; ks++) P.xmass1[(size_t)ks * P.cap + i] = (R)get(x + ks * hw);
-  if (P.xscav) for (int ks = 0; ks < nspec; ks++) P.xscav[(size_t)ks * P.cap + i] = (R)-1;   // as after a release; the dump does not carry it
-}
-
-// ---------------------------------------------------------------------------
-// concoutput.f90:296-447 -- the sparse grid_conc writer.  For one (species, pointspec,
-// age class): class mean of the sampling grid, the non-zero test, and the run-length compression (start index
-// of every run of non-zero cells; values with a sign that flips from run to run) as two scans and two
-// element-wise kernels.  Arithmetic in float, the reference's own kind for this routine, contraction off.
-// ---------------------------------------------------------------------------
-template <typename G>
-__global__ void __launch_bounds__(kBlock) k_co_values(const G *__restrict__ grid, size_t class_stride, int nclass, long long n,
-                                                      float *__restrict__ val, unsigned int *__restrict__ nz, unsigned int *__restrict__ rs) {
-#pragma clang fp contract(off)
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  auto value = [&](long long j) -> float {          // mean_mod.f90:mean_sp, times nclassunc (concoutput.f90:323-325)
-    float xl = 0.f;
-    for (int l = 0; l < nclass; l++) xl = xl + (float)grid[(size_t)l * class_stride + j];
-    return (xl / (float)nclass) * (float)nclass;
-  };
-  const float v = value(i);
-  const bool on = v > 1.17549435e-38f;               // smallnum = tiny(0.0)
-  const bool prev = i > 0 && value(i - 1) > 1.17549435e-38f;
-  val[i] = v;
-  nz[i] = on ? 1u : 0u;
-  rs[i] = (on && !prev) ? 1u : 0u;                   // sp_zer: a run starts here
-}
-
-__global__ void __launch_bounds__(kBlock) k_co_write(const float *__restrict__ val, const unsigned int *__restrict__ nz, const unsigned int *__restrict__ rs,
-                                                     const unsigned int *__restrict__ rpos /* exclusive scan of nz */,
-                                                     const unsigned int *__restrict__ runid /* inclusive scan of rs */, long long n,
-                                                     const float *__restrict__ scale /* volume (conc, pptv) or area, per cell */, int conc, float outnum, float tot_mu,
-                                                     int idx0, int *__restrict__ wi, float *__restrict__ wr,
-                                                     const float *__restrict__ dens = nullptr, float weightmolar = 1.f) {
-#pragma clang fp contract(off)
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || !nz[i]) return;
-  const unsigned int run = runid[i];
-  const float sp_fact = (run & 1u) ? 1.f : -1.f;     // sp_fact starts at -1 and flips at every run start
-  if (rs[i]) wi[run - 1] = (int)i + idx0;
-  float r;
-  if (conc == 2) {                                     // mixing ratio, concoutput.f90:575-579
-    r = sp_fact * 1.e12f * val[i] / scale[i] / outnum * 28.97f / weightmolar / dens[i];
-  } else if (conc) {
-    const float f3 = 1.e12f / scale[i] / outnum;     // factor3d, concoutput.f90:226 (ldirect = 1)
-    r = sp_fact * val[i] * f3 / tot_mu;
-  } else r = sp_fact * 1.e12f * val[i] / scale[i];
-  wr[rpos[i]] = r;
-}
-
-// densityoutgrid, concoutput.f90:176-205: air density at the centre of every output cell from the met density of slot
-// memind(2) (the r2 pack), nearest column, linear between the two z levels around the mid height of the output layer
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_co_density(View<R> V, int nxg, int nyg, int nzg, const float *__restrict__ outheight,
-                                                       float dxout, float dyout, float outlon0, float outlat0, float dx, float dy, float xlon0, float ylat0,
-                                                       float *__restrict__ dens) {
-#pragma clang fp contract(off)
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)nxg * nyg * nzg) return;
-  const int ix = (int)(i % nxg), jy = (int)((i / nxg) % nyg), kz = 1 + (int)(i / ((long long)nxg * nyg));
-  const float halfheight = kz == 1 ? outheight[0] / 2.f : (outheight[kz - 1] + outheight[kz - 2]) / 2.f;
-  int kzz;
-  for (kzz = 2; kzz <= V.nz; kzz++)
-    if ((float)V.height[kzz - 2] < halfheight && (float)V.height[kzz - 1] > halfheight) break;
-  kzz = max(min(kzz, V.nz), 2);
-  const float dz1 = halfheight - (float)V.height[kzz - 2], dz2 = (float)V.height[kzz - 1] - halfheight, dz = dz1 + dz2;
-  float xl = outlon0 + (float)ix * dxout, yl = outlat0 + (float)jy * dyout;
-  xl = (xl - xlon0) / dx;
-  yl = (yl - ylat0) / dy;
-  const int iix = max(min((int)lroundf(xl), V.nxmin1), 0), jjy = max(min((int)lroundf(yl), V.nymin1), 0);
-  const size_t col = ((size_t)jjy * V.nx + iix) * V.nz;
-  const float r1 = (float)V.r2[(col + (kzz - 1)) * 4 + V.m2 * 2], r0 = (float)V.r2[(col + (kzz - 2)) * 4 + V.m2 * 2];
-  dens[i] = (r1 * dz1 + r0 * dz2) / dz;
-}
-
-// The wind pack blended in time for the step in flight: out0 at itime, out1 (may be NULL) at itime + lsynctime*ldirect.
-// (y(memind(1))*dt2 + y(memind(2))*dt1)*dtt, interpol_wind.f90:189-191, per grid point instead of per particle.
-template <typename R>
-__global__ void __launch_bounds__(256) k_blend_w3(const R *__restrict__ w3, const R *__restrict__ r2, long long npoint, int m1, int m2, R dt1a, R dt2a, R dtta,
-                                                  R dt1b, R dt2b, R dttb, R *__restrict__ out0, R *__restrict__ out1, R *__restrict__ rout0) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npoint) return;
-  const R *p = w3 + i * 6;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const R y1 = p[m1 * 3 + k], y2 = p[m2 * 3 + k];
-    out0[i * 3 + k] = (y1 * dt2a + y2 * dt1a) * dtta;
-    if (out1) out1[i * 3 + k] = (y1 * dt2b + y2 * dt1b) * dttb;
-  }
-  const R *q = r2 + i * 4;                     // (rho, drhodz) of the two slots, interpol_all.f90:189-198
-#pragma unroll
-  for (int k = 0; k < 2; k++) rout0[i * 2 + k] = (q[m1 * 2 + k] * dt2a + q[m2 * 2 + k] * dt1a) * dtta;
-}
-
-// After the stable sort of the slots by their 3-bit key: list length = number of keys <= 4 (PBL
-// classes), particles due = number of keys <= 6.  One wave, two 64-ary searches (5 dependent
-// loads each at 1e8 keys).
-__device__ __forceinline__ long long count_le_sorted(const unsigned char *__restrict__ keys, long long lo, long long hi, unsigned char bound) {
-  const int lane = threadIdx.x & 63;
-  while (hi > lo) {   // keys[< lo] <= bound < keys[>= hi]
-    const long long step = (hi - lo + 63) / 64;
-    const long long pos = lo + lane * step;
-    const bool le = pos < hi && keys[pos] <= bound;
-    const int cnt = __popcll(__ballot(le));    // the keys are sorted: the lanes that see <= bound are the first cnt
-    if (cnt == 0) { hi = lo; break; }
-    const long long nlo = lo + (long long)(cnt - 1) * step + 1;
-    const long long nhi = lo + (long long)cnt * step;
-    lo = nlo;
-    hi = nhi < hi ? nhi : hi;
-  }
-  return lo;
-}
-// live particles (itra1 /= -999999999) among the first n storage spaces: one atomic per block
-__global__ void __launch_bounds__(256) k_count_live(const int *__restrict__ itra1, long long n, unsigned long long *__restrict__ out) {
-  __shared__ unsigned int part[4];
-  unsigned int c = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) c += itra1[i] != kDead;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, (unsigned long long)(part[0] + part[1] + part[2] + part[3]));
-}
-// the latest time of birth (itramem, in the run's time direction) among the live particles of the first n storage spaces
-__global__ void __launch_bounds__(256) k_birth_max(const int *__restrict__ itra1, const int *__restrict__ itramem, long long n, int ldirect, long long *__restrict__ out) {
-  long long m = LLONG_MIN;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    if (itra1[i] != kDead) m = max(m, (long long)ldirect * itramem[i]);
-  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_down(m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m != LLONG_MIN) atomicMax(out, m);
-}
-// Counters of the step's work list (unsigned ints, zeroed at the start of every step):
-//   [0]     length of the whole list (all PBL particles; k_pbl_finish)
-//   [kCtrBase + 12 j + ...]: launch j of the Langevin kernel (ONE pointer gives a launch everything it needs):
-//     + c,     c = 0..3: particles of stability class c + 1 in its list (they sit at the head of the class's segment)
-//     + 4 + c: the chunk cursor of that class
-//     + 8 + c: first entry of the class's segment in the list (the list is sorted by class; the same in every launch)
-constexpr int kMaxSlices = 16, kCtrBase = 8, kCtrStride = 12, kCtrWords = kCtrBase + (kMaxSlices + 1) * kCtrStride;
-__global__ void k_list_counts(const unsigned char *__restrict__ sorted_keys, long long n, unsigned int *__restrict__ ctr, Stats *st) {
-  if (blockIdx.x != 0 || threadIdx.x >= 64) return;
-  long long upto[5];
-  upto[0] = 0;
-  for (int c = 1; c <= 4; c++) upto[c] = count_le_sorted(sorted_keys, upto[c - 1], n, (unsigned char)(8 * c - 1));
-  const long long npbl = upto[4];
-  const long long ndue = count_le_sorted(sorted_keys, npbl, n, kKeyDone);
-  if (threadIdx.x == 0) {
-    ctr[0] = (unsigned int)npbl;
-    for (int c = 1; c <= 4; c++) {
-      ctr[kCtrBase + c - 1] = (unsigned int)(upto[c] - upto[c - 1]);
-      for (int j = 0; j <= kMaxSlices; j++) ctr[kCtrBase + kCtrStride * j + 8 + c - 1] = (unsigned int)upto[c - 1];
-    }
-    st->n_due += (unsigned long long)ndue;
-  }
-}
-
-// The Langevin kernel: persistent waves, lane refill (see the header comment above).
-// Only the pass loop lives here; set-up and completion run in k_prep / k_pbl_finish
-// where all lanes are active.
-// LEAN: no dry deposition, no settling (gases).  TSW / CBLF / RNGM: see pbl_pass.
-//
-// The kernel runs as a short sequence of launches per step (Engine::step).  A lane can SUSPEND its particle between two
-// passes: the state goes into the particle's hand-over record (state PBL_CONTINUE) and the slot is appended to the next
-// launch's list, class by class (one atomic per wave and event); the next launch continues it.  Three rules, all decided
-// per wave:
-//  * class purity: the list is sorted by stability class, every class has a chunk cursor of its own and a wave draws from
-//    ONE class at a time.  When that class has no chunk left the wave runs on with what it holds, without refilling,
-//    until fewer than drain_lanes lanes are busy, suspends those particles and moves to the next class with all lanes
-//    free -- so the lanes of a wave always run ONE branch of hanna_short / cbl (before: for up to 300 passes after the
-//    cursor had crossed a class boundary the waves ran both classes' code for the sake of a few long-lived particles:
-//    12 % of the hanna_short and 7 % of the CBL sub-steps at 1.25e7 particles);
-//  * drain: the same rule after the last class -- the wave hands its last particles on and ends; the next launch packs
-//    the leftovers of all waves densely (before: the last tenth of a launch ran with waves of a lane or two);
-//  * pass budget (cap_passes > 0, optional): at most cap_passes passes per particle and launch.
-// The last launch of the sequence has no next list (drain_lanes = 0, cap_passes = 0): it runs everything to the end.
-// A particle's random numbers are keyed on (particle number, step, draw index) and the draw index travels in the record:
-// suspending does not change a bit of the result (tests/test_gpu_parity.py::test_time_slices_do_not_change_a_bit).
-// SUSP = false: the instance of a step with ONE launch -- nothing can be suspended or resumed, and the refill, which runs with two
-// lanes of the wave, carries none of that (the hand-over of suspended particles cost 2 % of the kernel's instructions at 1e8).
-template <typename R, bool LEAN, int TSW, int CBLF, int RNGM, bool SUSP = false>
-__global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : FPX_LOOP_WAVES) k_pbl_loop(View<R> V_arg, Parts<R> P_arg, PblRec<R> Q_arg, int itime, unsigned int step, Stats *st,
-                                                     const unsigned int *__restrict__ pbl_list,
-                                                     unsigned int *__restrict__ blk,
-                                                     int cap_passes, int drain_lanes,
-                                                     unsigned int *__restrict__ next_list) {
-  // (the View alone: k_pbl_loop<double, true, 1, 1, 2> 157 -> 153 VGPRs, 49 -> 19 spilled SGPRs, 24 B -> no scratch; -0.5 to -1 % of the launch)
-#if !defined(FPX_VIEW_BY_VALUE) && !defined(FPX_LOOP_ONLY_VIEW)
-  struct KArgs { View<R> V; Parts<R> P; PblRec<R> Q; };
-  const KArgs &ka = *(const KArgs *)(const void *)__builtin_amdgcn_kernarg_segment_ptr();
-  const View<R> &V = ka.V; const Parts<R> &P = ka.P; const PblRec<R> &Q = ka.Q;
-  (void)V_arg; (void)P_arg; (void)Q_arg;
-#else
-  FPX_VIEW_FROM_KERNARG(V, V_arg);
-  const Parts<R> &P = P_arg; const PblRec<R> &Q = Q_arg;
-#endif
-  // blk: this launch's block of the counters (see k_list_counts): per class c the first blk[c] entries of the class's segment
-  // [blk[8 + c], ...) of pbl_list, the class's chunk cursor blk[4 + c]; the next launch's block follows
-  const unsigned int *mine = blk;
-  unsigned int *next_cnt = blk + kCtrStride;
-  // (only the current class's length and segment start live in scalar registers, not all four: twelve registers through the
-  // whole kernel were taken from the polynomial constants of the fine loop, which then came back through v_readlane in
-  // every sub-step)
-  // A short list (the later launches): only as many blocks as it fills take part, so that its waves are spread over the
-  // CUs one block each instead of three to a SIMD on some and none on others (a pass of a wave alone on its SIMD takes a
-  // third of the time).
-  const unsigned int nlist_all = mine[0] + mine[1] + mine[2] + mine[3];
-  if ((unsigned long long)blockIdx.x * kBlock >= (unsigned long long)nlist_all) return;
-  const bool can_suspend = SUSP && (drain_lanes > 0 || cap_passes > 0);
-  // dynamic LDS: [S_COUNT][kBlock] stash (per-lane pass-level state, see Stash) + the height column,
-  // sized by the host (loop_smem_bytes) so that three blocks fit one CU for the usual nz
-  extern __shared__ __align__(16) unsigned char fpx_loop_smem[];
-  static_assert(kStashStride == kBlock, "stash layout is one column per thread of the block");
-  R *stash_mem = reinterpret_cast<R *>(fpx_loop_smem);
-  R *hgt = stash_mem + stash_slots<R>(LEAN, SUSP) * kStashStride;   // (the host sizes the block's LDS alike: loop_smem_bytes)
-  for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
-  // the block's copy of the lookup tables of the fp64 logarithm and exponential (m_log_abs, m_exp_tab): 768 B
-  __shared__ double lds_tab[sizeof(R) == 8 ? kLdsTabDoubles : 1];
-  if (sizeof(R) == 8)
-    for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
-  // ... and, where the block has the room (the fp64 gas kernels), of the table of the error-function pair (m_erf_tab2): 2.4 KB,
-  // static like the tables above, so the host's rule for the dynamic part (loop_smem_bytes) does not change.  With it a
-  // one-launch fp64 gas kernel has 19 x 2 KB + 8 nz + 768 B + 2496 B per block: 43.3 KB at nz = 138, three blocks per CU
-  // (53248 B each) up to nz = 1380.
-  constexpr bool ERFTAB = stash_has_erf_tab<R>(LEAN);
-  __shared__ __align__(16) double lds_erft[ERFTAB ? kErfcxIntervals * kErfcxRow : 2];
-  if (ERFTAB)
-    for (int k = threadIdx.x; k < kErfcxIntervals * kErfcxRow; k += blockDim.x) lds_erft[k] = kErfcxTab[k];
-  __syncthreads();
-  typedef typename StashFor<R, ERFTAB>::type stash_t;
-  const stash_t S = make_stash<R, ERFTAB>((typename Stash<R>::lds_ptr)(stash_mem + threadIdx.x), (lds_tab_ptr)lds_tab, (lds_erft_ptr)lds_erft);
-  const int lane = threadIdx.x & 63;
-  const TimeW<R> W = time_weights(V, itime);   // wave-uniform
-  const R cap_r = cap_passes > 0 ? (R)cap_passes : (R)1e30;
-
-  // The list is in slot order, i.e. sorted by grid cell after a locality sort.  A wave takes
-  // CHUNKS of consecutive entries (one atomic per chunk) and refills its lanes from its own
-  // chunk, so the particles a wave works on at any moment come from neighbouring cells
-  // (same mixing height, same stability regime, shared cache lines).
-  // 64 entries per claim: with larger chunks (nlist/(8*nwaves) = 2000 entries at 1e8 was tried first) the kernel
-  // ended half a chunk's worth of work -- tens of milliseconds -- after the list ran out, most waves idle;
-  // measured 429 -> 395 ms.  One atomic per 64 refills is still negligible.
-  unsigned int cur = 0, end = 0;     // wave-uniform: the unread part of the wave's chunk
-  unsigned int cbase = 0;            // wave-uniform: first entry of the chunk
-  unsigned int ahead = 0;            // lane l: entry cbase + l of the list (the whole chunk, read with the claim)
-  bool out_of_chunks = false;        // wave-uniform
-  int wcls = 0;                      // wave-uniform: class (0..3) the wave draws its particles from
-  unsigned int cls_out = 0u;         // wave-uniform: that class has no chunk left
-  unsigned int cls_n = mine[0], cls_seg = mine[8];   // wave-uniform: length and first entry of that class's segment (read again when the wave moves on)
-  // The wave-uniform values that are only read where a chunk is claimed -- once per 64 particles -- are kept in VECTOR
-  // registers (the kernel has nine to spare; the empty asm makes them lane values for the compiler), not in scalar ones: the
-  // scalar file is what the fine loop's polynomial constants live in, and every scalar held across the loop came back as a
-  // v_readlane in each sub-step (+0.8 % VALU instructions at 1e8 with all of these in scalar registers).
-#define FPX_IN_VGPR(x) asm volatile("" : "+v"(x))
-  if (SUSP) { FPX_IN_VGPR(cbase); FPX_IN_VGPR(cls_out); FPX_IN_VGPR(cls_n); FPX_IN_VGPR(cls_seg); }
-#ifdef FPX_LANE_STATS
-  const unsigned long long t_s = wall_clock64();   // 100 MHz; timeline of the wave: start, list exhausted, end
-  unsigned long long t_x = 0;
-#endif
-
-  bool have = false;
-  unsigned int s = 0, pid = 0;
-  double xt = 0, yt = 0;
-  R zt = 0, wp = 0;
-  int ldt = 0;
-  short icbt = 1;
-  int lvl = 0;                       // the level of the lane's last pass, where the next pass starts its level search (find_level_from); 0: none
-  LoopCtx<R> A;
-
-  // the lanes of `who` (all of them hold a particle) hand their particles on: record written, slot appended to the next
-  // launch's list in the segment of the wave's class
-  auto write_record = [&](int state, int indz) {
-    PblRecord<R> *rp = Q.rec + s;
-    rp->v[0] = S.get(S_DX); rp->v[1] = S.get(S_DY); rp->v[2] = S.get(S_DAW); rp->v[3] = S.get(S_DCW);
-    rp->v[4] = zt; rp->v[5] = S.get(S_UP); rp->v[6] = S.get(S_VP); rp->v[7] = wp;
-    if (state == PBL_CONTINUE) {
-      rp->v[8] = S.get(S_UST);      // hanna.f90:43 may have floored it; v[9..12] stay as k_prep wrote them
-    } else {
-      rp->v[8] = S.get(S_U); rp->v[9] = S.get(S_V); rp->v[10] = S.get(S_W);
-    }
-    rp->i[0] = A.nrand; rp->i[1] = ldt;
-    rp->i[2] = pbl_pack(state, icbt, indz, A.ngrid, abs(A.itimec - itime));
-    if (!LEAN && V.drydep) Q.tdep[s] = S.get(S_TDEP);
-  };
-  auto suspend = [&](bool mine_goes) {   // convergent: every lane of the wave calls it
-    const unsigned long long sm = __ballot(mine_goes);
-    if (sm == 0ull) return;
-    if (mine_goes) { write_record(PBL_CONTINUE, lvl); have = false; }
-    unsigned int base = 0;
-    if (lane == 0) base = atomicAdd(next_cnt + wcls, (unsigned int)__popcll(sm));
-    base = __builtin_amdgcn_readfirstlane(base);
-    const unsigned int seg = mine[8 + wcls];
-    if (mine_goes) next_list[seg + base + (unsigned int)__popcll(sm & ((1ull << lane) - 1ull))] = s;
-  };
-
-  for (;;) {
-    FPX_LANES(st, 10);
-    unsigned long long need = __ballot(!have);
-    if (need != 0ull && !out_of_chunks) {
-      if (!SUSP) {
-        // One launch, nothing to suspend: the class segments of the list are adjacent, so the wave walks the list as ONE
-        // sequence with ONE cursor (chunks may straddle a class boundary, as in round 3)
-        if (cur >= end) {
-          unsigned int c = 0;
-          if (lane == 0) c = atomicAdd(blk + 4, 1u);
-          c = __builtin_amdgcn_readfirstlane(c);
-          const unsigned long long c0 = (unsigned long long)c * 64u;
-          if (c0 >= nlist_all) {
-            out_of_chunks = true;
-#ifdef FPX_LANE_STATS
-            t_x = wall_clock64();
-#endif
-          } else {
-            cur = (unsigned int)c0;
-            cbase = cur;
-            end = min(cur + 64u, nlist_all);
-            ahead = pbl_list[min(cur + (unsigned int)lane, nlist_all - 1u)];
-          }
-        }
-      } else
-      while (cur >= end && !out_of_chunks) {   // wave-uniform: take the next chunk of the wave's class
-        if (__builtin_amdgcn_readfirstlane(cls_out) == 0u) {
-          const unsigned int nseg = __builtin_amdgcn_readfirstlane(cls_n), seg = __builtin_amdgcn_readfirstlane(cls_seg);
-          const unsigned int kk = (nseg + 63u) >> 6;       // this class's length in chunks
-          unsigned int c = 0;
-          if (lane == 0) c = atomicAdd(blk + 4 + wcls, 1u);
-          c = __builtin_amdgcn_readfirstlane(c);
-          if (c < kk) {
-            cur = seg + c * 64u;
-            cbase = cur; FPX_IN_VGPR(cbase);
-            end = min(cur + 64u, seg + nseg);
-            ahead = pbl_list[min(cur + (unsigned int)lane, end - 1u)];
-            break;
-          }
-          cls_out = 1u; FPX_IN_VGPR(cls_out);
-        }
-        // The wave's class has no chunk left.  A launch that can hand particles on keeps the wave on what it holds -- no
-        // refill, so no second class in the wave -- until fewer than drain_lanes lanes are busy, then suspends those and
-        // moves on to the next class with all lanes free; the last launch moves on at once (and mixes).
-        if (can_suspend) {
-          const int live = __popcll(__ballot(have));
-          if (live > 0 && live >= drain_lanes) break;
-          suspend(have);
-          need = ~0ull;
-        }
-        wcls++;
-        cls_out = 0u; FPX_IN_VGPR(cls_out);
-        if (wcls < 4) { cls_n = mine[wcls]; cls_seg = mine[8 + wcls]; FPX_IN_VGPR(cls_n); FPX_IN_VGPR(cls_seg); }
-        if (wcls == 4) {
-          out_of_chunks = true;
-#ifdef FPX_LANE_STATS
-          t_x = wall_clock64();
-#endif
-        }
-      }
-      if (cur < end) {
-        // A refill is ONE memory round trip: the list entry comes from the chunk read above (cross-lane), everything else
-        // depends on the slot only and is requested together -- grid and mixing height travel in the record k_prep wrote.
-        // (Before: list entry -> state -> mixing height -> six stash values one after the other = nine dependent round
-        // trips, with two of the wave's lanes active, in 60 % of the passes.)
-        const unsigned int rank = __popcll(need & ((1ull << lane) - 1ull));
-        const unsigned int my = cur + rank;
-        const unsigned int s_new = (unsigned int)__builtin_amdgcn_ds_bpermute((int)(min(my - cbase, 63u) << 2), (int)ahead);   // all lanes
-        if (!have && my < end) {
-          FPX_LANES(st, 8);
-          s = s_new;
-          const PblRecord<R> *rp = Q.rec + s;
-          const double l_xt = P.xt[s], l_yt = P.yt[s];
-          const unsigned int l_pid = P.pid[s];
-          const int r_nrand = rp->i[0], r_ldt = SUSP ? rp->i[1] : 0, r_pk = rp->i[2];
-          const R r_ust = rp->v[8], r_wst = rp->v[kRecWst], r_ol = rp->v[10], r_trans = rp->v[11], r_h = rp->v[12];
-          // the step's invariants as k_prep took them, same line as the above (a launch that may meet a suspended particle, whose
-          // v[0..7] are in use, takes them here instead: step_invariants below)
-          const R r_iaux = SUSP ? (R)0 : rp->v[0], r_sigu = SUSP ? (R)0 : rp->v[1], r_itlu = SUSP ? (R)0 : rp->v[2];
-          // a fresh particle's state is in the particle arrays, a suspended one's in its record: both are requested
-          // (one round trip either way; suspended particles are the few)
-          R l_zt = P.zt[s], l_wp = P.wp[s], l_up = P.up[s], l_vp = P.vp[s];
-          int l_idt = P.idt[s];
-          short l_cbt = P.cbt[s];
-          const R c_dx = SUSP ? rp->v[0] : (R)0, c_dy = SUSP ? rp->v[1] : (R)0, c_daw = SUSP ? rp->v[2] : (R)0, c_dcw = SUSP ? rp->v[3] : (R)0;
-          const R c_zt = SUSP ? rp->v[4] : (R)0, c_up = SUSP ? rp->v[5] : (R)0, c_vp = SUSP ? rp->v[6] : (R)0, c_wp = SUSP ? rp->v[7] : (R)0;
-          int l_npoint = 0;
-          if (!LEAN && V.lsettling) l_npoint = P.npoint[s];
-          R c_tdep = (R)0;
-          if (SUSP && !LEAN && V.drydep) c_tdep = Q.tdep[s];
-          __builtin_amdgcn_sched_barrier(0);   // every load above is issued before the first value is used
-          const bool resumed = SUSP && pbl_state(r_pk) == PBL_CONTINUE;
-          xt = l_xt; yt = l_yt; pid = l_pid;
-          zt = resumed ? c_zt : l_zt; wp = resumed ? c_wp : l_wp;
-          ldt = resumed ? r_ldt : l_idt;
-          icbt = resumed ? (short)pbl_icbt(r_pk) : l_cbt;
-          lvl = pbl_indz(r_pk);   // k_prep's level of the particle's height (FRESH), or that of its last pass (CONTINUE): a guess, tested before use
-          {
-            R ddx, ddy;
-            adv_begin_known(V, xt, yt, pbl_ngrid(r_pk), r_h, A, ddx, ddy);
-            A.itimec = SUSP ? itime + pbl_elapsed(r_pk) * V.ldirect : itime;   // FRESH: elapsed = 0
-            A.nrand = r_nrand;
-            A.nsp = 0;
-            if (!LEAN && V.lsettling) {
-              const int nsp = settling_species(V, l_npoint);
-              const SettleSpec<R> sp = settle_spec(V, nsp);
-              S.put(S_SET_NUM, spec_row(V, nsp).density > (R)0 ? sp.num : (R)0);   // density(nsp) <= 0: no settling (advance.f90:525)
-              S.put(S_SET_DQ6, sp.dq6); S.put(S_SET_V0, sp.vset);
-              S.put(S_SETCELL, (R)settling_column(V, (R)xt, (R)yt));   // < nx*ny: exact in R (f32: grids up to 2^24 columns, checked at fpx_create)
-              if (sizeof(R) == 4) S.put(S_RT_TAG, (R)0);
-            }
-            S.put(S_DDX, ddx); S.put(S_DDY, ddy);
-          }
-          S.put(S_DX, resumed ? c_dx : (R)0); S.put(S_DY, resumed ? c_dy : (R)0);
-          S.put(S_DAW, resumed ? c_daw : (R)0); S.put(S_DCW, resumed ? c_dcw : (R)0);
-          S.put(S_W, (R)0);
-          S.put(S_UP, resumed ? c_up : l_up); S.put(S_VP, resumed ? c_vp : l_vp);
-          S.put(S_WST2, r_wst * r_wst);
-          S.put(S_OL, r_ol);
-          S.put(S_TRANS, (r_wst * r_wst * r_wst) * r_trans);   // (wst**3)*transition, cbl.f90:103-104
-          if (SUSP) S.put(S_NPASS, (R)0);
-          if (!LEAN && V.drydep) S.put(S_TDEP, resumed ? c_tdep : (R)0);
-          if (SUSP) {
-            __builtin_amdgcn_sched_barrier(0);   // last, with everything else of the refill stored: the helper's temporaries do not meet the loaded values
-            const StepInv<R> I = step_invariants(r_h, r_ol, r_ust, r_wst, S);
-            S.put(S_UST, I.ust); S.put(S_IAUX, I.iaux); S.put(S_SIGU, I.sigu); S.put(S_ITLU, inv_pack_itlu(I));
-          } else {
-            S.put(S_UST, r_ust); S.put(S_IAUX, r_iaux); S.put(S_SIGU, r_sigu); S.put(S_ITLU, r_itlu);
-          }
-          have = true;
-        }
-        cur = min(cur + (unsigned int)__popcll(need), end);
-      }
-    }
-    if (!__any(have)) {
-      if (out_of_chunks) break;   // no lane has work and the list is used up: the grid drains
-      continue;                   // chunk ran dry mid-refill: take the next one
-    }
-    bool over_budget = false;
-    if (have) {
-      Rng<R, RNGM> G;
-      make_rng(V, pid, step, G);
-      const int rc = pbl_pass<R, !LEAN, !LEAN, TSW, CBLF>(V, hgt, G, W, itime, xt, yt, zt, wp, ldt, icbt, A, S, lvl, st, RecCold<R>{Q.rec[0].v, s});
-      R npass = (R)0;
-      if (SUSP) { npass = S.get(S_NPASS) + (R)1; S.put(S_NPASS, npass); }
-      if (rc != PBL_CONTINUE) {
-        FPX_LANES(st, 9);
-        // the particle's state at the end of its last pass goes into its hand-over record: one contiguous line;
-        // k_pbl_finish writes the particle arrays from it
-        write_record(rc, lvl);
-        have = false;
-      } else over_budget = SUSP && npass >= cap_r;
-    }
-    if (SUSP && cap_passes > 0) suspend(over_budget);
-  }
-#ifdef FPX_LANE_STATS
-  if (lane == 0) {
-    const unsigned long long t_e = wall_clock64();
-    atomicAdd(&st->lanes[11][0], 1ull);
-    atomicAdd(&st->lanes[11][1], t_x - t_s);            // sum over waves: start -> list exhausted
-    atomicAdd(&st->lanes[12][0], t_e - t_s);            // sum over waves: start -> end
-    atomicMax(&st->lanes[12][1], t_e - t_s);            // longest wave
-    atomicMax(&st->lanes[13][0], ~(t_x - t_s));         // ~(first wave to see the list exhausted)
-    atomicMax(&st->lanes[13][1], t_e - t_x);            // longest drain of one wave
-  }
-#endif
-}
-
-// diagnostics: the fp64 math helpers of fpx_device.hpp on plain arrays (fpx_math_probe)
-__global__ void k_math_probe(int fn, const double *__restrict__ x, double *__restrict__ y, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double v = x[i];
-  double r = 0.0, c, ic2;
-  switch (fn) {
-    case 0: r = m_expp(v); break;
-    case 1: r = m_logp(v); break;
-    case 2: r = m_sqrtp(v); break;
-    case 3: r = m_rcp(v); break;
-    case 4: r = m_rsqrt(v); break;
-    case 5: m_cuberoot_parts(v, c, ic2); r = c; break;
-    case 7: r = m_erf_e(v, m_expp(-(v * v))); break;
-    case 8: r = m_pow08(v); break;
-    case 9: r = m_exp_tab(v, &kExpTab[0]); break;
-    case 10: r = m_log_abs(v); break;
-    case 11: r = m_rcbrt(v); break;
-    // 15 .. 18: the raw seeds the root helpers refine -- v_rcp_f64, v_rsq_f64, and the f32 paths of x**(-1/3) and x**(-1/5)
-    case 15: r = __builtin_amdgcn_rcp(v); break;
-    case 16: r = __builtin_amdgcn_rsq(v); break;
-    case 17: r = m_rcbrt_seed(__log2f((float)v)); break;
-    case 18: r = m_rfifth_seed(v); break;
-    // 19 .. 27, 31: the forms with two quadratic steps, whatever FPX_NEWTON_HW / FPX_NEWTON_F32 make the kernels call
-    case 19: r = m_rcp_q2(v); break;
-    case 20: r = m_rsqrt_q2(v); break;
-    case 21: r = m_sqrtp_q2(v); break;
-    case 22: m_sqrt_rsqrt_q2(v, c, ic2); r = c; break;
-    case 23: m_sqrt_rsqrt_q2(v, c, ic2); r = ic2; break;
-    case 24: r = m_rcbrt_q2(v, m_rcbrt_seed(__log2f((float)v))); break;
-    case 25: r = m_pow08_as<false>(v); break;
-    case 26: m_cuberoot_parts_as<false>(v, c, ic2); r = c; break;
-    case 27: m_cuberoot_parts_as<false>(v, c, ic2); r = ic2; break;
-    case 31: r = m_divf_with(3.0, v, m_rcp_q2(v)); break;
-    // 28 .. 30: the forms the kernels call that have no number above -- m_sqrt_rsqrt's two results, m_divf as 3/x
-    case 28: m_sqrt_rsqrt(v, c, ic2); r = c; break;
-    case 29: m_sqrt_rsqrt(v, c, ic2); r = ic2; break;
-    case 30: r = m_divf(3.0, v); break;
-    default: m_cuberoot_parts(v, c, ic2); r = ic2; break;
-  }
-  y[i] = r;
-}
-
-// diagnostics (fpx_math_probe, fn 12 .. 14): the error function with E = exp(-x*x) handed in, x = in[0 .. n), E = in[n .. 2n) --
-// 12: the polynomial form (m_erf_e2), 13: the table form with the table in LDS as in k_pbl_loop (m_erf_tab2); both take the
-// point as either member of the pair, which must agree, else NaN -- and 14: exp(-x/2) with the factor in the constants
-// (m_exp_tab_nh; x = in[0 .. n) alone).
-__global__ void __launch_bounds__(kBlock) k_erf_probe(int fn, const double *__restrict__ in, double *__restrict__ y, long long n) {
-  __shared__ __align__(16) double lds_erft[kErfcxIntervals * kErfcxRow];
-  for (int k = threadIdx.x; k < kErfcxIntervals * kErfcxRow; k += blockDim.x) lds_erft[k] = kErfcxTab[k];
-  __syncthreads();
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double v = in[i];
-  if (fn == 14) { y[i] = m_exp_tab_nh(v, &kExpTab[0]); return; }
-  const double E = in[n + i];
-  const long long j = i + 1 < n ? i + 1 : 0;   // the pair's other member: a neighbour
-  const double v2 = in[j], E2 = in[n + j];
-  double a, b, c, d;
-  if (fn == 12) { m_erf_e2(v, E, v2, E2, a, b); m_erf_e2(v2, E2, v, E, c, d); }
-  else { m_erf_tab2(v, E, v2, E2, (lds_erft_ptr)lds_erft, a, b); m_erf_tab2(v2, E2, v, E, (lds_erft_ptr)lds_erft, c, d); }
-  const bool same = a == d || (a != a && d != d);
-  y[i] = same ? a : __builtin_nan("");
-}
-
-// diagnostics (fpx_hanna_probe): hanna() of a Langevin pass on plain arrays, ten values per point -- sigu, sigv, sigw, dsigwdz, 1/tlu,
-// 1/tlv, tlw, floored ust, regime, -h/ol > 5.  which = 0: the way the engine goes -- step_invariants() with the plain math as in
-// k_prep, packed as the record carries them, through stash slots and StashInv with the stash's LDS tables as in k_pbl_loop;
-// which = 1: hanna() as it stands.  One launch per form, so that the compiler cannot share a subexpression between them.
-__global__ void __launch_bounds__(kBlock) k_hanna_probe(int which, const double *__restrict__ in, double *__restrict__ out, long long n) {
-  __shared__ double slots[(S_ITLU + 1) * kStashStride];
-  __shared__ double lds_tab[kLdsTabDoubles];
-  for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
-  __syncthreads();
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double h = in[5 * i], ol = in[5 * i + 1], ust = in[5 * i + 2], wst = in[5 * i + 3], z = in[5 * i + 4];
-  double *o = out + 10 * i;
-  Turb<double> T;
-  T.ol = ol; T.h = h; T.zeta = z / h; T.sigw = 0.; T.dsigwdz = 0.;
-  if (which == 0) {
-    const Stash<double> S{(Stash<double>::lds_ptr)(slots + threadIdx.x), (lds_tab_ptr)lds_tab};
-    const StepInv<double> I = step_invariants(h, ol, ust, wst, PlainMath());
-    S.put(S_UST, I.ust); S.put(S_OL, ol); S.put(S_WST2, wst * wst);
-    S.put(S_IAUX, I.iaux); S.put(S_SIGU, I.sigu); S.put(S_ITLU, inv_pack_itlu(I));
-    const StashInv<double> SI{S};
-    T.ust = S.get(S_UST);
-    double itlu, itlv;
-    hanna(T, z, SI, S, itlu, itlv);
-    o[0] = T.sigu; o[1] = T.sigv; o[2] = T.sigw; o[3] = T.dsigwdz; o[4] = itlu; o[5] = itlv; o[6] = T.tlw;
-    o[7] = T.ust; o[8] = (double)SI.regime(); o[9] = SI.deep() ? 1. : 0.;
-  } else {
-    T.ust = ust; T.wst = wst;
-    const bool deep = -h / T.ol > 5.;
-    hanna(T, z, Stash<double>{nullptr, (lds_tab_ptr)lds_tab});   // (the pass called hanna() with the stash's tables)
-    o[0] = T.sigu; o[1] = T.sigv; o[2] = T.sigw; o[3] = T.dsigwdz; o[4] = m_rcp(T.tlu); o[5] = m_rcp(T.tlv); o[6] = T.tlw;
-    o[7] = T.ust; o[8] = h / m_abs(ol) < 1. ? 0. : ol < 0. ? 1. : 2.; o[9] = deep ? 1. : 0.;
-  }
-}
-
-// diagnostics (fpx_cbl_probe): cbl() of a fine sub-step on plain arrays, called as the fp64 gas kernels of k_pbl_loop call it -- a
-// StashErfTab over the block's LDS copies of the exp table and the error-function table.  in[10i .. 10i+9] = wp, z (= zp/h), wt
-// (= wst^3 * transition), 1/h, rhograd/rhoa, sigmaw, 1/sigmaw, dsigmawdz, tlw, ldirect; out[3i .. 3i+2] = ath, bth, flagrein.
-// FORM 0: the body in the reference's dimensional variables, 1: the normalised one; an instance each, whatever FPX_CBL_NORMALISED is.
-template <int FORM>
-__global__ void __launch_bounds__(kBlock) k_cbl_probe(const double *__restrict__ in, double *__restrict__ out, long long n) {
-  __shared__ double lds_tab[kLdsTabDoubles];
-  __shared__ __align__(16) double lds_erft[kErfcxIntervals * kErfcxRow];
-  for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
-  for (int k = threadIdx.x; k < kErfcxIntervals * kErfcxRow; k += blockDim.x) lds_erft[k] = kErfcxTab[k];
-  __syncthreads();
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double *x = in + 10 * i;
-  const StashErfTab S = make_stash<double, true>(nullptr, (lds_tab_ptr)lds_tab, (lds_erft_ptr)lds_erft);
-  double ath = 0., bth = 0.;
-  int flagrein = 0;
-  cbl<FORM>(S, x[9] < 0. ? -1 : 1, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], ath, bth, flagrein);
-  out[3 * i] = ath; out[3 * i + 1] = bth; out[3 * i + 2] = (double)flagrein;
-}
-
-// diagnostics (fpx_find_level_probe): the level search of a Langevin pass on plain arrays, the height column in LDS as in k_pbl_loop.
-// which = 0: find_level_from with the point's guess (0: none); which = 1: find_level and the two heights the pass read after it.
-// One launch per form.  idx[i] = the level, zz[2i], zz[2i+1] = height(indz), height(indz+1).
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_find_level_probe(int which, const R *__restrict__ height, int nz, const R *__restrict__ z,
-                                                            const int *__restrict__ guess, long long n, int *__restrict__ idx, R *__restrict__ zz) {
-  __shared__ R hgt[kMaxNz];
-  for (int k = threadIdx.x; k < nz; k += blockDim.x) hgt[k] = height[k];
-  __syncthreads();
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const R zt = z[i];
-  R zlo, zhi;
-  int k;
-  if (which == 0) k = find_level_from(hgt, nz, zt, guess[i], zlo, zhi);
-  else { k = find_level(hgt, nz, zt); zlo = hgt[k - 1]; zhi = hgt[k]; }
-  idx[i] = k; zz[2 * i] = zlo; zz[2 * i + 1] = zhi;
-}
-
-// completion of ONE boundary-layer particle: label 700 if it left the PBL, sigmas for the mesoscale term, label 99 to the end
-// of advance(), epilogue.  A function of its own for the same reason as prep_body: on a grid with polar caps the waves without
-// a particle in a cap run the mother-grid instance (POLAR = false, CAPCHECK), the others the polar one.
-template <typename R, bool DRYDEP, bool POLAR, bool NEST, bool CAPCHECK>
-__device__ __forceinline__ void finish_body(const View<R> &V, const GridP<R> &Gp, Parts<R> &P, unsigned int s, const PblRecord<R> &rec, R tdep,
-                                            int itime, unsigned int step, Stats *st, const R *hgt, DryDep<R> *dry) {
-  constexpr bool MOTHER = !POLAR && !NEST;
-  const int pk = rec.i[2];
-  PState<R> ps;
-  ps.xt = P.xt[s]; ps.yt = P.yt[s]; ps.zt = rec.v[4];
-  ps.up = rec.v[5]; ps.vp = rec.v[6]; ps.wp = rec.v[7];
-  ps.usigold = P.us[s]; ps.vsigold = P.vs[s]; ps.wsigold = P.ws[s];
-  ps.ldt = rec.i[1]; ps.icbt = (short)pbl_icbt(pk);
-  Rng<R> G;
-  make_rng(V, P.pid[s], step, G);
-  const TimeW<R> W = time_weights(V, itime);
-  AdvCtx<R> A;
-  {
-    // same cell as at entry: the horizontal position does not change inside the loop
-    AdvCtx<R> A0;
-    adv_begin<R, MOTHER>(V, ps.xt, ps.yt, ps.zt, itime, 0, A0);
-    A = A0;
-  }
-  if (V.lsettling) A.nsp = settling_species(V, P.npoint[s]);
-  A.dxsave = rec.v[0]; A.dysave = rec.v[1]; A.dawsave = rec.v[2]; A.dcwsave = rec.v[3];
-  A.u = rec.v[8]; A.v = rec.v[9]; A.w = rec.v[10];
-  A.nrand = rec.i[0]; A.itimec = itime + pbl_elapsed(pk) * V.ldirect;
-  const int rc = pbl_state(pk), indz = pbl_indz(pk);   // (every particle of the list is DONE or ESCAPED when the last time slice has run)
-  R usig = (R)0, vsig = (R)0, wsig = (R)0;
-  R prob[kMaxSpec];
-  {
-    Cell<R> C;
-    cell_setup(C, A.ix, A.jy, A.ixp, A.jyp, A.xr, A.yr);
-    if (rc == PBL_ESCAPED) {
-      above_step(V, hgt, G, W, itime, ps.xt, ps.yt, ps.zt, ps.wp, ps.ldt, A, usig, vsig, wsig);
-    } else {
-      level_pair_sigma(V, fld_of(V, A.ngrid), C, W, indz, usig, vsig, wsig);   // advance.f90:604-606
-    }
-    // advance.f90:582-599 in closed form: prob(ks) = 1 - exp(-vdepo(ks) * T / (2*href)), T = the loop's sum of |dt| over the
-    // passes that ended below 2*href (pbl_pass); the deposition velocity of the particle's cell, as every pass saw it
-#pragma unroll
-    for (int ks = 0; ks < kMaxSpec; ks++) {
-      prob[ks] = (R)0;
-      if (DRYDEP && ks < V.nspec && V.drydepspec[ks]) {
-        const R vdepo = interp_vdep(V, fld_of(V, A.ngrid), C, W, ks);
-        prob[ks] = (R)1 - m_expp(-vdepo * tdep / ((R)2. * (R)15.));   // href = 15, par_mod.f90:76
-      }
-    }
-  }
-  // what the epilogue reads of the particle travels with the last gather
-  EpiPre<R> pre;
-  int itramem = 0;
-  unsigned int sl = s;
-  auto late_epi = [&]() {
-    asm volatile("" : "+v"(sl));
-    pre.template load<DRYDEP>(V, Gp, P, sl);
-    itramem = P.itramem[sl];
-  };
-  const int nstop = adv_finish<R, Rng<R>, POLAR, MOTHER, decltype(late_epi), CAPCHECK>(V, hgt, G, itime, ps, A, usig, vsig, wsig, late_epi);
-  epilogue_store<R, DRYDEP>(V, Gp, P, s, itime, itramem, nstop, ps, prob, st, &pre, dry);
-}
-
-// completion of the PBL particles (finish_body).  One thread per list entry or slot.
-template <typename R, bool DRYDEP, bool POLAR, bool NEST>
-__global__ void __launch_bounds__(kBlock, FPX_FINISH_WAVES) k_pbl_finish(View<R> V_arg, GridP<R> Gp_arg, Parts<R> P_arg, PblRec<R> Q_arg, int itime, unsigned int step, Stats *st,
-                                                       const unsigned char *__restrict__ pbl_key, long long numpart,
-                                                       const unsigned int *__restrict__ pbl_list, const unsigned int *__restrict__ pbl_count) {
-#ifndef FPX_VIEW_BY_VALUE
-  struct KArgs { View<R> V; GridP<R> Gp; Parts<R> P; PblRec<R> Q; };
-  const KArgs &ka = *(const KArgs *)(const void *)__builtin_amdgcn_kernarg_segment_ptr();
-  const View<R> &V = ka.V; const GridP<R> &Gp = ka.Gp; Parts<R> &P = const_cast<Parts<R> &>(ka.P); const PblRec<R> &Q = ka.Q;
-  (void)V_arg; (void)Gp_arg; (void)P_arg; (void)Q_arg;
-#else
-  const View<R> &V = V_arg; const GridP<R> &Gp = Gp_arg; Parts<R> &P = P_arg; const PblRec<R> &Q = Q_arg;
-#endif
-  // Two orders.  pbl_list given: the work list (class by class, each class in slot = cell order): every lane busy.  With cost
-  // buckets in the list (32 interleaved sub-sequences of the cell-sorted slots) following it costs this kernel half of its
-  // time again in scattered record and state accesses (0.58 -> 0.87 ms at 1.25e7 particles); then pbl_list is null and the
-  // kernel goes through the SLOTS, taking those whose key of this step says "boundary layer" (0.77 ms when every slot has a
-  // lane and the others idle; with the per-wave queue below the waves are full).
-  __shared__ R hgt[kMaxNz];
-  for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
-  __syncthreads();
-  // Slot order: every wave walks tiles of 64 consecutive slots, collects the boundary-layer ones in a queue of its own in LDS
-  // and works them off 64 at a time -- full waves in (nearly) slot order, whatever share of a tile is boundary layer.
-  __shared__ unsigned int queue_mem[kBlock / 64][128];
-  // (an LDS pointer by type: as a generic one it made the compiler emit an instruction its own verifier rejects in the polar instance)
-  typedef volatile unsigned int __attribute__((address_space(3))) *lds_queue_ptr;
-  const lds_queue_ptr queue = (lds_queue_ptr)&queue_mem[threadIdx.x >> 6][0];
-  const int lane = threadIdx.x & 63;
-  unsigned int qlen = 0;   // wave-uniform
-  const long long nwork = pbl_list ? (long long)*pbl_count : (numpart + 63) >> 6;   // list entries | tiles of 64 slots
-  const long long stride = pbl_list ? (long long)gridDim.x * blockDim.x : (long long)gridDim.x * (kBlock / 64);
-  long long it = pbl_list ? (long long)blockIdx.x * blockDim.x : (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-  for (;;) {   // ONE body for both orders (the body is large: a single call site keeps it inlined once)
-    // one wave's worth of particles: slot s for the lanes with `mine` (every lane of the wave goes through the body: the
-    // dry-deposition scatter at its end needs them all)
-    unsigned int s = 0;
-    bool mine = false;
-    if (pbl_list) {
-      if (it >= nwork) break;          // the same for every lane of the block
-      const long long i = it + threadIdx.x;
-      mine = i < nwork;
-      if (mine) s = pbl_list[i];
-      it += stride;
-    } else {
-      while (qlen < 64u && it < nwork) {
-        const long long i = it * 64 + lane;
-        const bool pbl = i < numpart && pbl_key[i] < kKeyDone;
-        const unsigned long long m = __ballot(pbl);
-        if (pbl) queue[qlen + (unsigned int)__popcll(m & ((1ull << lane) - 1ull))] = (unsigned int)i;
-        qlen += (unsigned int)__popcll(m);
-        it += stride;
-      }
-      if (qlen == 0u) break;           // the same for every lane of the wave
-      const unsigned int take = min(qlen, 64u), rest = qlen - take;
-      mine = (unsigned int)lane < take;
-      if (mine) s = queue[lane];
-      const unsigned int carry = (unsigned int)lane < rest ? queue[64 + lane] : 0u;
-      if ((unsigned int)lane < rest) queue[lane] = carry;
-      qlen = rest;
-    }
-    DryDep<R> dry;
-#pragma unroll
-    for (int ks = 0; ks < kMaxSpec; ks++) dry.dep[ks] = 0.f;
-    dry.x = (R)0; dry.y = (R)0; dry.nage = 1; dry.kp = 1; dry.nclass = 1;
-    if (mine) {
-      const PblRecord<R> rec = Q.rec[s];
-      const R tdep = DRYDEP ? Q.tdep[s] : (R)0;
-      if (POLAR && !NEST && !__any(pbl_ngrid(rec.i[2]) < 0)) {   // wave-uniform: no particle of this wave sits in a polar cap
-        finish_body<R, DRYDEP, false, false, true>(V, Gp, P, s, rec, tdep, itime, step, st, hgt, DRYDEP ? &dry : nullptr);
-      } else {
-        finish_body<R, DRYDEP, POLAR, NEST, false>(V, Gp, P, s, rec, tdep, itime, step, st, hgt, DRYDEP ? &dry : nullptr);
-      }
-    }
-    if (DRYDEP && Gp.on && V.ldirect == 1) {
-      // drydepokernel / drydepokernel_nest (timemanager.f90:690-696), with every lane of the wave: lanes of the same output
-      // cell are summed into its neighbourhood before the atomics (wave_kernel_add); a lane without a deposit adds nothing
-#pragma unroll
-      for (int ks = 0; ks < kMaxSpec; ks++) {
-        if (ks < V.nspec && V.drydepspec[ks]) {
-          drydepo_particle<R, true>(V, Gp, dry.nclass, dry.dep[ks], ks, dry.x, dry.y, dry.nage, dry.kp);
-          if (Gp.nested) drydepo_particle<R, true>(V, Gp, dry.nclass, dry.dep[ks], ks, dry.x, dry.y, dry.nage, dry.kp, true);
-        }
-      }
-    }
-  }
-}
-
-// conccalc.f90:50-295: every slot, whole waves stay convergent for the wave-level pre-reduction
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_conccalc(View<R> V_arg, GridP<R> Gp_arg, Parts<R> P_arg, long long numpart, int itime, R weight) {
-#ifndef FPX_VIEW_BY_VALUE
-  struct KArgs { View<R> V; GridP<R> Gp; Parts<R> P; };
-  const KArgs &ka = *(const KArgs *)(const void *)__builtin_amdgcn_kernarg_segment_ptr();
-  const View<R> &V = ka.V; const GridP<R> &Gp = ka.Gp; const Parts<R> &P = ka.P;
-  (void)V_arg; (void)Gp_arg; (void)P_arg;
-#else
-  const View<R> &V = V_arg; const GridP<R> &Gp = Gp_arg; const Parts<R> &P = P_arg;
-#endif
-  __shared__ R hgt[kMaxNz];
-  __shared__ R outh[kMaxNz];
-  for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
-  for (int k = threadIdx.x; k < Gp.numzgrid; k += blockDim.x) outh[k] = Gp.outheight[k];
-  __syncthreads();
-  const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  bool active = s < numpart;
-  double xt = 0, yt = 0;
-  R zt = 0, xm[kMaxSpec];
-  int itage = 0, npoint = 1, nclass = 1;
-#pragma unroll
-  for (int ks = 0; ks < kMaxSpec; ks++) xm[ks] = (R)0;
-  if (active) {
-    // the particle's state in ONE memory round trip (nearly every particle is due; the asm keeps the compiler from sinking
-    // each load behind the branch that first needs it)
-    int itra1 = P.itra1[s], itramem = P.itramem[s];
-    xt = P.xt[s]; yt = P.yt[s]; zt = P.zt[s];
-    npoint = P.npoint[s]; nclass = P.nclass[s];
-#pragma unroll
-    for (int ks = 0; ks < kMaxSpec; ks++)
-      if (ks < V.nspec) xm[ks] = P.xmass1[(size_t)ks * P.cap + s];
-    static_assert(kMaxSpec == 5, "the tie below names five species");
-    asm volatile("" : "+v"(itra1), "+v"(itramem), "+v"(xt), "+v"(yt), "+v"(zt), "+v"(npoint), "+v"(nclass),
-                      "+v"(xm[0]), "+v"(xm[1]), "+v"(xm[2]), "+v"(xm[3]), "+v"(xm[4]));
-    itage = abs(itime - itramem);
-    active = itra1 == itime;
-    if (!(xt >= 0. && xt <= (double)V.nxmin1 && yt >= 0. && yt <= (double)V.nymin1) || !(zt == zt)) active = false;
-  }
-  if (P.xscav) {   // wave-uniform: DRYBKDEP / WETBKDEP
-    R sc[kMaxSpec];
-#pragma unroll
-    for (int ks = 0; ks < kMaxSpec; ks++) sc[ks] = (active && ks < V.nspec) ? m_max(P.xscav[(size_t)ks * P.cap + s], (R)0) : (R)0;
-    conccalc_particle(V, Gp, hgt, active, xt, yt, zt, itage, npoint, nclass, xm, weight, sc, outh);
-  } else {
-    conccalc_particle(V, Gp, hgt, active, xt, yt, zt, itage, npoint, nclass, xm, weight, (const R *)nullptr, outh);
-  }
-}
-
-// The receptor block of timemanager.f90:564-598 (backward runs with DRYBKDEP / WETBKDEP): once per particle, before it is
-// moved for the first time -- xscav_frac1 < 0 marks a particle that has not been through it (releaseparticles.f90:167-171).
-// get_vdep_prob.f90 sets the cell (the nest's inside a nest) but not the weights p1..p4, dt1, dt2, dtt that
-// interpol_vdep[_nests] reads: those are the ones initialize() of the same particle left in interpol_mod, i.e. the
-// mother grid's weights at the particle's position and the step's time weights -- computed here from the position.
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_bkdep(View<R> V_arg, WetP<R> Wp, Parts<R> P, long long numpart, int itime, int drybkdep, int wetbkdep,
-                                                  const R *__restrict__ zspan /* [numpoint] zpoint2 - zpoint1 */) {
-  FPX_VIEW_FROM_KERNARG(V, V_arg);
-  __shared__ R hgt[kMaxNz];
-  for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
-  __syncthreads();
-  const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= numpart) return;
-  if (P.itra1[s] != itime) return;
-  bool todo = false;
-  for (int ks = 0; ks < V.nspec; ks++) todo = todo || P.xscav[(size_t)ks * P.cap + s] < (R)0;
-  if (!todo) return;
-  const double xt = P.xt[s], yt = P.yt[s];
-  const R zt = P.zt[s];
-  if (!(xt >= 0. && xt <= (double)V.nxmin1 && yt >= 0. && yt <= (double)V.nymin1) || !(zt == zt)) return;   // k_prep terminates it
-  if (drybkdep) {
-    const R href = (R)15.;
-    // get_vdep_prob.f90:52-99
-    const int ngrid = pick_grid<R, false>(V, xt, yt);
-    int ix, jy;
-    if (ngrid > 0) {
-      const NestDesc<R> &N = V.nest[ngrid - 1];
-      ix = (int)(R)((xt - (double)N.xl) * (double)N.xres);
-      jy = (int)(R)((yt - (double)N.yl) * (double)N.yres);
-    } else {
-      ix = (int)xt; jy = (int)yt;
-    }
-    Cell<R> C;
-    cell_setup(C, ix, jy, ix + 1, jy + 1, (R)xt, (R)yt);
-    {   // the weights of initialize(): ddx = real(xt) - real(int(xt)) on the mother grid
-      const int ixm = (int)xt, jym = (int)yt;
-      const R ddx = (R)xt - (R)ixm, ddy = (R)yt - (R)jym, rddx = (R)1 - ddx, rddy = (R)1 - ddy;
-      C.p1 = rddx * rddy; C.p2 = ddx * rddy; C.p3 = rddx * ddy; C.p4 = ddx * ddy;
-    }
-    const Fld<R> F = fld_of(V, ngrid);
-    const TimeW<R> W = time_weights(V, itime);
-    for (int ks = 0; ks < V.nspec; ks++) {
-      if (!(P.xscav[(size_t)ks * P.cap + s] < (R)0)) continue;
-      if (V.drydepspec[ks]) {
-        R prob = (R)0;
-        if (V.drydep && zt < (R)2. * href) prob = interp_vdep(V, F, C, W, ks);   // :105-127: the deposition velocity itself
-        P.xscav[(size_t)ks * P.cap + s] = prob;
-      } else {
-        P.xmass1[(size_t)ks * P.cap + s] = (R)0;
-        P.xscav[(size_t)ks * P.cap + s] = (R)0;
-      }
-    }
-  }
-  if (wetbkdep) {
-    const int np = release_index(V, P.npoint[s]);
-    for (int ks = 0; ks < V.nspec; ks++) {
-      if (!(P.xscav[(size_t)ks * P.cap + s] < (R)0)) continue;
-      R grfr = (R)0;
-      const R wetscav = get_wetscav(V, Wp, hgt, itime, V.lsynctime, xt, yt, zt, ks, grfr);
-      if (wetscav > (R)0) {
-        P.xscav[(size_t)ks * P.cap + s] = wetscav * zspan[np] * grfr;
-      } else {
-        P.xmass1[(size_t)ks * P.cap + s] = (R)0;
-        P.xscav[(size_t)ks * P.cap + s] = (R)0;
-      }
-    }
-  }
-}
-
-// wetdepo.f90:58-151: every live particle that is due or overdue
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_wetdepo(View<R> V_arg, GridP<R> Gp_arg, WetP<R> Wp_arg, Parts<R> P_arg, long long numpart, int itime,
-                                                    int ltsample, int loutnext) {
-#ifndef FPX_VIEW_BY_VALUE
-  struct KArgs { View<R> V; GridP<R> Gp; WetP<R> Wp; Parts<R> P; };
-  const KArgs &ka = *(const KArgs *)(const void *)__builtin_amdgcn_kernarg_segment_ptr();
-  const View<R> &V = ka.V; const GridP<R> &Gp = ka.Gp; const WetP<R> &Wp = ka.Wp; const Parts<R> &P = ka.P;
-  (void)V_arg; (void)Gp_arg; (void)Wp_arg; (void)P_arg;
-#else
-  const View<R> &V = V_arg; const GridP<R> &Gp = Gp_arg; const WetP<R> &Wp = Wp_arg; const Parts<R> &P = P_arg;
-#endif
-  __shared__ R hgt[kMaxNz];
-  for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
-  __syncthreads();
-  // every lane stays to the end (the wave-level sums of wetdepo_scatter need convergent waves): `live` says whether the lane
-  // holds a particle that is scavenged at all
-  const long long s0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  bool live = s0 < numpart;
-  const long long s = live ? s0 : 0;
-  // the particle's state in ONE memory round trip (as in k_conccalc)
-  int itra1 = P.itra1[s], itramem = P.itramem[s], nunc = P.nclass[s];
-  int kp = Gp.ioutputforeachrelease == 1 ? P.npoint[s] : 1;
-  double xt = P.xt[s], yt = P.yt[s];
-  R zt = P.zt[s];
-  R xm_all[kMaxSpec];
-#pragma unroll
-  for (int ks = 0; ks < kMaxSpec; ks++) xm_all[ks] = (ks < V.nspec && Wp.wetdepspec[ks]) ? P.xmass1[(size_t)ks * P.cap + s] : (R)0;
-  static_assert(kMaxSpec == 5, "the tie below names five species");
-  asm volatile("" : "+v"(itra1), "+v"(itramem), "+v"(nunc), "+v"(kp), "+v"(xt), "+v"(yt), "+v"(zt),
-                    "+v"(xm_all[0]), "+v"(xm_all[1]), "+v"(xm_all[2]), "+v"(xm_all[3]), "+v"(xm_all[4]));
-  if (itra1 == kDead) live = false;
-  if (V.ldirect == 1) { if (itra1 > itime) live = false; } else { if (itra1 < itime) live = false; }
-  if (!(xt >= 0. && xt <= (double)V.nxmin1 && yt >= 0. && yt <= (double)V.nymin1) || !(zt == zt)) live = false;
-  if (!live) { xt = 0.; yt = 0.; zt = (R)0; }      // a harmless position for the lanes that only take part in the sums
-  const int ldeltat = itime <= loutnext ? itime - (loutnext - Gp.loutstep) : itime - loutnext;   // wetdepo.f90:58-62
-  const int nage = ageclass(Gp, abs(itra1 - itramem));
-  const R smallnum = sizeof(R) == 4 ? (R)1.17549435e-38f : (R)2.2250738585072014e-308;
-  for (int ks = 0; ks < V.nspec; ks++) {
-    if (!Wp.wetdepspec[ks]) continue;
-    R grfr = (R)0;
-    R wetdeposit = (R)0;
-    if (live) {
-      const R wetscav = get_wetscav(V, Wp, hgt, itime, ltsample, xt, yt, zt, ks, grfr);
-      const R xm = pick(xm_all, ks);
-      if (wetscav > (R)0) wetdeposit = xm * ((R)1 - m_exp(-wetscav * (R)abs(ltsample))) * grfr;
-      const R restmass = xm - wetdeposit;
-      P.xmass1[(size_t)ks * P.cap + s] = restmass > smallnum ? restmass : (R)0;
-      if (V.decay[ks] > (R)0) wetdeposit = wetdeposit * m_exp((R)abs(ldeltat) * V.decay[ks]);
-    }
-    if (V.ldirect == 1 && Gp.on) wetdepo_scatter(V, Gp, nunc, wetdeposit, ks, (R)xt, (R)yt, nage, kp);
-    if (V.ldirect == 1 && Gp.on && Gp.nested) wetdepo_scatter(V, Gp, nunc, wetdeposit, ks, (R)xt, (R)yt, nage, kp, true);   // wetdepo.f90:142
-  }
-}
-
-template <typename T>
-__global__ void k_convert(const T *__restrict__ src, double *__restrict__ dst64, float *__restrict__ dst32, long long n) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (dst64) dst64[i] = (double)src[i];
-  if (dst32) dst32[i] = (float)src[i];
-}
-
 // ---------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------
-// ---------------------------------------------------------------------------
-FPX_TU_CLOSE   // one type for all translation units
+// one type for all translation units
 struct EngineBase {
   virtual ~EngineBase() {}
   virtual int set_height(const void *h, int n) = 0;
@@ -2121,7 +160,7 @@ struct EngineBase {
   virtual int checkpoint_read(const char *path, int32_t *itime, int64_t *numpart_out, int32_t *numparticlecount) = 0;
 };
 EngineBase *make_engine_f32(const fpx_config *cfg, int *rc);   // defined by the unit that holds Engine<float>
-// The three kernels of the step are compiled in units of their own (fpx_tu.hpp: FPX_TU_PART 1 and 2) and reach the
+// The three kernels of the step are compiled in units of their own (fpx_step_prep.hip, fpx_step_loop.hip) and reach the
 // engine as untyped host-stub addresses; the engine casts them to the kernel's signature (same headers, same layout).
 // real_bytes 8|4 picks the arithmetic type.
 const void *step_kernel_prep(int real_bytes, bool drydep, bool init, bool polar, bool nest);
@@ -6578,64 +4617,6 @@ struct Engine : EngineBase {
 };
 
 FPX_TU_CLOSE
-#if FPX_TU_PART == 1 || FPX_TU_PART < 0
-template <typename R>
-static const void *prep_table(bool drydep, bool init, bool polar, bool nest) {
-#define FPX_PREP(DD, II) (polar ? (nest ? (const void *)k_prep<R, DD, II, true, true> : (const void *)k_prep<R, DD, II, true, false>) \
-                                : (nest ? (const void *)k_prep<R, DD, II, false, true> : (const void *)k_prep<R, DD, II, false, false>))
-  if (drydep) return init ? FPX_PREP(true, true) : FPX_PREP(true, false);
-  return init ? FPX_PREP(false, true) : FPX_PREP(false, false);
-#undef FPX_PREP
-}
-#if FPX_TU_REAL != 4
-const void *step_kernel_prep_f64(bool drydep, bool init, bool polar, bool nest) { return prep_table<double>(drydep, init, polar, nest); }
-#endif
-#if FPX_TU_REAL != 8
-const void *step_kernel_prep_f32(bool drydep, bool init, bool polar, bool nest) { return prep_table<float>(drydep, init, polar, nest); }
-#endif
-#endif
-#if FPX_TU_PART == 2 || FPX_TU_PART < 0
-// the Langevin kernel specialised for the run's switches (gases: LEAN) or the general one
-template <typename R, bool SUSP>
-static const void *loop_table_s(bool lean, int turbswitch, int cblflag, int rng_mode, bool *is_lean) {
-  const bool philox = rng_mode == FPX_RNG_PHILOX;
-  *is_lean = false;
-  if (turbswitch < 0) return (const void *)k_pbl_loop<R, false, -1, -1, -1, SUSP>;   // turboff: the general instance (it alone has the switch)
-  if (lean) {
-    *is_lean = true;
-    if (turbswitch && cblflag == 1) return philox ? (const void *)k_pbl_loop<R, true, 1, 1, 2, SUSP> : (const void *)k_pbl_loop<R, true, 1, 1, 0, SUSP>;
-    if (turbswitch && cblflag != 1) return philox ? (const void *)k_pbl_loop<R, true, 1, 0, 2, SUSP> : (const void *)k_pbl_loop<R, true, 1, 0, 0, SUSP>;
-    if (!turbswitch && cblflag != 1) return philox ? (const void *)k_pbl_loop<R, true, 0, 0, 2, SUSP> : (const void *)k_pbl_loop<R, true, 0, 0, 0, SUSP>;
-    *is_lean = false;
-  } else if (philox) {   // aerosols (settling / dry deposition) with the counter RNG: same switch specialisation
-    if (turbswitch && cblflag == 1) return (const void *)k_pbl_loop<R, false, 1, 1, 2, SUSP>;
-    if (turbswitch && cblflag != 1) return (const void *)k_pbl_loop<R, false, 1, 0, 2, SUSP>;
-  }
-  return (const void *)k_pbl_loop<R, false, -1, -1, -1, SUSP>;
-}
-// (a step of several launches runs the SUSP twin of the SAME specialisation: the arithmetic of a particle must not depend on
-// how its step is scheduled -- two instances with different compile-time switches round differently)
-template <typename R>
-static const void *loop_table(bool lean, int turbswitch, int cblflag, int rng_mode, bool susp, bool *is_lean) {
-  return susp ? loop_table_s<R, true>(lean, turbswitch, cblflag, rng_mode, is_lean) : loop_table_s<R, false>(lean, turbswitch, cblflag, rng_mode, is_lean);
-}
-template <typename R>
-static const void *finish_table(bool drydep, bool polar, bool nest) {
-  if (drydep) return polar ? (nest ? (const void *)k_pbl_finish<R, true, true, true> : (const void *)k_pbl_finish<R, true, true, false>)
-                           : (nest ? (const void *)k_pbl_finish<R, true, false, true> : (const void *)k_pbl_finish<R, true, false, false>);
-  return polar ? (nest ? (const void *)k_pbl_finish<R, false, true, true> : (const void *)k_pbl_finish<R, false, true, false>)
-               : (nest ? (const void *)k_pbl_finish<R, false, false, true> : (const void *)k_pbl_finish<R, false, false, false>);
-}
-#if FPX_TU_REAL != 4
-const void *step_kernel_loop_f64(bool lean, int turbswitch, int cblflag, int rng_mode, bool susp, bool *is_lean) { return loop_table<double>(lean, turbswitch, cblflag, rng_mode, susp, is_lean); }
-const void *step_kernel_finish_f64(bool drydep, bool polar, bool nest) { return finish_table<double>(drydep, polar, nest); }
-#endif
-#if FPX_TU_REAL != 8
-const void *step_kernel_loop_f32(bool lean, int turbswitch, int cblflag, int rng_mode, bool susp, bool *is_lean) { return loop_table<float>(lean, turbswitch, cblflag, rng_mode, susp, is_lean); }
-const void *step_kernel_finish_f32(bool drydep, bool polar, bool nest) { return finish_table<float>(drydep, polar, nest); }
-#endif
-#endif
-#if FPX_TU_PART <= 0
 #if FPX_TU_REAL != 8
 EngineBase *make_engine_f32(const fpx_config *cfg, int *rc) {
   auto *p = new (std::nothrow) Engine<float>();
@@ -6661,10 +4642,9 @@ const void *step_kernel_finish(int rb, bool drydep, bool polar, bool nest) {
   return rb == 8 ? step_kernel_finish_f64(drydep, polar, nest) : step_kernel_finish_f32(drydep, polar, nest);
 }
 #endif
-#endif   // FPX_TU_PART <= 0
 }  // namespace fpx
 
-#if FPX_TU_REAL != 4 && FPX_TU_PART <= 0
+#if FPX_TU_REAL != 4
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -7001,4 +4981,4 @@ int fpx_find_level_probe(int32_t real_bytes, const void *height, int32_t nz, con
 }
 
 }  // extern "C"
-#endif   // FPX_TU_REAL != 4 && FPX_TU_PART <= 0
+#endif   // FPX_TU_REAL != 4

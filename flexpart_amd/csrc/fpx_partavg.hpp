@@ -3,7 +3,7 @@
 //
 // po_gather is the interpolation to the particle's position that partoutput.f90:63-175 and partpos_average.f90:31-152 share
 // word for word -- topography, PV, humidity, temperature, density, tropopause, mixing height, and for the averages the two
-// wind components -- in the host's real kind H, in the reference's order, FMA contraction off; k_partoutput (fpx_engine.hip)
+// wind components -- in the host's real kind H, in the reference's order, FMA contraction off; k_partoutput (fpx_particles.hpp)
 // and k_partavg both call it.  Where the reference mixes kinds (xlon, ddx, ddy: a double position with default reals) the
 // expression is formed in double and rounded to H.  uu and vv come from the unblended wind pack of the two time slots
 // whether or not the step's blended pack exists: the blended pack rounds in another order.
