@@ -72,9 +72,12 @@ struct EngineBase {
   virtual int verttransform(int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) = 0;
   virtual int verttransform_nest(int nest, int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) = 0;
   virtual int calcpar(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) = 0;
+  virtual int calcpar_nest(int nest, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) = 0;
   virtual double cp_ms() = 0;
   virtual int getvdep_init(const fpx_getvdep_tables *t) = 0;
   virtual int getvdep(int slot, const fpx_getvdep_in *g, void *vdep_out) = 0;
+  virtual int getvdep_nest_init(int nest, const void *xlandusen) = 0;
+  virtual int getvdep_nest(int nest, int slot, const fpx_getvdep_in *g, void *vdep_out) = 0;
   virtual double gv_ms() = 0;
   virtual int calcpv_init(const fpx_calcpv_cfg *c) = 0;
   virtual int get_pvh(int nest, void *pvh_out) = 0;
@@ -837,11 +840,14 @@ struct Engine : EngineBase {
     }
     pvh_on_device[nest] = true;
     // without sfc the slot's 2-D fields are still those of the previous wind field until fpx_calcpar has run: not loaded
-    if (nest) nest_loaded[nest - 1][s] = true; else { slot_loaded[s] = sfc != nullptr; vdep_pending[s] = false; }
-    if (!nest) vt_slot_on_device = slot;      // whose model-level arrays the buffers hold (fpx_calcpar)
+    if (nest) { nest_loaded[nest - 1][s] = sfc != nullptr; nest_vdep_pending[nest - 1][s] = false; }   // sfc = NULL: until fpx_calcpar_nest
+    else { slot_loaded[s] = sfc != nullptr; vdep_pending[s] = false; }
+    vt_slot_on_device[nest] = slot;           // whose model-level arrays the grid's buffers hold (fpx_calcpar, fpx_calcpar_nest)
+    if (nest) { nest_dyn[nest - 1] = m->nest_dy; nest_ylat0n[nest - 1] = m->nest_ylat0; }   // calcpar_nests.f90:73
     return 0;
   }
-  int vt_slot_on_device = 0;
+  int vt_slot_on_device[1 + kMaxNests] = {};
+  double nest_dyn[kMaxNests] = {}, nest_ylat0n[kMaxNests] = {};
 
   // ---- calcpv / calcpv_nests on the device (fpx_calcpv.hpp; launched by verttransform_t when pvh = NULL) ----------
   double pv_dxn[kMaxNests] = {};       // com_mod's dxn(l): calcpv_nests.f90:168,171 divides by it (dx/xresoln need not round to it)
@@ -867,60 +873,77 @@ struct Engine : EngineBase {
   double pv_ms() override { return pv_last_ms; }
 
   // ---- calcpar on the device ----------------------------------------------------------
+  // g = 0: the mother grid (calcpar.f90); g = l >= 1: nested grid l (one iteration l of calcpar_nests.f90:63-225): the same
+  // kernel on the nest's arrays, extents and latitudes, with buffers and gather packs of the nest's own
   template <typename H>
-  int calcpar_t(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) {
+  int calcpar_t(int g, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) {
     enum { UUH, VVH, PVH, WWH, TTH, QVH, PS, TT2, TD2, AKZ, BKZ, AKN, BKN, HGT,
            UU, VV, WW, TT, QV, PV, RHO, DRHO, UPOL, VPOL, UVZ, WZ, RHOH, PINM, KUV, KW, NBUF };
-    void **vt_dev = vt_sets[0];
+    void **vt_dev = vt_sets[g];
     auto D = [&](int i) { return (H *)vt_dev[i]; };
+    const HostGrid HG = host_grid(g);
+    const WindDst T = wind_dst(g);
     const int nz = cfg.nz, s = slot - 1;
-    const size_t n2 = (size_t)cfg.nxmax * cfg.nymax;
+    const size_t n2 = (size_t)HG.nxmax * HG.nymax;
     int rc;
-    if (!cp_buf) {
+    if (!cp_buf[g]) {
       H *q = nullptr;
       if ((rc = dalloc(&q, 8 * n2 + 2 * (size_t)nz))) return rc;       // surfstr, sshf, excessoro, ustar, wstar, oli, hmix, tropopause | akm, bkm
       HIPCHK(hipMemsetAsync(q, 0, (8 * n2 + 2 * (size_t)nz) * sizeof(H), stream));
-      cp_buf = q;
+      cp_buf[g] = q;
     }
-    H *B = (H *)cp_buf;
+    H *B = (H *)cp_buf[g];
     H *d_str = B, *d_shf = B + n2, *d_exc = B + 2 * n2, *d_ust = B + 3 * n2, *d_wst = B + 4 * n2, *d_oli = B + 5 * n2, *d_hmix = B + 6 * n2, *d_akm = B + 8 * n2, *d_bkm = d_akm + nz;
-    H *d_trop = (H *)diag_tropo[s];            // the slot's tropopause in the host's layout (kept for partoutput); stale values persist as in the reference
-    if ((rc = diag_alloc())) return rc;
-    d_trop = (H *)diag_tropo[s];
+    // the slot's tropopause in the host's layout (the mother grid's is kept for partoutput): it starts at zero and stale values
+    // persist as in the reference -- the kernel writes a column only where the criterion fires (calcpar_nests.f90:201-214)
+    H *d_trop;
+    if (g == 0) {
+      if ((rc = diag_alloc())) return rc;
+      d_trop = (H *)diag_tropo[s];
+    } else {
+      if (!nest_tropo[g - 1][s]) {
+        H *q = nullptr;
+        if ((rc = dalloc(&q, n2))) return rc;
+        HIPCHK(hipMemsetAsync(q, 0, n2 * sizeof(H), stream));
+        nest_tropo[g - 1][s] = q;
+      }
+      d_trop = (H *)nest_tropo[g - 1][s];
+    }
     HIPCHK(hipMemcpyAsync(d_str, c->surfstr, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_shf, c->sshf, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
     if (c->lsubgrid == 1) HIPCHK(hipMemcpyAsync(d_exc, c->excessoro, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_akm, c->akm, (size_t)nz * sizeof(H), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_bkm, c->bkm, (size_t)nz * sizeof(H), hipMemcpyHostToDevice, stream));
     cp::Args<H> A;
-    A.G.nx = cfg.nx; A.G.ny = cfg.ny; A.G.nz = nz; A.G.nuvz = nz; A.G.nwz = nz; A.G.nxmax = cfg.nxmax; A.G.nymax = cfg.nymax;
+    A.G.nx = HG.nx; A.G.ny = HG.ny; A.G.nz = nz; A.G.nuvz = nz; A.G.nwz = nz; A.G.nxmax = HG.nxmax; A.G.nymax = HG.nymax;
     A.G.dx = (H)cfg.dx; A.G.dy = (H)cfg.dy; A.G.xlon0 = (H)cfg.xlon0; A.G.ylat0 = (H)cfg.ylat0;
+    if (g) { A.G.dy = (H)nest_dyn[g - 1]; A.G.ylat0 = (H)nest_ylat0n[g - 1]; }   // altmin: ylat0n(l) + jy*dyn(l), calcpar_nests.f90:73
     A.I = vt::In<H>{D(UUH), D(VVH), D(PVH), D(WWH), D(TTH), D(QVH), D(PS), D(TT2), D(TD2), D(AKZ), D(BKZ), D(AKN), D(BKN), D(HGT)};
     A.surfstr = d_str; A.sshf = d_shf; A.excessoro = d_exc; A.akm = d_akm; A.bkm = d_bkm; A.lsubgrid = c->lsubgrid;
-    A.zlev = D(RHOH);                          // scratch of the transform, free between calls
+    A.zlev = D(RHOH);                          // scratch of the grid's transform, free between calls
     A.ustar = d_ust; A.wstar = d_wst; A.oli = d_oli; A.hmix = d_hmix; A.tropopause = d_trop;
     Events<2> ev;
     HIPCHK(ev.create());
     HIPCHK(hipEventRecord(ev[0], stream));
-    cp::k_calcpar<H><<<(cfg.nx * cfg.ny + 255) / 256, 256, 0, stream>>>(A);
+    cp::k_calcpar<H><<<(HG.nx * HG.ny + 255) / 256, 256, 0, stream>>>(A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev[1], stream));
-    // into the gather packs, as upload_fields does from the host's arrays
+    // into the gather packs, as upload_fields / upload_nest_fields do from the host's arrays
     auto pk2 = [&](const H *in, const R *outp, int stride, int off) -> int {
-      const int tot = cfg.nx * cfg.ny;
-      k_pack2<H, R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, (R *)outp, cfg.nx, cfg.ny, cfg.nxmax, stride, off);
+      const int tot = HG.nx * HG.ny;
+      k_pack2<H, R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>(in, (R *)outp, HG.nx, HG.ny, HG.nxmax, stride, off);
       HIPCHK(hipGetLastError());
       return 0;
     };
-    if ((rc = pk2(d_ust, V.sfc, 8, s * 4 + 0)) || (rc = pk2(d_wst, V.sfc, 8, s * 4 + 1)) || (rc = pk2(d_oli, V.sfc, 8, s * 4 + 2)) || (rc = pk2(d_hmix, V.sfc, 8, s * 4 + 3))) return rc;
-    if (slot == 1 && (rc = pk2(d_trop, V.tropo, 1, 0))) return rc;        // literal time index 1, advance.f90:253
-    diag_have[DG_TROPO + s] = true;
-    if (V.vdep && c->vdep) {
+    if ((rc = pk2(d_ust, T.sfc, 8, s * 4 + 0)) || (rc = pk2(d_wst, T.sfc, 8, s * 4 + 1)) || (rc = pk2(d_oli, T.sfc, 8, s * 4 + 2)) || (rc = pk2(d_hmix, T.sfc, 8, s * 4 + 3))) return rc;
+    if (slot == 1 && (rc = pk2(d_trop, T.tropo, 1, 0))) return rc;        // literal time index 1, advance.f90:253 (tropopausen: :263)
+    if (g == 0) diag_have[DG_TROPO + s] = true;
+    if (T.vdep && c->vdep) {
       const size_t plane = n2 * cfg.host_real_bytes;
       for (int ks = 0; ks < cfg.nspec; ks++)
-        if ((rc = p2(host_grid(0), (const char *)c->vdep + plane * ks, V.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
+        if ((rc = p2(HG, (const char *)c->vdep + plane * ks, T.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
     }
-    k_hcell<R><<<(cfg.nx * cfg.ny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(V.sfc, (R *)V.hcell, cfg.nx, cfg.ny);
+    k_hcell<R><<<(HG.nx * HG.ny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(T.sfc, (R *)T.hcell, HG.nx, HG.ny);
     HIPCHK(hipGetLastError());
     if (out) {
       void *dst[5] = {out->ustar, out->wstar, out->oli, out->hmix, out->tropopause};
@@ -932,30 +955,45 @@ struct Engine : EngineBase {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
     cp_last_ms = ms;
-    cp_slot_on_device = slot;                  // whose ustar, oli the buffer holds (fpx_getvdep)
+    cp_slot_on_device[g] = slot;               // whose ustar, oli the grid's buffer holds (fpx_getvdep, fpx_getvdep_nest)
     // device_vdep with DRYDEP: the slot's vdep is still the previous wind field's until fpx_getvdep has run: not loaded
-    vdep_pending[s] = V.vdep && !c->vdep;
-    slot_loaded[s] = !vdep_pending[s];
+    const bool pending = T.vdep && !c->vdep;
+    if (g == 0) { vdep_pending[s] = pending; slot_loaded[s] = !pending; }
+    else { nest_vdep_pending[g - 1][s] = pending; nest_loaded[g - 1][s] = !pending; }
     return 0;
   }
-  void *cp_buf = nullptr;
+  void *cp_buf[1 + kMaxNests] = {};          // one per grid, sized by it: calls for the mother grid and the nests may interleave
+  void *nest_tropo[kMaxNests][2] = {};       // tropopausen(:,:,1,n,l) in the host's layout and real kind, allocated on first use
   double cp_last_ms = 0;
-  int cp_slot_on_device = 0;
+  int cp_slot_on_device[1 + kMaxNests] = {};
   bool vdep_pending[2] = {false, false};
+  bool nest_vdep_pending[kMaxNests][2] = {};
   int calcpar(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) override {
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "calcpar: slot must be 1 or 2");
     if (!c || !c->surfstr || !c->sshf || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "calcpar: surfstr, sshf, akm, bkm are required");
     if (c->lsubgrid == 1 && !c->excessoro) return fail(FPX_ERR_ARG, "calcpar: excessoro required with lsubgrid = 1");
     if (cfg.drydep && !c->vdep && !c->device_vdep) return fail(FPX_ERR_ARG, "calcpar: vdep (the host's getvdep) required with DRYDEP");
-    if (!vt_set_ready[0] || vt_slot_on_device != slot) return fail(FPX_ERR_STATE, "calcpar: fpx_verttransform_ecmwf of this slot first (its model-level arrays are read on the device)");
-    return cfg.host_real_bytes == 4 ? calcpar_t<float>(slot, c, out) : calcpar_t<double>(slot, c, out);
+    if (!vt_set_ready[0] || vt_slot_on_device[0] != slot) return fail(FPX_ERR_STATE, "calcpar: fpx_verttransform_ecmwf of this slot first (its model-level arrays are read on the device)");
+    return cfg.host_real_bytes == 4 ? calcpar_t<float>(0, slot, c, out) : calcpar_t<double>(0, slot, c, out);
+  }
+  int calcpar_nest(int nest, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) override {
+    if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "calcpar_nest: nest out of range (fpx_nests_init first)");
+    if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "calcpar_nest: slot must be 1 or 2");
+    if (!c || !c->surfstr || !c->sshf || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "calcpar_nest: surfstrn, sshfn, akm, bkm are required");
+    if (c->lsubgrid == 1 && !c->excessoro) return fail(FPX_ERR_ARG, "calcpar_nest: excessoron required with lsubgrid = 1");
+    if (cfg.drydep && !c->vdep && !c->device_vdep) return fail(FPX_ERR_ARG, "calcpar_nest: vdepn (the host's getvdep_nests) required with DRYDEP");
+    if (!vt_set_ready[nest] || vt_slot_on_device[nest] != slot)
+      return fail(FPX_ERR_STATE, "calcpar_nest: fpx_verttransform_nest of this nest and slot first (its model-level arrays are read on the device)");
+    return cfg.host_real_bytes == 4 ? calcpar_t<float>(nest, slot, c, out) : calcpar_t<double>(nest, slot, c, out);
   }
   // ---- getvdep on the device (calcpar.f90:171-189) ------------------------------------------------------------
-  void *gv_tab = nullptr, *gv_land = nullptr, *gv_buf = nullptr;
-  unsigned char *gv_season = nullptr;
+  void *gv_tab = nullptr;                      // the resistance and species tables: shared by the mother grid and the nests
+  void *gv_land[1 + kMaxNests] = {}, *gv_buf[1 + kMaxNests] = {};   // per grid (0 = mother, l = nest l): xlanduse / xlandusen(:,:,:,l); inputs and vdep planes
+  unsigned char *gv_season[1 + kMaxNests] = {};
+  int gv_land_classes[1 + kMaxNests] = {};    // numclass the grid's gv_land was sized for
   gv::Layout gv_lay{0, 0, 0};
   double gv_bdate = 0, gv_last_ms = 0;
-  bool gv_ready = false;
+  bool gv_ready = false, gv_nest_ready[kMaxNests] = {};
 
   template <typename H>
   int getvdep_init_t(const fpx_getvdep_tables *t) {
@@ -963,12 +1001,13 @@ struct Engine : EngineBase {
     const size_t n2 = (size_t)cfg.nxmax * cfg.nymax;
     int rc;
     gv_ready = false;
+    for (int l = 0; l < kMaxNests; l++) gv_nest_ready[l] = false;    // xlandusen follows the tables: fpx_getvdep_nest_init again
     if (!gv_tab || Ly.numclass != gv_lay.numclass || Ly.ni != gv_lay.ni || Ly.maxspec != gv_lay.maxspec) {
       H *q = nullptr;
       if ((rc = dalloc(&q, (size_t)Ly.total()))) return rc;
       gv_tab = q;
       if ((rc = dalloc(&q, n2 * Ly.numclass))) return rc;
-      gv_land = q;
+      gv_land[0] = q;
     }
     std::vector<H> pk((size_t)Ly.total());
     auto put = [&](int off, const void *src, size_t n) { memcpy(pk.data() + off, src, n * sizeof(H)); };
@@ -979,7 +1018,7 @@ struct Engine : EngineBase {
     for (int i = 0; i < 6; i++) put(Ly.spec() + i * ms, sp[i], ms);
     put(Ly.vset(), t->vset, (size_t)ms * Ly.ni); put(Ly.vset() + ms * Ly.ni, t->schmi, (size_t)ms * Ly.ni); put(Ly.vset() + 2 * ms * Ly.ni, t->fract, (size_t)ms * Ly.ni);
     HIPCHK(hipMemcpyAsync(gv_tab, pk.data(), pk.size() * sizeof(H), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(gv_land, t->xlanduse, n2 * nc * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(gv_land[0], t->xlanduse, n2 * nc * sizeof(H), hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     gv_lay = Ly;
     gv_bdate = t->bdate;
@@ -997,6 +1036,25 @@ struct Engine : EngineBase {
     const gv::Layout Ly{t->numclass, t->ni, t->maxspec};
     if ((size_t)Ly.total() * cfg.host_real_bytes > (size_t)60 * 1024) return fail(FPX_ERR_ARG, "getvdep_init: the resistance tables do not fit the LDS of a block (60 KiB)");
     return cfg.host_real_bytes == 4 ? getvdep_init_t<float>(t) : getvdep_init_t<double>(t);
+  }
+  // xlandusen(0:nxmaxn-1,0:nymaxn-1,numclass,l) of nested grid `nest`; the resistance and species tables are fpx_getvdep_init's
+  int getvdep_nest_init(int nest, const void *xlandusen) override {
+    if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "getvdep_nest_init: nest out of range (fpx_nests_init first)");
+    if (!xlandusen) return fail(FPX_ERR_ARG, "getvdep_nest_init: xlandusen is required");
+    if (!cfg.drydep) return fail(FPX_ERR_ARG, "getvdep_nest_init: the run has no dry deposition (DRYDEP)");
+    if (!gv_ready) return fail(FPX_ERR_STATE, "getvdep_nest_init: fpx_getvdep_init first (numclass and the resistance tables are shared)");
+    const size_t bytes = (size_t)nest_nxmaxn * nest_nymaxn * gv_lay.numclass * cfg.host_real_bytes;
+    int rc;
+    if (!gv_land[nest] || gv_land_classes[nest] != gv_lay.numclass) {
+      char *q = nullptr;
+      if ((rc = dalloc(&q, bytes))) return rc;
+      gv_land[nest] = q;
+      gv_land_classes[nest] = gv_lay.numclass;
+    }
+    HIPCHK(hipMemcpyAsync(gv_land[nest], xlandusen, bytes, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    gv_nest_ready[nest - 1] = true;
+    return 0;
   }
 
   // caldate.f90:42-65 (the date part), its default-real literals in the host's real kind H
@@ -1033,12 +1091,13 @@ struct Engine : EngineBase {
     }
     return 10000 * yyyy + 100 * mm + dd;
   }
-  // getvdep.f90:51-77: the seasonal category of every grid row at wind-field time wftime
+  // getvdep.f90:51-77: the seasonal category of every grid row at wind-field time wftime.  The rows of a nest go through
+  // the very same formula, ylat = jy*dy + ylat0 with the MOTHER grid's dy, ylat0 (getvdep_nests.f90:54), over its nyn rows
   template <typename H>
-  void gv_seasons(int wftime, std::vector<unsigned char> &ls) {
+  void gv_seasons(int wftime, std::vector<unsigned char> &ls, int ny) {
 #pragma clang fp contract(off)
-    ls.resize(cfg.ny);
-    for (int jy = 0; jy < cfg.ny; jy++) {
+    ls.resize(ny);
+    for (int jy = 0; jy < ny; jy++) {
       double jul = gv_bdate + (double)wftime / 86400.;
       const H ylat = (H)jy * (H)cfg.dy + (H)cfg.ylat0;
       if (ylat < (H)0) jul = jul + (double)(365 / 2);
@@ -1056,49 +1115,53 @@ struct Engine : EngineBase {
     }
   }
 
+  // gr = 0: the mother grid (calcpar.f90:171-189 with getvdep.f90); gr = l >= 1: nested grid l (calcpar_nests.f90:139-157 with
+  // getvdep_nests.f90): the same kernel on the nest's arrays and xlandusen(:,:,:,l), with buffers and a gather pack of the nest's own
   template <typename H>
-  int getvdep_t(int slot, const fpx_getvdep_in *g, void *vdep_out) {
+  int getvdep_t(int gr, int slot, const fpx_getvdep_in *g, void *vdep_out) {
+    const HostGrid HG = host_grid(gr);
+    const WindDst T = wind_dst(gr);
     const int s = slot - 1, nspec = cfg.nspec;
-    const size_t n2 = (size_t)cfg.nxmax * cfg.nymax;
+    const size_t n2 = (size_t)HG.nxmax * HG.nymax;
     int rc;
-    if (!gv_buf) {
+    if (!gv_buf[gr]) {
       H *q = nullptr;
       if ((rc = dalloc(&q, (9 + (size_t)FPX_MAXSPEC) * n2))) return rc;      // ssr, lsprec, convprec, sd, ustar, oli, ps, tt2, td2 | vdep planes
       HIPCHK(hipMemsetAsync(q, 0, (9 + (size_t)FPX_MAXSPEC) * n2 * sizeof(H), stream));
-      gv_buf = q;
-      if ((rc = dalloc(&gv_season, (size_t)cfg.ny))) return rc;
+      gv_buf[gr] = q;
+      if ((rc = dalloc(&gv_season[gr], (size_t)HG.ny))) return rc;
     }
-    H *B = (H *)gv_buf;
+    H *B = (H *)gv_buf[gr];
     const void *host[9] = {g->ssr, g->lsprec, g->convprec, g->sd, g->ustar, g->oli, g->ps, g->tt2, g->td2};
     const H *dev[9];
     for (int i = 0; i < 9; i++) {
       dev[i] = B + i * n2;
       if (host[i]) HIPCHK(hipMemcpyAsync(B + i * n2, host[i], n2 * sizeof(H), hipMemcpyHostToDevice, stream));
     }
-    if (!g->ustar) dev[4] = (const H *)cp_buf + 3 * n2;                        // what fpx_calcpar left (calcpar_t)
-    if (!g->oli) dev[5] = (const H *)cp_buf + 5 * n2;
+    if (!g->ustar) dev[4] = (const H *)cp_buf[gr] + 3 * n2;                    // what fpx_calcpar / fpx_calcpar_nest of this grid left (calcpar_t)
+    if (!g->oli) dev[5] = (const H *)cp_buf[gr] + 5 * n2;
     for (int i = 6; i < 9; i++)
-      if (!host[i]) dev[i] = (const H *)vt_sets[0][i];                         // PS, TT2, TD2 of the transform (verttransform_t)
+      if (!host[i]) dev[i] = (const H *)vt_sets[gr][i];                        // PS, TT2, TD2 of the grid's transform (verttransform_t)
     std::vector<unsigned char> ls;
-    gv_seasons<H>(g->wftime, ls);
-    HIPCHK(hipMemcpyAsync(gv_season, ls.data(), ls.size(), hipMemcpyHostToDevice, stream));
+    gv_seasons<H>(g->wftime, ls, HG.ny);
+    HIPCHK(hipMemcpyAsync(gv_season[gr], ls.data(), ls.size(), hipMemcpyHostToDevice, stream));
     gv::Args<H> A;
-    A.nx = cfg.nx; A.ny = cfg.ny; A.nxmax = cfg.nxmax; A.nymax = cfg.nymax; A.nspec = nspec;
-    A.T = gv_lay; A.tables = (const H *)gv_tab; A.xlanduse = (const H *)gv_land;
+    A.nx = HG.nx; A.ny = HG.ny; A.nxmax = HG.nxmax; A.nymax = HG.nymax; A.nspec = nspec;
+    A.T = gv_lay; A.tables = (const H *)gv_tab; A.xlanduse = (const H *)gv_land[gr];
     A.ssr = dev[0]; A.lsprec = dev[1]; A.convprec = dev[2]; A.sd = dev[3]; A.ustar = dev[4]; A.oli = dev[5]; A.ps = dev[6]; A.tt2 = dev[7]; A.td2 = dev[8];
-    A.lseason = gv_season;
+    A.lseason = gv_season[gr];
     H *d_vdep = B + 9 * n2;
     A.vdep = d_vdep;
     Events<2> ev;
     HIPCHK(ev.create());
     HIPCHK(hipEventRecord(ev[0], stream));
-    gv::k_getvdep<H><<<(cfg.nx * cfg.ny + 255) / 256, 256, (size_t)gv_lay.total() * sizeof(H), stream>>>(A);
+    gv::k_getvdep<H><<<(HG.nx * HG.ny + 255) / 256, 256, (size_t)gv_lay.total() * sizeof(H), stream>>>(A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev[1], stream));
-    // into the gather pack, as upload_fields does from the host's vdep(0,0,1,n) planes
-    const int tot = cfg.nx * cfg.ny;
+    // into the gather pack, as upload_fields / upload_nest_fields do from the host's vdep(0,0,1,n) planes
+    const int tot = HG.nx * HG.ny;
     for (int ks = 0; ks < nspec; ks++) {
-      k_pack2<H, R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>(d_vdep + n2 * ks, (R *)V.vdep, cfg.nx, cfg.ny, cfg.nxmax, 2 * nspec, s * nspec + ks);
+      k_pack2<H, R><<<(tot + kBlock - 1) / kBlock, kBlock, 0, stream>>>(d_vdep + n2 * ks, (R *)T.vdep, HG.nx, HG.ny, HG.nxmax, 2 * nspec, s * nspec + ks);
       HIPCHK(hipGetLastError());
     }
     if (vdep_out) HIPCHK(hipMemcpyAsync(vdep_out, d_vdep, n2 * nspec * sizeof(H), hipMemcpyDeviceToHost, stream));
@@ -1106,7 +1169,9 @@ struct Engine : EngineBase {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
     gv_last_ms = ms;
-    if (vdep_pending[s]) { vdep_pending[s] = false; slot_loaded[s] = true; }   // fpx_calcpar(device_vdep = 1) was waiting for this
+    // fpx_calcpar / fpx_calcpar_nest (device_vdep = 1) was waiting for this
+    if (gr == 0) { if (vdep_pending[s]) { vdep_pending[s] = false; slot_loaded[s] = true; } }
+    else if (nest_vdep_pending[gr - 1][s]) { nest_vdep_pending[gr - 1][s] = false; nest_loaded[gr - 1][s] = true; }
     return 0;
   }
   int getvdep(int slot, const fpx_getvdep_in *g, void *vdep_out) override {
@@ -1114,11 +1179,23 @@ struct Engine : EngineBase {
     if (!cfg.drydep || !V.vdep) return fail(FPX_ERR_ARG, "getvdep: the run has no dry deposition (DRYDEP)");
     if (!gv_ready) return fail(FPX_ERR_STATE, "getvdep: fpx_getvdep_init first (the land-use inventory and the resistance tables)");
     if (!g || !g->ssr || !g->lsprec || !g->convprec || !g->sd) return fail(FPX_ERR_ARG, "getvdep: ssr, lsprec, convprec, sd are required");
-    if ((!g->ustar || !g->oli) && (!cp_buf || cp_slot_on_device != slot))
+    if ((!g->ustar || !g->oli) && (!cp_buf[0] || cp_slot_on_device[0] != slot))
       return fail(FPX_ERR_ARG, "getvdep: ustar / oli = NULL means the ones fpx_calcpar left on the device: fpx_calcpar of this slot first");
-    if ((!g->ps || !g->tt2 || !g->td2) && (!vt_set_ready[0] || vt_slot_on_device != slot))
+    if ((!g->ps || !g->tt2 || !g->td2) && (!vt_set_ready[0] || vt_slot_on_device[0] != slot))
       return fail(FPX_ERR_ARG, "getvdep: ps / tt2 / td2 = NULL means the ones of fpx_verttransform_ecmwf: transform this slot first");
-    return cfg.host_real_bytes == 4 ? getvdep_t<float>(slot, g, vdep_out) : getvdep_t<double>(slot, g, vdep_out);
+    return cfg.host_real_bytes == 4 ? getvdep_t<float>(0, slot, g, vdep_out) : getvdep_t<double>(0, slot, g, vdep_out);
+  }
+  int getvdep_nest(int nest, int slot, const fpx_getvdep_in *g, void *vdep_out) override {
+    if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "getvdep_nest: nest out of range (fpx_nests_init first)");
+    if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "getvdep_nest: slot must be 1 or 2");
+    if (!cfg.drydep || !h_nest[nest - 1].vdep) return fail(FPX_ERR_ARG, "getvdep_nest: the run has no dry deposition (DRYDEP)");
+    if (!gv_ready || !gv_nest_ready[nest - 1]) return fail(FPX_ERR_STATE, "getvdep_nest: fpx_getvdep_init, then fpx_getvdep_nest_init of this nest first (the tables and the nest's land-use inventory)");
+    if (!g || !g->ssr || !g->lsprec || !g->convprec || !g->sd) return fail(FPX_ERR_ARG, "getvdep_nest: ssrn, lsprecn, convprecn, sdn are required");
+    if ((!g->ustar || !g->oli) && (!cp_buf[nest] || cp_slot_on_device[nest] != slot))
+      return fail(FPX_ERR_ARG, "getvdep_nest: ustarn / olin = NULL means the ones fpx_calcpar_nest left on the device: fpx_calcpar_nest of this nest and slot first");
+    if ((!g->ps || !g->tt2 || !g->td2) && (!vt_set_ready[nest] || vt_slot_on_device[nest] != slot))
+      return fail(FPX_ERR_ARG, "getvdep_nest: psn / tt2n / td2n = NULL means the ones of fpx_verttransform_nest: transform this nest and slot first");
+    return cfg.host_real_bytes == 4 ? getvdep_t<float>(nest, slot, g, vdep_out) : getvdep_t<double>(nest, slot, g, vdep_out);
   }
   double gv_ms() override { return gv_last_ms; }
   double vt_last_ms = 0, po_last_ms = 0;
@@ -1145,8 +1222,8 @@ struct Engine : EngineBase {
       return fail(FPX_ERR_ARG, "verttransform_nest: uuhn, vvhn, wwhn, tthn, qvhn, psn, tt2n, td2n, akz, bkz, aknew, bknew are required (pvhn = NULL: calcpv_nests on the device)");
     if (m->nuvz != cfg.nz || m->nwz != cfg.nz) return fail(FPX_ERR_ARG, "verttransform_nest: nuvz = nwz = nz expected");
     if (!(m->nest_dy > 0)) return fail(FPX_ERR_ARG, "verttransform_nest: nest_dy (dyn) and nest_ylat0 (ylat0n) of fpx_model_levels are required");
-    if (!sfc || !sfc->hmix || !sfc->ustar || !sfc->wstar || !sfc->oli || !sfc->tropopause) return fail(FPX_ERR_ARG, "verttransform_nest: hmixn, ustarn, wstarn, olin, tropopausen are required");
-    if (cfg.drydep && !sfc->vdep) return fail(FPX_ERR_ARG, "verttransform_nest: vdepn required with DRYDEP");
+    if (sfc && (!sfc->hmix || !sfc->ustar || !sfc->wstar || !sfc->oli || !sfc->tropopause)) return fail(FPX_ERR_ARG, "verttransform_nest: hmixn, ustarn, wstarn, olin, tropopausen are required (or sfc = NULL and fpx_calcpar_nest)");
+    if (sfc && cfg.drydep && !sfc->vdep) return fail(FPX_ERR_ARG, "verttransform_nest: vdepn required with DRYDEP");
     if (!m->pvh) {
       if (!pv_ready) return fail(FPX_ERR_STATE, "verttransform_nest: fpx_calcpv_init first (dxn of the nests) to compute pvhn on the device");
       if (!(pv_dxn[nest - 1] > 0)) return fail(FPX_ERR_ARG, "verttransform_nest: dxn of this nest (fpx_calcpv_init) must be positive");
@@ -4725,6 +4802,9 @@ int fpx_partoutput_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) retur
 int fpx_calcpar(fpx_handle h, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) { FPX_GUARD(h); return h->impl->calcpar(slot, c, out); }
 int fpx_getvdep_init(fpx_handle h, const fpx_getvdep_tables *t) { FPX_GUARD(h); return h->impl->getvdep_init(t); }
 int fpx_getvdep(fpx_handle h, int32_t slot, const fpx_getvdep_in *g, void *vdep_out) { FPX_GUARD(h); return h->impl->getvdep(slot, g, vdep_out); }
+int fpx_calcpar_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) { FPX_GUARD(h); return h->impl->calcpar_nest(nest, slot, c, out); }
+int fpx_getvdep_nest_init(fpx_handle h, int32_t nest, const void *xlandusen) { FPX_GUARD(h); return h->impl->getvdep_nest_init(nest, xlandusen); }
+int fpx_getvdep_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_getvdep_in *g, void *vdep_out) { FPX_GUARD(h); return h->impl->getvdep_nest(nest, slot, g, vdep_out); }
 int fpx_calcpv_init(fpx_handle h, const fpx_calcpv_cfg *c) { FPX_GUARD(h); return h->impl->calcpv_init(c); }
 int fpx_get_pvh(fpx_handle h, int32_t nest, void *pvh_out) { FPX_GUARD(h); return h->impl->get_pvh(nest, pvh_out); }
 int fpx_calcpv_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_calcpv_time: null"); *ms = h->impl->pv_ms(); return FPX_OK; }

@@ -2,7 +2,8 @@
 // with getvdep.f90, getrb.f90, getrc.f90, raerod.f90, psih.f90 and partdep.f90, from ustar and oli (which fpx_calcpar has
 // just written on the device), ps, tt2, td2 (of fpx_verttransform_ecmwf) and the four 2-D fields ssr, lsprec, convprec, sd.
 // The land-use inventory (xlanduse) and the resistance tables stay the host's: they are read once at start-up and come in
-// through fpx_getvdep_init as plain arrays of com_mod.  Mother grid only: getvdep_nests / vdepn stay an input of the host.
+// through fpx_getvdep_init as plain arrays of com_mod.  A nested grid (getvdep_nests.f90) runs the same kernel on its own
+// view: nxn, nyn, strides nxmaxn, nymaxn, xlandusen(:,:,:,l) of fpx_getvdep_nest_init, and a season table over its nyn rows.
 // One lane per grid column; consecutive lanes own consecutive ix, so every read of a 2-D field and of one class plane of
 // xlanduse is one contiguous row segment.  The small tables (z0, ri, rac, rcl/rgs/rlu, the per-species constants, vset,
 // schmi, fract) sit in LDS, loaded once per block.  z0(7), which calcpar.f90:174 overwrites per column, is lane-private and

@@ -53,6 +53,8 @@ class Engine:
         self.nxmax, self.nymax, self.nzmax = nx + pad[0], ny + pad[1], nz + pad[2]
         self.nest_pad = (int(nest_pad[0]), int(nest_pad[1]))
         self._nest_extent = (0, 0)                      # nxn, nyn of nest 1 once init_nest has run
+        self._nest_extents = []                         # nxn, nyn of every nest (init_nest, init_nests)
+        self._nest_max = None                           # nxmaxn, nymaxn
         dx, dy, xlon0, ylat0 = (float(v) for v in sc["geom"])
         xg, ng, sg = (int(v) for v in sc["globalflags"])
         nspec = int(sc["nspec"])
@@ -163,7 +165,8 @@ class Engine:
         """compact [...][nyn][nxn] nest array -> the host's [...][nymaxn][nxmaxn] (nest_pad), the leading axis grown to nlev."""
         a = np.asarray(a)
         lead = a.shape[:-2] if nlev is None else (nlev,) + a.shape[1:-2]
-        out = np.zeros(lead + (a.shape[-2] + self.nest_pad[1], a.shape[-1] + self.nest_pad[0]), dtype or self.hreal)
+        nxmaxn, nymaxn = self._nest_max or (a.shape[-1] + self.nest_pad[0], a.shape[-2] + self.nest_pad[1])   # one nxmaxn, nymaxn for all nests
+        out = np.zeros(lead + (nymaxn, nxmaxn), dtype or self.hreal)
         out[tuple(slice(0, n) for n in a.shape)] = a
         return out
 
@@ -194,8 +197,8 @@ class Engine:
         Returns the z-level arrays asked for (compact), height and nmixz."""
         from ._lib import FpxModelLevels, FpxFieldsOut
         rt = self.hreal
-        if nest is not None:      # m is the nest's input (synthetic.nest_model_levels): fpx_verttransform_nest, nest 1
-            return self._verttransform_nest(slot, m, sfc, want, device_pv)
+        if nest is not None:      # m is the nest's input (synthetic.nest_model_levels): fpx_verttransform_nest of nest `nest` (1-based)
+            return self._verttransform_nest(slot, m, sfc, want, device_pv, nest=int(nest))
         keep = {} if host_arrays is None else host_arrays     # host_arrays: a dict the caller keeps alive -> arrays stay put and are pinned
         ml = FpxModelLevels()
         ml.pin_host = 0 if host_arrays is None else 1
@@ -352,7 +355,72 @@ class Engine:
         check(self.lib.fpx_getvdep_time(self.h, C.byref(ms)), "fpx_getvdep_time")
         return dict(vdep=out[:, : self.ny, : self.nx].astype(np.float64), device_ms=ms.value, call_ms=call_s * 1e3)
 
-    def _verttransform_nest(self, slot, n, sfc, want, device_pv=False):
+    def _nest_compact(self, a, nest):
+        nxn, nyn = self._nest_extents[nest - 1]
+        return a[..., :nyn, :nxn].astype(np.float64)
+
+    def calcpar_nest(self, nest, slot, cin, vdep=None, device_vdep=False, padded=False):
+        """fpx_calcpar_nest after verttransform(slot, n, None, nest=nest): cin = synthetic.calcpar_inputs(n) of the nest (compact
+        [nyn][nxn]).  Returns the five 2-D fields (compact; padded: the host-shaped arrays as copied back) and the device time."""
+        from ._lib import FpxCalcparIn, FpxCalcparOut
+        rt = self.hreal
+        keep = {}
+        c = FpxCalcparIn()
+        for k in ("surfstr", "sshf", "excessoro"):
+            if cin.get(k) is None:
+                continue
+            keep[k] = self._nest_host(cin[k])
+            setattr(c, k, keep[k].ctypes.data)
+        for k in ("akm", "bkm"):
+            keep[k] = np.ascontiguousarray(np.asarray(cin[k]).astype(rt))
+            setattr(c, k, keep[k].ctypes.data)
+        c.lsubgrid = int(cin["lsubgrid"])
+        c.device_vdep = int(bool(device_vdep))
+        if vdep is not None:
+            keep["vdep"] = self._nest_host(vdep)
+            c.vdep = keep["vdep"].ctypes.data
+        o = FpxCalcparOut()
+        res = {}
+        for k in ("ustar", "wstar", "oli", "hmix", "tropopause"):
+            res[k] = np.zeros((self._nest_max[1], self._nest_max[0]), rt)
+            setattr(o, k, res[k].ctypes.data)
+        check(self.lib.fpx_calcpar_nest(self.h, int(nest), int(slot), C.byref(c), C.byref(o)), "fpx_calcpar_nest")
+        out = res if padded else {k: self._nest_compact(v, nest) for k, v in res.items()}
+        ms = C.c_double(0)
+        check(self.lib.fpx_calcpar_time(self.h, C.byref(ms)), "fpx_calcpar_time")
+        out["device_ms"] = ms.value
+        return out
+
+    def getvdep_nest_init(self, nest, xlanduse):
+        """fpx_getvdep_nest_init: xlandusen of nest `nest`, compact [numclass][nyn][nxn]; after getvdep_init (the shared tables)."""
+        xl = self._nest_host(xlanduse)
+        check(self.lib.fpx_getvdep_nest_init(self.h, int(nest), _vp(xl)), "fpx_getvdep_nest_init")
+
+    def getvdep_nest(self, nest, slot, gin, given=None):
+        """fpx_getvdep_nest: gin = synthetic.getvdep_inputs() on the nest (wftime and compact [nyn][nxn] ssr, lsprec, convprec, sd);
+        `given`: any of ustar, oli, ps, tt2, td2 as the host's arrays -- what is missing is taken from the device
+        (fpx_calcpar_nest, fpx_verttransform_nest of this nest and slot).  Returns vdepn [nspec][nyn][nxn] as copied back, and the times."""
+        from ._lib import FpxGetvdepIn
+        import time as _time
+        g = FpxGetvdepIn()
+        g.wftime = int(gin["wftime"])
+        keep = {}
+        src = {k: gin[k] for k in ("ssr", "lsprec", "convprec", "sd")}
+        src.update(given or {})
+        for k, v in src.items():
+            if v is None:
+                continue
+            keep[k] = self._nest_host(v)
+            setattr(g, k, keep[k].ctypes.data)
+        out = np.zeros((self.nspec, self._nest_max[1], self._nest_max[0]), self.hreal)
+        t0 = _time.perf_counter()
+        check(self.lib.fpx_getvdep_nest(self.h, int(nest), int(slot), C.byref(g), _vp(out)), "fpx_getvdep_nest")
+        call_s = _time.perf_counter() - t0
+        ms = C.c_double(0)
+        check(self.lib.fpx_getvdep_time(self.h, C.byref(ms)), "fpx_getvdep_time")
+        return dict(vdep=self._nest_compact(out, nest), device_ms=ms.value, call_ms=call_s * 1e3)
+
+    def _verttransform_nest(self, slot, n, sfc, want, device_pv=False, nest=1):
         from ._lib import FpxModelLevels, FpxFieldsOut
         rt = self.hreal
         nxn, nyn = int(n["grid"][0]), int(n["grid"][1])
@@ -372,17 +440,20 @@ class Engine:
         ml.nuvz = ml.nwz = self.nz
         ml.nest_dy, ml.nest_ylat0 = float(rt(n["geom"][1])), float(rt(n["geom"][3]))
         f = FpxFields()
-        for k in ("hmix", "ustar", "wstar", "oli", "tropopause"):
+        for k in ("hmix", "ustar", "wstar", "oli", "tropopause", "vdep"):
+            if sfc is None or (k == "vdep" and "vdep" not in sfc):      # sfc = None: calcpar_nest(nest, slot, ..) follows
+                continue
             keep["s" + k] = self._nest_host(sfc[k])
             setattr(f, k, keep["s" + k].ctypes.data)
         o = FpxFieldsOut()
         res = {}
+        nxmaxn, nymaxn = self._nest_max or (nxn + self.nest_pad[0], nyn + self.nest_pad[1])
         for k in want:
             if k in ("uupol", "vvpol"):
                 continue
-            res[k] = np.zeros((self.nzmax, nyn + self.nest_pad[1], nxn + self.nest_pad[0]), rt)
+            res[k] = np.zeros((self.nzmax, nymaxn, nxmaxn), rt)
             setattr(o, k, res[k].ctypes.data)
-        check(self.lib.fpx_verttransform_nest(self.h, 1, int(slot), C.byref(ml), C.byref(f), C.byref(o)), "fpx_verttransform_nest")
+        check(self.lib.fpx_verttransform_nest(self.h, int(nest), int(slot), C.byref(ml), C.byref(f) if sfc is not None else None, C.byref(o)), "fpx_verttransform_nest")
         return {k: v[: self.nz, :nyn, :nxn].astype(np.float64) for k, v in res.items()}
 
     def upload_diag_fields_from_scenario(self, sc):
@@ -750,21 +821,30 @@ class Engine:
 
     def init_nest(self, nest, nestgeom):
         """fpx_nests_init for one nested grid: geometry as gridcheck_nests.f90:359-372 derives it."""
+        self.init_nests([(nest, nestgeom)])
+
+    def init_nests(self, nests):
+        """fpx_nests_init for the nested grids [((nxn, nyn), (dxn, dyn, xlon0n, ylat0n)), ...]: geometry as
+        gridcheck_nests.f90:359-372 derives it.  The host's arrays of all nests share nxmaxn, nymaxn (par_mod): the largest
+        extents plus nest_pad."""
         rt = self.hreal
-        nxn, nyn = (int(v) for v in nest)
-        self._nest_extent = (nxn, nyn)
-        dxn, dyn, xlon0n, ylat0n = (rt(v) for v in nestgeom)
         dx, dy, xlon0, ylat0 = (rt(self.cfg.dx), rt(self.cfg.dy), rt(self.cfg.xlon0), rt(self.cfg.ylat0))
         n = FpxNests()
         n.struct_bytes = C.sizeof(FpxNests)
-        n.numbnests = 1
-        n.nxmaxn, n.nymaxn = nxn + self.nest_pad[0], nyn + self.nest_pad[1]
-        n.nxn[0], n.nyn[0] = nxn, nyn
-        xaux2 = xlon0n + rt(nxn - 1) * dxn
-        yaux2 = ylat0n + rt(nyn - 1) * dyn
-        n.xresoln[0] = float(dx / dxn); n.yresoln[0] = float(dy / dyn)
-        n.xln[0] = float((xlon0n - xlon0) / dx); n.xrn[0] = float((xaux2 - xlon0) / dx)
-        n.yln[0] = float((ylat0n - ylat0) / dy); n.yrn[0] = float((yaux2 - ylat0) / dy)
+        n.numbnests = len(nests)
+        self._nest_extents = [(int(e[0]), int(e[1])) for e, _ in nests]
+        self._nest_extent = self._nest_extents[0]
+        self._nest_max = (max(e[0] for e in self._nest_extents) + self.nest_pad[0], max(e[1] for e in self._nest_extents) + self.nest_pad[1])
+        n.nxmaxn, n.nymaxn = self._nest_max
+        for l, ((nxn, nyn), nestgeom) in enumerate(nests):
+            nxn, nyn = int(nxn), int(nyn)
+            dxn, dyn, xlon0n, ylat0n = (rt(v) for v in nestgeom)
+            n.nxn[l], n.nyn[l] = nxn, nyn
+            xaux2 = xlon0n + rt(nxn - 1) * dxn
+            yaux2 = ylat0n + rt(nyn - 1) * dyn
+            n.xresoln[l] = float(dx / dxn); n.yresoln[l] = float(dy / dyn)
+            n.xln[l] = float((xlon0n - xlon0) / dx); n.xrn[l] = float((xaux2 - xlon0) / dx)
+            n.yln[l] = float((ylat0n - ylat0) / dy); n.yrn[l] = float((yaux2 - ylat0) / dy)
         check(self.lib.fpx_nests_init(self.h, C.byref(n)), "fpx_nests_init")
 
     def _upload_nest_slot(self, sc, m):

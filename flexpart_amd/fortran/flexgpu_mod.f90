@@ -504,9 +504,29 @@ module flexgpu_mod
       type(c_ptr), value :: h
       integer(c_int32_t), value :: nest, slot
       type(fpx_model_levels), intent(in) :: m
-      type(fpx_fields), intent(in) :: sfc
+      type(c_ptr), value :: sfc            ! c_loc of a type(fpx_fields), or c_null_ptr: flexgpu_calcpar_nests follows
       type(fpx_fields_out), intent(in) :: o
     end function fpx_verttransform_nest
+    integer(c_int) function fpx_calcpar_nest(h, nest, slot, c, o) bind(C, name='fpx_calcpar_nest')
+      import :: c_ptr, c_int, c_int32_t, fpx_calcpar_in, fpx_calcpar_out
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: nest, slot
+      type(fpx_calcpar_in), intent(in) :: c
+      type(fpx_calcpar_out), intent(in) :: o
+    end function fpx_calcpar_nest
+    integer(c_int) function fpx_getvdep_nest_init(h, nest, xlandusen) bind(C, name='fpx_getvdep_nest_init')
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: nest
+      type(c_ptr), value :: xlandusen
+    end function fpx_getvdep_nest_init
+    integer(c_int) function fpx_getvdep_nest(h, nest, slot, g, vdep_out) bind(C, name='fpx_getvdep_nest')
+      import :: c_ptr, c_int, c_int32_t, fpx_getvdep_in
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: nest, slot
+      type(fpx_getvdep_in), intent(in) :: g
+      type(c_ptr), value :: vdep_out
+    end function fpx_getvdep_nest
     integer(c_int) function fpx_get_flux(h, f, allreduce, clear) bind(C, name='fpx_get_flux')
       import :: c_ptr, c_int, c_int32_t
       type(c_ptr), value :: h, f
@@ -1348,19 +1368,25 @@ contains
   ! Replaces `call verttransform_nests(n,uuhn,vvhn,wwhn,pvhn)` (getfields.f90:133,168,184) and the upload of slot n of
   ! every nest; writeback as in flexgpu_verttransform (uun ... drhodzn of slot n).
   ! device_pv = .true.: pvhn is not read; the device computes it (calcpv_nests.f90) -- flexgpu_calcpv_init first.
-  subroutine flexgpu_verttransform_nests(n, uuhn, vvhn, wwhn, pvhn, ierr, writeback, device_pv)
+  ! device_calcpar = .true.: hmixn ... vdepn are not taken from com_mod; flexgpu_calcpar_nests(n, ierr) computes them.
+  subroutine flexgpu_verttransform_nests(n, uuhn, vvhn, wwhn, pvhn, ierr, writeback, device_pv, device_calcpar)
     integer, intent(in) :: n
     real, intent(in) :: uuhn(0:nxmaxn-1,0:nymaxn-1,nuvzmax,maxnests), vvhn(0:nxmaxn-1,0:nymaxn-1,nuvzmax,maxnests)
     real, intent(in) :: pvhn(0:nxmaxn-1,0:nymaxn-1,nuvzmax,maxnests), wwhn(0:nxmaxn-1,0:nymaxn-1,nwzmax,maxnests)
     integer, intent(out) :: ierr
-    logical, intent(in), optional :: writeback, device_pv
+    logical, intent(in), optional :: writeback, device_pv, device_calcpar
     type(fpx_model_levels) :: m
-    type(fpx_fields) :: f
+    type(fpx_fields), target :: f
     type(fpx_fields_out) :: o
+    type(c_ptr) :: fp
     integer :: l
     logical :: wb, dpv
     wb = .true.; if (present(writeback)) wb = writeback
     dpv = .false.; if (present(device_pv)) dpv = device_pv
+    fp = c_loc(f)
+    if (present(device_calcpar)) then
+      if (device_calcpar) fp = c_null_ptr
+    end if
     ierr = 0
     do l = 1, numbnests
       m%uuh = loc_r(uuhn(0:,0,1,l)); m%vvh = loc_r(vvhn(0:,0,1,l)); m%pvh = loc_r(pvhn(0:,0,1,l)); m%wwh = loc_r(wwhn(0:,0,1,l))
@@ -1383,10 +1409,82 @@ contains
         o%tt = loc_r(ttn(0:,0,1,n,l)); o%qv = loc_r(qvn(0:,0,1,n,l)); o%pv = loc_r(pvn(0:,0,1,n,l))
         o%rho = loc_r(rhon(0:,0,1,n,l)); o%drhodz = loc_r(drhodzn(0:,0,1,n,l))
       end if
-      ierr = fpx_verttransform_nest(flexgpu_handle, int(l, c_int32_t), int(n, c_int32_t), m, f, o)
+      ierr = fpx_verttransform_nest(flexgpu_handle, int(l, c_int32_t), int(n, c_int32_t), m, fp, o)
       if (ierr /= 0) return
     end do
   end subroutine flexgpu_verttransform_nests
+
+  ! Replaces `call calcpar_nests(n,uuhn,vvhn,pvhn)` (getfields.f90:132,167,183) for ustarn, wstarn, olin, hmixn, tropopausen
+  ! of slot n of every nest: call after flexgpu_verttransform_nests(n, ..., device_calcpar=.true.).  vdepn: with DRYDEP
+  ! either the host's vdepn(:,:,:,n,l) must exist, or device_vdep = .true. and flexgpu_getvdep_nests(n, ierr) follows.
+  ! writeback (default .true.): the five fields are also copied into com_mod.
+  subroutine flexgpu_calcpar_nests(n, ierr, writeback, device_vdep)
+    integer, intent(in) :: n
+    integer, intent(out) :: ierr
+    logical, intent(in), optional :: writeback, device_vdep
+    type(fpx_calcpar_in) :: c
+    type(fpx_calcpar_out) :: o
+    integer :: l
+    logical :: wb, dv
+    wb = .true.; if (present(writeback)) wb = writeback
+    dv = .false.; if (present(device_vdep)) dv = device_vdep
+    ierr = 0
+    do l = 1, numbnests
+      c%surfstr = loc_r(surfstrn(0:,0,1,n,l)); c%sshf = loc_r(sshfn(0:,0,1,n,l))
+      c%akm = loc_r(akm); c%bkm = loc_r(bkm)
+      c%excessoro = loc_r(excessoron(0:,0,l)); c%lsubgrid = lsubgrid
+      c%vdep = c_null_ptr
+      c%device_vdep = 0
+      if (DRYDEP .and. dv) then
+        c%device_vdep = 1
+      else if (DRYDEP) then
+        c%vdep = loc_r(vdepn(0:,0,1,n,l))
+      end if
+      c%reserved = 0
+      o%ustar = c_null_ptr; o%wstar = c_null_ptr; o%oli = c_null_ptr; o%hmix = c_null_ptr; o%tropopause = c_null_ptr
+      if (wb) then
+        o%ustar = loc_r(ustarn(0:,0,1,n,l)); o%wstar = loc_r(wstarn(0:,0,1,n,l)); o%oli = loc_r(olin(0:,0,1,n,l))
+        o%hmix = loc_r(hmixn(0:,0,1,n,l)); o%tropopause = loc_r(tropopausen(0:,0,1,n,l))
+      end if
+      ierr = fpx_calcpar_nest(flexgpu_handle, int(l, c_int32_t), int(n, c_int32_t), c, o)
+      if (ierr /= 0) return
+    end do
+  end subroutine flexgpu_calcpar_nests
+
+  ! once, after flexgpu_getvdep_init (whose resistance and species tables the nests share): xlandusen of every nest
+  subroutine flexgpu_getvdep_nests_init(ierr)
+    integer, intent(out) :: ierr
+    integer :: l
+    ierr = 0
+    do l = 1, numbnests
+      ierr = fpx_getvdep_nest_init(flexgpu_handle, int(l, c_int32_t), loc_r(xlandusen(0:,0,1,l)))
+      if (ierr /= 0) return
+    end do
+  end subroutine flexgpu_getvdep_nests_init
+
+  ! vdepn(:,:,1:nspec,n,l) of slot n of every nest after flexgpu_calcpar_nests(n, ierr, device_vdep=.true.); as
+  ! getvdep_nests.f90:54 the season of a nest's row is taken from the mother grid's dy, ylat0.
+  subroutine flexgpu_getvdep_nests(n, ierr, writeback)
+    integer, intent(in) :: n
+    integer, intent(out) :: ierr
+    logical, intent(in), optional :: writeback
+    type(fpx_getvdep_in) :: g
+    type(c_ptr) :: vout
+    integer :: l
+    logical :: wb
+    wb = .true.; if (present(writeback)) wb = writeback
+    ierr = 0
+    do l = 1, numbnests
+      g%wftime = int(wftime(n), c_int32_t); g%reserved = 0
+      g%ssr = loc_r(ssrn(0:,0,1,n,l)); g%lsprec = loc_r(lsprecn(0:,0,1,n,l))
+      g%convprec = loc_r(convprecn(0:,0,1,n,l)); g%sd = loc_r(sdn(0:,0,1,n,l))
+      g%ustar = c_null_ptr; g%oli = c_null_ptr; g%ps = c_null_ptr; g%tt2 = c_null_ptr; g%td2 = c_null_ptr
+      vout = c_null_ptr
+      if (wb) vout = loc_r(vdepn(0:,0,1,n,l))
+      ierr = fpx_getvdep_nest(flexgpu_handle, int(l, c_int32_t), int(n, c_int32_t), g, vout)
+      if (ierr /= 0) return
+    end do
+  end subroutine flexgpu_getvdep_nests
 
   ! once, after gridcheck_nests and flexgpu_nests_init: com_mod's dxn, which calcpv_nests.f90:168,171 divides by
   subroutine flexgpu_calcpv_init(ierr)
@@ -1473,7 +1571,7 @@ contains
 
   ! ---- getvdep on the device (the DRYDEP block of calcpar, calcpar.f90:171-189) --------------------------------
   ! once, after readlanduse / readdepo / readspecies / assignland have filled com_mod and after flexgpu_init: the land-use
-  ! inventory of the mother grid and the resistance tables.  (No nest variant: getvdep_nests / vdepn stay the host's.)
+  ! inventory of the mother grid and the resistance tables.  (The nests: flexgpu_getvdep_nests_init, flexgpu_getvdep_nests.)
   subroutine flexgpu_getvdep_init(ierr)
     integer, intent(out) :: ierr
     type(fpx_getvdep_tables) :: t

@@ -879,6 +879,42 @@ def getvdep_inputs(m_or_shape, seed=4200, wftime=0):
 
 
 # --------------------------------------------------------------------------
+# calcpar_nests / getvdep_nests: the same inputs on a nested grid (a nest_model_levels() dict), with patterns and draws of
+# their own, so that a mother-grid array read in a nest's place shows
+# --------------------------------------------------------------------------
+def nest_calcpar_inputs(n, lsubgrid=1):
+    """surfstrn, sshfn, excessoron (compact [nyn][nxn]) and akm, bkm for a nest_model_levels() dict, under the keys of
+    calcpar_inputs()."""
+    c = calcpar_inputs(n, lsubgrid)
+    c["surfstr"] = c["surfstr"][::-1, :].copy() * 1.25
+    c["sshf"] = -c["sshf"][:, ::-1].copy()
+    c["excessoro"] = c["excessoro"][::-1, ::-1].copy()
+    return c
+
+
+def nest_getvdep_tables(n, nspec, seed=4150):
+    """getvdep_tables() whose xlanduse is the nest's xlandusen(:,:,:,l), [numclass][nyn][nxn]; the small tables are the
+    mother grid's (com_mod has one set)."""
+    return getvdep_tables(int(n["grid"][0]), int(n["grid"][1]), nspec, seed=seed)
+
+
+def nest_getvdep_inputs(n_or_shape, seed=4250, wftime=0):
+    """getvdep_inputs() on a nest: ssrn, lsprecn, convprecn, sdn (and, given a shape (nyn, nxn), ustarn, olin, psn, tt2n, td2n)."""
+    return getvdep_inputs(n_or_shape, seed=seed, wftime=wftime)
+
+
+def no_tropopause_columns(n, mask):
+    """A copy of a model_levels() / nest_model_levels() dict in which the columns `mask` [ny][nx] cool by more than 2 K/km
+    all the way to the model top, free of isothermal or inversion layers: no layer meets the thermal-tropopause criterion
+    (calcpar.f90:236-258, calcpar_nests.f90:201-214) there, so the tropopause of such a column keeps its previous value."""
+    out = dict(n)
+    ak, bk, ps = np.asarray(n["akz"]), np.asarray(n["bkz"]), np.asarray(n["ps"])
+    zapprox = -7400.0 * np.log((ak[:, None, None] + bk[:, None, None] * ps[None]) / 101325.0)
+    out["tth"] = np.where(np.asarray(mask)[None], 300.0 - 0.0030 * zapprox, np.asarray(n["tth"]))
+    return out
+
+
+# --------------------------------------------------------------------------
 # calcpv / calcpv_nests: model-level input that drives every branch of the theta-surface search
 # --------------------------------------------------------------------------
 PV_NX, PV_NY, PV_NZ = 37, 29, 20           # nlck = nuvz/3 = 6: searches do run out

@@ -251,7 +251,11 @@ int fpx_verttransform_ecmwf(fpx_handle h, int32_t slot, const fpx_model_levels *
 /* The same for nested grid `nest` (1-based, after fpx_nests_init): replaces `call verttransform_nests(memind(k),
  * uuhn,vvhn,wwhn,pvhn)` (getfields.f90:133,168,184; verttransform_nests.f90:55-420 without its cloud diagnostics) and the
  * fpx_upload_nest_fields of that slot.  Pointers address the nest's arrays of that nest, e.g. c_loc(uuhn(0,0,1,l)),
- * c_loc(tthn(0,0,1,n,l)), strides nxmaxn, nymaxn; the z levels are the mother grid's. */
+ * c_loc(tthn(0,0,1,n,l)), strides nxmaxn, nymaxn; the z levels are the mother grid's.
+ * sfc: as for the mother grid -- the nest's hmixn, ustarn, wstarn, olin, tropopausen, vdepn when calcpar_nests runs on the
+ * host.  sfc = NULL: fpx_calcpar_nest(h, nest, slot, ..) follows and computes them on the device; until it has run the
+ * nest's slot is "not loaded" and fpx_step / fpx_releaseparticles refuse it (FPX_ERR_STATE).  nest_dy, nest_ylat0 of
+ * this call are remembered per nest (the latitude of calcpar_nests.f90:73). */
 int fpx_verttransform_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out);
 /* device time of the transform kernels of the last call, milliseconds (without the PV kernels of a call with pvh = NULL) */
 int fpx_verttransform_time(fpx_handle h, double *ms);
@@ -296,13 +300,26 @@ typedef struct {
 /* optional copies back into the host's arrays of slot n (NULL members are skipped), e.g. c_loc(hmix(0,0,1,n)) */
 typedef struct { void *ustar, *wstar, *oli, *hmix, *tropopause; } fpx_calcpar_out;
 int fpx_calcpar(fpx_handle h, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out);
-/* device time of the kernel of the last fpx_calcpar call, milliseconds */
+/* The same for nested grid `nest` (1-based): replaces one iteration l of the loop of calcpar_nests.f90:63-225 -- without its
+ * getvdep_nests block (:139-157, fpx_getvdep_nest below or the host's vdepn) and without calcpv_nests (:223, the
+ * transform's).  The same kernel as fpx_calcpar runs on the nest's arrays: the model levels fpx_verttransform_nest(h,
+ * nest, slot, m, NULL, ..) uploaded -- it must be the last transform into that nest's buffers -- with extents nxn(l),
+ * nyn(l), strides nxmaxn, nymaxn and the latitude ylat0n(l) + jy*dyn(l) (:73; nest_ylat0, nest_dy of that transform).
+ * c addresses the nest's arrays: c_loc(surfstrn(0,0,1,n,l)), c_loc(sshfn(0,0,1,n,l)), c_loc(excessoron(0,0,l)),
+ * c_loc(vdepn(0,0,1,n,l)) (or device_vdep = 1 and fpx_getvdep_nest next); akm, bkm as for the mother grid.  It writes the
+ * nest's gather packs where fpx_upload_nest_fields writes them and marks the nest's slot loaded (with device_vdep = 1:
+ * once fpx_getvdep_nest has run).  tropopausen lives in a buffer per nest and slot that starts at zero; a column in which
+ * no layer meets the criterion keeps its previous value, as in the reference (:201-214).  out: optional copies back into
+ * the nest's arrays, e.g. c_loc(hmixn(0,0,1,n,l)).  Calls for the mother grid and for the nests may interleave in any
+ * order: every grid has buffers of its own. */
+int fpx_calcpar_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out);
+/* device time of the kernel of the last fpx_calcpar / fpx_calcpar_nest call (whichever grid it was for), milliseconds */
 int fpx_calcpar_time(fpx_handle h, double *ms);
 /* ---- getvdep on the device: the dry-deposition velocities of calcpar (calcpar.f90:171-189) -----------------
  * Replaces the DRYDEP block of calcpar -- z0(7) from ustar, rh = ew(td2)/ew(tt2), `call getvdep(..)` (getvdep.f90 with
  * getrb.f90, getrc.f90, raerod.f90, psih.f90, partdep.f90; the season through caldate.f90) and vdep(ix,jy,i,n) = vd(i) --
- * for the mother grid.  There is no nest variant: getvdep_nests / vdepn stay the host's and remain an input
- * (fpx_upload_nest_fields, fpx_verttransform_nest).  The land-use inventory and the resistance tables are read once at
+ * for the mother grid; fpx_getvdep_nest_init / fpx_getvdep_nest below do the same for a nested grid (getvdep_nests.f90;
+ * a host may still pass its own vdepn instead).  The land-use inventory and the resistance tables are read once at
  * start-up by the host and handed over once; what runs on the device is the per-column arithmetic, in the host's real
  * kind.  All pointers address host arrays of com_mod in their own shapes and real kind. */
 typedef struct {
@@ -330,7 +347,21 @@ typedef struct {
  * != NULL, also into the host's planes c_loc(vdep(0,0,1,n)) (nxmax*nymax values per species).  Marks a slot loaded that
  * fpx_calcpar(device_vdep = 1) left waiting.  Refused without DRYDEP and before fpx_getvdep_init. */
 int fpx_getvdep(fpx_handle h, int32_t slot, const fpx_getvdep_in *g, void *vdep_out);
-/* device time of the kernel of the last fpx_getvdep call, milliseconds */
+/* The land-use inventory of nested grid `nest`: c_loc(xlandusen(0,0,1,l)), (0:nxmaxn-1,0:nymaxn-1,numclass) (com_mod.f90).
+ * After fpx_getvdep_init, whose resistance and species tables (and numclass) the nests share; a repeated
+ * fpx_getvdep_init asks for it again. */
+int fpx_getvdep_nest_init(fpx_handle h, int32_t nest, const void *xlandusen);
+/* fpx_getvdep for nested grid `nest`: replaces the DRYDEP block of calcpar_nests (calcpar_nests.f90:139-157) with
+ * getvdep_nests.f90.  g addresses the nest's arrays, c_loc(ssrn(0,0,1,n,l)) ...; the NULL rules are fpx_getvdep's: ustarn,
+ * olin from fpx_calcpar_nest of this nest and slot, psn, tt2n, td2n from fpx_verttransform_nest of this nest and slot.
+ * Writes the nest's vdep pack and, with vdep_out != NULL, c_loc(vdepn(0,0,1,n,l)); marks a slot loaded that
+ * fpx_calcpar_nest(device_vdep = 1) left waiting.  z0(7) per column from ustarn (:142) and rh = ew(td2n)/ew(tt2n) (:146)
+ * as for the mother grid.
+ * The reference is reproduced as written: the seasonal category of row jy of a nest comes from ylat = jy*dy + ylat0 with
+ * the MOTHER grid's dy and ylat0 (getvdep_nests.f90:54), not from the nest's own latitude ylat0n(l) + jy*dyn(l).  A host
+ * that wants the other behaviour keeps computing its own vdepn and passes it (fpx_calcpar_nest, fpx_verttransform_nest). */
+int fpx_getvdep_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_getvdep_in *g, void *vdep_out);
+/* device time of the kernel of the last fpx_getvdep / fpx_getvdep_nest call (whichever grid it was for), milliseconds */
 int fpx_getvdep_time(fpx_handle h, double *ms);
 /* ---- partoutput: the binary particle dump (SURVEY section 8 f, item 4) ----------------------
  * Replaces `call partoutput(itime)` (timemanager.f90:454; the routine: partoutput.f90:63-190):
