@@ -43,6 +43,7 @@
 #include "fpx_probes.hpp"
 #include "fpx_rng_host.hpp"
 #include "fpx_host_res.hpp"
+#include "fpx_recfile.hpp"
 
 namespace fpx {
 
@@ -276,7 +277,6 @@ struct Engine : EngineBase {
   WetNest<R> h_wnest[kMaxNests] = {};     // host copy of the device table Wp.nest
   WetNest<R> *d_wnest = nullptr;
   bool wet_nest_slot[kMaxNests][2] = {};
-  size_t n_grid3 = 0, n_grid2 = 0, n_grid3n = 0, n_grid2n = 0;
   ncclComm_t comm = nullptr;
   int comm_ranks = 1, comm_rank = 0;
   long long rel_global_count = 0;        // particles released so far by all ranks (key of the release's counter RNG)
@@ -284,14 +284,12 @@ struct Engine : EngineBase {
   fpx_allreduce_fn host_allreduce = nullptr;
   void *host_allreduce_user = nullptr;
   Scratch red_pin{true};                 // pinned bounce buffer of the host transport: [send | recv]
-  // Receive buffers of the grid reduction (the reference's gridunc0, drygridunc0, wetgridunc0, griduncn0, ... and
-  // creceptor0: mpi_mod.f90:2451-2492,2543-2569; allocated in outgrid_init.f90:220-225).  The per-rank partial sums
-  // stay untouched in Gp.*: drygridunc / wetgridunc accumulate over the whole run and are reduced again at every
-  // output time.  Allocated on the first reduction.
-  R *gridunc0 = nullptr, *griduncn0 = nullptr, *creceptor0 = nullptr;
-  float *drygridunc0 = nullptr, *wetgridunc0 = nullptr, *drygriduncn0 = nullptr, *wetgriduncn0 = nullptr;
-  bool red_valid[7] = {};                // which receive buffers hold the sums of the last reduction
-  enum { RG_GRID = 0, RG_DRY, RG_WET, RG_GRIDN, RG_DRYN, RG_WETN, RG_REC };
+  // The output accumulators' sums over the ranks (fpx_host_res.hpp), one per accumulator: the reference's gridunc0,
+  // drygridunc0, wetgridunc0, griduncn0, ... and creceptor0 (mpi_mod.f90:2451-2492,2543-2569; allocated in
+  // outgrid_init.f90:220-225), and the same for flux and init_cond.  The per-rank partial sums stay untouched in Gp.*,
+  // fx_flux and ic_grid: drygridunc / wetgridunc accumulate over the whole run and are reduced again at every output
+  // time.  The extents are set where the accumulators are allocated (sum_grid.count() elements of gridunc, ...).
+  RankSum sum_grid, sum_dry, sum_wet, sum_gridn, sum_dryn, sum_wetn, sum_rec, sum_flux, sum_ic;
   Scratch d_sel_tmp;
   int pbl_grid = 0, pbl_per_cu = 0;
   // TABLE_SEQ state
@@ -1304,15 +1302,10 @@ struct Engine : EngineBase {
     const int reclen = 8 + (10 + cfg.nspec) * (int)sizeof(H);
     const size_t recwords = (size_t)reclen / 4 + 2;
     Scratch b_flags, b_idx, b_out, b_tmp;
-    FILE *fh = fopen(path, "wb");
-    if (!fh) return fail(FPX_ERR_ARG, std::string("partoutput: cannot open ") + path);
-    FileCloser closer(fh);
+    RecFile file(path);
+    if (!file.is_open()) return fail(FPX_ERR_ARG, std::string("partoutput: cannot open ") + path);
     unsigned int count = 0;
-    bool io_ok = true;
-    {
-      const int32_t hdr[3] = {4, itime, 4};              // write(unitpartout) itime, partoutput.f90:90
-      io_ok = fwrite(hdr, 4, 3, fh) == 3;
-    }
+    file.scalar((int32_t)itime);                         // write(unitpartout) itime, partoutput.f90:90
     if (n > 0) {
       hipError_t e;
       if ((e = b_flags.reserve(n * sizeof(unsigned int), stream)) != hipSuccess || (e = b_idx.reserve(n * sizeof(unsigned int), stream)) != hipSuccess)
@@ -1360,31 +1353,26 @@ struct Engine : EngineBase {
         };
         const size_t nchunks = (total + chunk - 1) / chunk;
         if (e == hipSuccess) e = issue(0);
-        for (size_t k = 0; e == hipSuccess && io_ok && k < nchunks; k++) {
+        for (size_t k = 0; e == hipSuccess && file.ok() && k < nchunks; k++) {
           e = hipEventSynchronize(done[k & 1]);
           if (e == hipSuccess && k + 1 < nchunks) e = issue(k + 1);
           const size_t nbytes = std::min(chunk, total - k * chunk);
-          if (e == hipSuccess) io_ok = fwrite(pin.as<char>() + (k & 1) * bufsz, 1, nbytes, fh) == nbytes;
+          if (e == hipSuccess) file.write(pin.as<char>() + (k & 1) * bufsz, nbytes);   // the kernel has framed the records
         }
         if (e == hipSuccess) e = hipStreamSynchronize(stream); else (void)hipStreamSynchronize(stream);
         if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("partoutput: ") + hipGetErrorString(e));
       }
     }
     {   // the closing record, partoutput.f90:182-184
-      std::vector<unsigned char> rec(reclen + 8);
-      unsigned char *p = rec.data();
-      const int32_t rl = reclen, m5 = -99999;
+      const int32_t m5 = -99999;
       const H m4 = (H)-9999.9;
-      memcpy(p, &rl, 4); p += 4;
-      memcpy(p, &m5, 4); p += 4;
-      for (int j = 0; j < 3; j++) { memcpy(p, &m4, sizeof(H)); p += sizeof(H); }
-      memcpy(p, &m5, 4); p += 4;
-      for (int j = 0; j < 7 + cfg.nspec; j++) { memcpy(p, &m4, sizeof(H)); p += sizeof(H); }
-      memcpy(p, &rl, 4);
-      io_ok = io_ok && fwrite(rec.data(), 1, rec.size(), fh) == rec.size();
+      file.put(m5);
+      for (int j = 0; j < 3; j++) file.put(m4);
+      file.put(m5);
+      for (int j = 0; j < 7 + cfg.nspec; j++) file.put(m4);
+      file.end();                                        // reclen bytes, as every record of the kernel
     }
-    io_ok = (closer.close() == 0) && io_ok;
-    if (!io_ok) return fail(FPX_ERR_ARG, std::string("partoutput: write error on ") + path);
+    if (!file.close()) return fail(FPX_ERR_ARG, std::string("partoutput: write error on ") + path);
     if (nrec) *nrec = count;
     return 0;
   }
@@ -1897,20 +1885,19 @@ struct Engine : EngineBase {
     // nest = 1: the nested output grid (concoutput_nest.f90: the same algorithm on griduncn, wetgriduncn, drygriduncn, arean, volumen)
     const long long n2 = c->nest ? (long long)Gp.numxgridn * Gp.numygridn : (long long)Gp.numxgrid * Gp.numygrid, n3 = n2 * Gp.numzgrid;
     R *g3 = c->nest ? Gp.griduncn : Gp.gridunc;            // the rank's own partial sums (zeroed afterwards with clear = 1)
-    float *gwet = c->nest ? Gp.wetgriduncn : Gp.wetgridunc, *gdry = c->nest ? Gp.drygriduncn : Gp.drygridunc;
-    const R *s3 = g3;                                      // what is written
-    if (c->reduced) {
-      // the sums over all ranks that fpx_get_grids / fpx_get_wetgrid / fpx_get_grids_nest (allreduce = 1) left in the
-      // receive buffers -- concoutput_mpi.f90:279,298 writes from gridunc0 / drygridunc0 / wetgridunc0
-      const int ig = c->nest ? RG_GRIDN : RG_GRID, id = c->nest ? RG_DRYN : RG_DRY, iw = c->nest ? RG_WETN : RG_WET;
-      if (comm_ranks > 1) {
-        if (!red_valid[ig] || (c->drydep && !red_valid[id]) || (c->wetdep && !red_valid[iw]))
-          return fail(FPX_ERR_STATE, "concoutput: reduced = 1 needs fpx_get_grids / fpx_get_wetgrid / fpx_get_grids_nest with allreduce = 1 first");
-        s3 = c->nest ? griduncn0 : gridunc0;
-        if (c->drydep) gdry = c->nest ? drygriduncn0 : drygridunc0;
-        if (c->wetdep) gwet = c->nest ? wetgriduncn0 : wetgridunc0;
-      }
+    // What is written: with reduced = 1 the sums over all ranks that fpx_get_grids / fpx_get_wetgrid / fpx_get_grids_nest
+    // (allreduce = 1) left in the receive buffers -- concoutput_mpi.f90:279,298 writes from gridunc0 / drygridunc0 /
+    // wetgridunc0 -- of the grids this call writes
+    const void *s3v = nullptr, *sdry = nullptr, *swet = nullptr;
+    {
+      const char *getters = "fpx_get_grids / fpx_get_wetgrid / fpx_get_grids_nest";
+      int rc;
+      if ((rc = source(c->nest ? sum_gridn : sum_grid, g3, c->reduced, "concoutput", getters, &s3v))) return rc;
+      if (c->drydep && (rc = source(c->nest ? sum_dryn : sum_dry, c->nest ? Gp.drygriduncn : Gp.drygridunc, c->reduced, "concoutput", getters, &sdry))) return rc;
+      if (c->wetdep && (rc = source(c->nest ? sum_wetn : sum_wet, c->nest ? Gp.wetgriduncn : Gp.wetgridunc, c->reduced, "concoutput", getters, &swet))) return rc;
     }
+    const R *s3 = (const R *)s3v;
+    const float *gdry = (const float *)sdry, *gwet = (const float *)swet;
     float *d_area = nullptr, *d_vol = nullptr, *val = nullptr, *wr = nullptr;
     unsigned int *nz = nullptr, *rs = nullptr, *rpos = nullptr, *runid = nullptr;
     int *wi = nullptr;
@@ -1952,7 +1939,7 @@ struct Engine : EngineBase {
     std::vector<int> h_wi((size_t)n3);
     std::vector<float> h_wr((size_t)n3);
     // one compressed dump: device work, then the four records (count, indices, count, values)
-    auto dump = [&](auto *grid, size_t class_stride, long long n, const float *scale, int conc, int idx0, FILE *fh, float wm = 1.f) -> int {
+    auto dump = [&](auto *grid, size_t class_stride, long long n, const float *scale, int conc, int idx0, RecFile &file, float wm = 1.f) -> int {
       const int nb = (int)((n + kBlock - 1) / kBlock);
       int32_t ci = 0, cr = 0;
       if (grid) {
@@ -1973,12 +1960,11 @@ struct Engine : EngineBase {
         if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
         if (e2 != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("concoutput: ") + hipGetErrorString(e2));
       }
-      const int32_t four = 4, li = 4 * ci, lr = 4 * cr;
-      bool ok = fwrite(&four, 4, 1, fh) == 1 && fwrite(&ci, 4, 1, fh) == 1 && fwrite(&four, 4, 1, fh) == 1;
-      ok = ok && fwrite(&li, 4, 1, fh) == 1 && (ci == 0 || fwrite(h_wi.data(), 4, (size_t)ci, fh) == (size_t)ci) && fwrite(&li, 4, 1, fh) == 1;
-      ok = ok && fwrite(&four, 4, 1, fh) == 1 && fwrite(&cr, 4, 1, fh) == 1 && fwrite(&four, 4, 1, fh) == 1;
-      ok = ok && fwrite(&lr, 4, 1, fh) == 1 && (cr == 0 || fwrite(h_wr.data(), 4, (size_t)cr, fh) == (size_t)cr) && fwrite(&lr, 4, 1, fh) == 1;
-      return ok ? 0 : fail(FPX_ERR_ARG, "concoutput: write error");
+      file.scalar(ci);
+      file.record(h_wi.data(), (size_t)ci * 4);
+      file.scalar(cr);
+      file.record(h_wr.data(), (size_t)cr * 4);
+      return file.ok() ? 0 : fail(FPX_ERR_ARG, "concoutput: write error");
     };
     int rc = 0;
     for (int ks = 0; ks < cfg.nspec && !rc; ks++)
@@ -1986,26 +1972,26 @@ struct Engine : EngineBase {
         if ((pass == 0 && !want_conc) || (pass == 1 && !want_ppt)) continue;
         char name[1024];
         snprintf(name, sizeof name, "%s%03d", pass == 0 ? prefix : c->prefix_pptv, ks + 1);
-        FILE *fh = fopen(name, "wb");
-        if (!fh) { rc = fail(FPX_ERR_ARG, std::string("concoutput: cannot open ") + name); break; }
-        const int32_t hdr[3] = {4, itime, 4};
-        if (fwrite(hdr, 4, 3, fh) != 3) rc = fail(FPX_ERR_ARG, "concoutput: write error");
+        RecFile file(name);
+        if (!file.is_open()) { rc = fail(FPX_ERR_ARG, std::string("concoutput: cannot open ") + name); break; }
+        file.scalar((int32_t)itime);
+        if (!file.ok()) rc = fail(FPX_ERR_ARG, "concoutput: write error");
         for (int kp = 0; kp < Gp.maxpointspec_act && !rc; kp++)
           for (int nage = 0; nage < Gp.nageclass && !rc; nage++) {
             // element (0,0,[1,]ks,kp,class 0,nage) of the 6-D / 7-D arrays; consecutive classes are class_stride apart
             const size_t o2 = ((((size_t)nage * Gp.nclassunc) * Gp.maxpointspec_act + kp) * Gp.maxspec + ks) * (size_t)n2;
             const size_t cs2 = (size_t)Gp.maxpointspec_act * Gp.maxspec * (size_t)n2;
             const size_t o3 = o2 * Gp.numzgrid, cs3 = cs2 * Gp.numzgrid;
-            rc = dump(c->wetdep && gwet ? gwet + o2 : (float *)nullptr, cs2, n2, d_area, 0, 0, fh);
-            if (!rc) rc = dump(c->drydep && gdry ? gdry + o2 : (float *)nullptr, cs2, n2, d_area, 0, 0, fh);
-            if (!rc) rc = dump(s3 + o3, cs3, n3, d_vol, pass == 0 ? 1 : 2, (int)n2 /* kz is 1-based in the index, :425 */, fh,
+            rc = dump(gwet ? gwet + o2 : (const float *)nullptr, cs2, n2, d_area, 0, 0, file);
+            if (!rc) rc = dump(gdry ? gdry + o2 : (const float *)nullptr, cs2, n2, d_area, 0, 0, file);
+            if (!rc) rc = dump(s3 + o3, cs3, n3, d_vol, pass == 0 ? 1 : 2, (int)n2 /* kz is 1-based in the index, :425 */, file,
                                pass == 1 ? (float)c->weightmolar[ks] : 1.f);
           }
-        if (fclose(fh) != 0 && !rc) rc = fail(FPX_ERR_ARG, "concoutput: write error");
+        if (!file.close() && !rc) rc = fail(FPX_ERR_ARG, "concoutput: write error");
       }
     if (rc) return rc;
     if (clear) {   // gridunc(:,:,:,:,:,:,:)=0., concoutput.f90:714 / griduncn, concoutput_nest.f90 (the deposition grids keep accumulating)
-      HIPCHK(hipMemsetAsync(g3, 0, (c->nest ? n_grid3n : n_grid3) * sizeof(R), stream));
+      HIPCHK(hipMemsetAsync(g3, 0, (c->nest ? sum_gridn : sum_grid).bytes(), stream));
       HIPCHK(hipStreamSynchronize(stream));
     }
     return 0;
@@ -2553,11 +2539,15 @@ struct Engine : EngineBase {
     return sizeof(CkptHeader) + h.rng_bytes + (uint64_t)h.numpart * per_particle + h.n_grid3 * sizeof(R) + 2 * h.n_grid2 * sizeof(float) +
            h.n_grid3n * sizeof(R) + 2 * h.n_grid2n * sizeof(float) + h.n_receptor * sizeof(R) + h.cbase_bytes;
   }
+  // a restore replaces the partial sums of every output grid and of the receptors: whatever was reduced before is stale
+  void invalidate_grid_sums() {
+    for (RankSum *s : {&sum_grid, &sum_dry, &sum_wet, &sum_gridn, &sum_dryn, &sum_wetn, &sum_rec}) s->invalidate();
+  }
   // a restore that failed half-way leaves no usable state behind: no particles, no valid reductions
   int ckpt_invalidate(int rc) {
     numpart = 0;
     maybe_new = true; births_unknown = true;
-    for (bool &v : red_valid) v = false;
+    invalidate_grid_sums();
     (void)hipStreamSynchronize(stream);
     const int nb = (int)((P.cap + kBlock - 1) / kBlock);
     k_fill<int><<<nb, kBlock, 0, stream>>>(P.itra1, kDead, 0, P.cap, nullptr);
@@ -2650,6 +2640,7 @@ struct Engine : EngineBase {
     FILE *fh = fopen(path, "wb");
     if (!fh) return fail(FPX_ERR_ARG, std::string("checkpoint_write: cannot open ") + path);
     FileCloser closer(fh);
+    const size_t n_grid3 = sum_grid.count(), n_grid2 = sum_dry.count(), n_grid3n = sum_gridn.count(), n_grid2n = sum_dryn.count();
     CkptHeader h;
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, "FPXCKPT1", 8);
@@ -2718,6 +2709,7 @@ struct Engine : EngineBase {
       return fail(FPX_ERR_ARG, "checkpoint_read: written with another precision, species count or random-number mode");
     if (h.numpart < 0 || h.numpart > P.cap) return fail(FPX_ERR_ARG, "checkpoint_read: more particles than storage spaces");
     if (h.particle_base != cfg.particle_base || h.seed != V.seed) return fail(FPX_ERR_ARG, "checkpoint_read: another shard or seed");
+    const size_t n_grid3 = sum_grid.count(), n_grid2 = sum_dry.count(), n_grid3n = sum_gridn.count(), n_grid2n = sum_dryn.count();
     const uint64_t g3 = Gp.on ? n_grid3 : 0, g2 = Gp.on ? n_grid2 : 0, g3n = Gp.on && Gp.nested ? n_grid3n : 0, g2n = Gp.on && Gp.nested ? n_grid2n : 0;
     const uint64_t nr = Gp.creceptor ? (uint64_t)Gp.numreceptor * cfg.maxspec : 0;
     if (h.n_grid3 != g3 || h.n_grid2 != g2 || h.n_grid3n != g3n || h.n_grid2n != g2n || h.n_receptor != nr)
@@ -2783,7 +2775,7 @@ struct Engine : EngineBase {
       uint64_t cnt = 0;
       if (fread(&cnt, 8, 1, fh) != 1) return ckpt_invalidate(fail(FPX_ERR_ARG, "checkpoint_read: file too short"));
       if ((rc = ckpt_get_plain(fh, (unsigned char *)fx_flux, n_flux * cfg.host_real_bytes, buf))) return ckpt_invalidate(rc);
-      fx_red_valid = false;
+      sum_flux.invalidate();                 // flux is the file's now
     }
     if (h.reserved & kCkptPartavg) {
       uint64_t cnt = 0;
@@ -2794,9 +2786,9 @@ struct Engine : EngineBase {
       uint64_t cnt = 0;
       if (fread(&cnt, 8, 1, fh) != 1 || cnt != (uint64_t)n_initcond) return ckpt_invalidate(fail(FPX_ERR_ARG, "checkpoint_read: the init_cond grid of the checkpoint is not the one configured"));
       if ((rc = ckpt_get_plain(fh, (unsigned char *)ic_grid, n_initcond * cfg.host_real_bytes, buf))) return ckpt_invalidate(rc);
-      ic_red_valid = false;
+      sum_ic.invalidate();                   // init_cond is the file's now
     }
-    for (bool &v : red_valid) v = false;
+    invalidate_grid_sums();
     rng4 = rs.r4; rng8 = rs.r8; rel_ran1 = rs.rel;
     step_counter = h.step_counter;
     rel_global_count = h.rel_global_count;
@@ -2946,7 +2938,7 @@ struct Engine : EngineBase {
     if (cfg.device_flux) { const int rc = flux_prepare(); if (rc) return rc; }
     if (cfg.device_partavg) { const int rc = partavg_prepare(); if (rc) return rc; }
     if (cfg.device_initcond) HIPCHK(ic_timer.begin(stream));
-    if (cfg.drydep) red_valid[RG_DRY] = red_valid[RG_DRYN] = false;
+    if (cfg.drydep) { sum_dry.invalidate(); sum_dryn.invalidate(); }   // the step's dry deposition adds to drygridunc / drygriduncn
     if (cfg.sort_interval > 0 && step_counter > 0 && step_counter % (unsigned)cfg.sort_interval == 0) {
       int rc = sort_particles();
       if (rc) return rc;
@@ -3374,8 +3366,9 @@ struct Engine : EngineBase {
     Gp.dxout = (R)g->dxout; Gp.dyout = (R)g->dyout; Gp.xoutshift = (R)g->xoutshift; Gp.youtshift = (R)g->youtshift;
     Gp.ind_samp = g->ind_samp; Gp.ioutputforeachrelease = g->ioutputforeachrelease; Gp.lusekerneloutput = g->lusekerneloutput;
     Gp.loutnext = 0; Gp.loutstep = 0;
-    n_grid2 = (size_t)g->numxgrid * g->numygrid * cfg.maxspec * g->maxpointspec_act * g->nclassunc * g->nageclass;
-    n_grid3 = n_grid2 * g->numzgrid;
+    const size_t n_grid2 = (size_t)g->numxgrid * g->numygrid * cfg.maxspec * g->maxpointspec_act * g->nclassunc * g->nageclass;
+    const size_t n_grid3 = n_grid2 * g->numzgrid;
+    sum_grid.shape(n_grid3, sizeof(R)); sum_dry.shape(n_grid2, sizeof(float)); sum_wet.shape(n_grid2, sizeof(float));
     int rc;
     R *oh;
     if ((rc = dalloc(&oh, g->numzgrid))) return rc;
@@ -3411,8 +3404,9 @@ struct Engine : EngineBase {
     if (g->numxgridn < 1 || g->numygridn < 1 || !(g->dxoutn > 0) || !(g->dyoutn > 0)) return fail(FPX_ERR_ARG, "outgrid_nest_init: bad grid");
     Gp.numxgridn = g->numxgridn; Gp.numygridn = g->numygridn;
     Gp.dxoutn = (R)g->dxoutn; Gp.dyoutn = (R)g->dyoutn; Gp.xoutshiftn = (R)g->xoutshiftn; Gp.youtshiftn = (R)g->youtshiftn;
-    n_grid2n = (size_t)g->numxgridn * g->numygridn * Gp.maxspec * Gp.maxpointspec_act * Gp.nclassunc * Gp.nageclass;
-    n_grid3n = n_grid2n * Gp.numzgrid;
+    const size_t n_grid2n = (size_t)g->numxgridn * g->numygridn * Gp.maxspec * Gp.maxpointspec_act * Gp.nclassunc * Gp.nageclass;
+    const size_t n_grid3n = n_grid2n * Gp.numzgrid;
+    sum_gridn.shape(n_grid3n, sizeof(R)); sum_dryn.shape(n_grid2n, sizeof(float)); sum_wetn.shape(n_grid2n, sizeof(float));
     int rc;
     if ((rc = dalloc(&Gp.griduncn, n_grid3n))) return rc;
     if ((rc = dalloc(&Gp.drygriduncn, n_grid2n))) return rc;
@@ -3441,24 +3435,10 @@ struct Engine : EngineBase {
   }
   int get_grids_nest(void *griduncn, void *drygriduncn, void *wetgriduncn, int allreduce, int clear) override {
     if (!Gp.nested) return fail(FPX_ERR_STATE, "get_grids_nest: fpx_outgrid_nest_init first");
-    const R *g3 = Gp.griduncn;
-    const float *gd = Gp.drygriduncn, *gw = Gp.wetgriduncn;
-    if (allreduce && comm_ranks > 1) {
-      // mpi_mod.f90:2543-2569 (mpif_tm_reduce_grid_nest): into the receive buffers, the partial sums stay
-      int rc;
-      if ((rc = reduce_into(Gp.griduncn, &griduncn0, n_grid3n, "get_grids_nest")) || (rc = reduce_into(Gp.drygriduncn, &drygriduncn0, n_grid2n, "get_grids_nest")) ||
-          (rc = reduce_into(Gp.wetgriduncn, &wetgriduncn0, n_grid2n, "get_grids_nest"))) return rc;
-      red_valid[RG_GRIDN] = red_valid[RG_DRYN] = red_valid[RG_WETN] = true;
-      g3 = griduncn0; gd = drygriduncn0; gw = wetgriduncn0;
-    }
-    int rc = download_real(griduncn, g3, n_grid3n);
-    if (rc) return rc;
-    if (drygriduncn) HIPCHK(hipMemcpyAsync(drygriduncn, gd, n_grid2n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (wetgriduncn) HIPCHK(hipMemcpyAsync(wetgriduncn, gw, n_grid2n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    // mpi_mod.f90:2543-2569 (mpif_tm_reduce_grid_nest): into the receive buffers, the partial sums stay.
     // concoutput_nest.f90 zeroes griduncn only; drygriduncn / wetgriduncn accumulate over the run
-    if (clear) HIPCHK(hipMemsetAsync(Gp.griduncn, 0, n_grid3n * sizeof(R), stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    return 0;
+    return fetch({{&sum_gridn, Gp.griduncn, griduncn, true, clear != 0}, {&sum_dryn, Gp.drygriduncn, drygriduncn, false, false},
+                  {&sum_wetn, Gp.wetgriduncn, wetgriduncn, false, false}}, allreduce, "get_grids_nest");
   }
   // receptor points: xreceptor, yreceptor (grid coordinates), receptorarea, readreceptors.f90:88-92
   int receptors_init(int n, const void *x, const void *y, const void *area) override {
@@ -3478,32 +3458,20 @@ struct Engine : EngineBase {
     HIPCHK(hipStreamSynchronize(stream));
     Gp.receptor = d;
     Gp.numreceptor = n;
+    sum_rec.shape((size_t)n * cfg.nspec, sizeof(R));      // the columns of the species in use
     return 0;
   }
   // creceptor(ld, maxspec) of the host (com_mod.f90:660): rows 1..numreceptor, columns 1..nspec are written
   int get_receptors(void *creceptor, int ld, int allreduce, int clear) override {
     if (!Gp.numreceptor) return fail(FPX_ERR_STATE, "get_receptors: fpx_receptors_init first");
     if (creceptor && ld < Gp.numreceptor) return fail(FPX_ERR_ARG, "get_receptors: leading dimension smaller than numreceptor");
-    const size_t n = (size_t)Gp.numreceptor * cfg.nspec;
-    const R *src = Gp.creceptor;
-    if (allreduce && comm_ranks > 1) {
-      int rc = reduce_into(Gp.creceptor, &creceptor0, n, "get_receptors");   // mpi_mod.f90:2480-2484, into creceptor0
-      if (rc) return rc;
-      red_valid[RG_REC] = true;
-      src = creceptor0;
-    }
-    if (creceptor) {
-      std::vector<R> tmp(n);
-      HIPCHK(hipMemcpyAsync(tmp.data(), src, n * sizeof(R), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      for (int ks = 0; ks < cfg.nspec; ks++)
-        for (int i = 0; i < Gp.numreceptor; i++) {
-          const R v = tmp[(size_t)ks * Gp.numreceptor + i];
-          if (cfg.host_real_bytes == 4) ((float *)creceptor)[(size_t)ks * ld + i] = (float)v; else ((double *)creceptor)[(size_t)ks * ld + i] = (double)v;
-        }
-    }
-    if (clear) HIPCHK(hipMemsetAsync(Gp.creceptor, 0, n * sizeof(R), stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    // mpi_mod.f90:2480-2484, into creceptor0; fetched densely in the host's kind, then column by column into the host's array
+    const size_t col = (size_t)Gp.numreceptor * cfg.host_real_bytes;
+    std::vector<unsigned char> tmp(creceptor ? col * cfg.nspec : 0);
+    const int rc = fetch({{&sum_rec, Gp.creceptor, creceptor ? tmp.data() : nullptr, true, clear != 0}}, allreduce, "get_receptors");
+    if (rc) return rc;
+    for (int ks = 0; creceptor && ks < cfg.nspec; ks++)
+      memcpy((unsigned char *)creceptor + (size_t)ks * ld * cfg.host_real_bytes, tmp.data() + ks * col, col);
     return 0;
   }
   int set_output_times(int loutnext, int loutstep) override {
@@ -3515,31 +3483,68 @@ struct Engine : EngineBase {
     if (!height_set || (Gp.ind_samp == -1 && (!slot_loaded[0] || !slot_loaded[1]))) return fail(FPX_ERR_STATE, "conccalc: height / fields not set");
     if (numpart == 0) return 0;
     const int nb = (int)((numpart + kBlock - 1) / kBlock);
-    red_valid[RG_GRID] = red_valid[RG_GRIDN] = red_valid[RG_REC] = false;   // the partial sums move on: earlier reductions are stale
+    sum_grid.invalidate(); sum_gridn.invalidate(); sum_rec.invalidate();   // k_conccalc adds to gridunc, griduncn and creceptor: earlier reductions are stale
     // (wave_kernel_add needs every lane of the wave: whole blocks of kBlock, no early return in the kernel)
     k_conccalc<R><<<nb, kBlock, 0, stream>>>(V, Gp, P, numpart, itime, (R)weight);
     HIPCHK(hipGetLastError());
     return 0;
   }
   // sum over the ranks of `send` into `recv` (device pointers, distinct buffers), on the handle's stream
-  template <typename T>
-  int reduce_into(const T *send, T **recv, size_t n, const char *who) {
-    if (!comm && !host_allreduce) return fail(FPX_ERR_STATE, std::string(who) + ": allreduce requested without fpx_comm_init / fpx_comm_init_host");
-    int rc;
-    if (!*recv && (rc = dalloc(recv, n))) return rc;
+  // n floats (elem = 4) or doubles (elem = 8)
+  int reduce_into(const void *send, void *recv, size_t n, size_t elem, const char *who) {
     if (comm) {
-      ncclResult_t r = ncclAllReduce(send, *recv, n, sizeof(T) == 8 ? ncclDouble : ncclFloat, ncclSum, comm, stream);
+      ncclResult_t r = ncclAllReduce(send, recv, n, elem == 8 ? ncclDouble : ncclFloat, ncclSum, comm, stream);
       if (r != ncclSuccess) return fail(FPX_ERR_DEVICE, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
       return 0;
     }
-    const size_t bytes = n * sizeof(T);
+    const size_t bytes = n * elem;
     HIPCHK(red_pin.reserve(2 * bytes, stream));
     HIPCHK(hipMemcpyAsync(red_pin.as(), send, bytes, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    if (host_allreduce(host_allreduce_user, red_pin.as(), red_pin.as<char>() + bytes, (int64_t)n, sizeof(T) == 8 ? 1 : 0) != 0)
+    if (host_allreduce(host_allreduce_user, red_pin.as(), red_pin.as<char>() + bytes, (int64_t)n, elem == 8 ? 1 : 0) != 0)
       return fail(FPX_ERR_DEVICE, std::string(who) + ": the host's all-reduce callback failed");
-    HIPCHK(hipMemcpyAsync(*recv, red_pin.as<char>() + bytes, bytes, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(recv, red_pin.as<char>() + bytes, bytes, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));    // the bounce buffer is reused by the next grid
+    return 0;
+  }
+  // The three things the getters and the writers do with an accumulator's sums over the ranks (RankSum, fpx_host_res.hpp).
+  // reduce: the sums of the partial sums as they are now, into the receive buffer.  What makes them stale again is said
+  // where it happens: the invalidate() calls next to the launches that add to an accumulator, to its zeroing by
+  // fluxoutput, and to a restored checkpoint.
+  int reduce(RankSum &s, const void *partial, const char *who) {
+    if (!comm && !host_allreduce) return fail(FPX_ERR_STATE, std::string(who) + ": allreduce requested without fpx_comm_init / fpx_comm_init_host");
+    const hipError_t e = s.reserve();
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    const int rc = reduce_into(partial, s.recv(), s.count(), s.elem(), who);
+    if (!rc) s.filled();
+    return rc;
+  }
+  // source: what the writer `who` writes -- the rank's own partial sums, or with reduced = 1 on several ranks the sums that
+  // `getter` (allreduce = 1) left in the receive buffer, provided nothing has been added to the partial sums since
+  int source(const RankSum &s, const void *partial, int reduced, const char *who, const char *getter, const void **src) {
+    *src = partial;
+    if (!reduced || comm_ranks == 1) return 0;
+    if (!s.valid()) return fail(FPX_ERR_STATE, std::string(who) + ": reduced = 1 needs " + getter + " with allreduce = 1 first");
+    *src = s.recv();
+    return 0;
+  }
+  // fetch: the path of the getters.  All accumulators of the call are reduced first if that is asked (on one rank there
+  // is nothing to reduce), then each is downloaded -- in the host's real kind (as_real: an array of R) or as it is; a null
+  // host pointer still reduces -- and zeroed if the getter clears it; one synchronisation.
+  struct Fetch { RankSum *sum; void *partial; void *host; bool as_real, clear; };
+  int fetch(std::initializer_list<Fetch> accs, int allreduce, const char *who) {
+    const bool reduced = allreduce && comm_ranks > 1;
+    int rc;
+    for (const Fetch &a : accs)
+      if (reduced && (rc = reduce(*a.sum, a.partial, who))) return rc;
+    for (const Fetch &a : accs) {
+      const void *src = reduced ? a.sum->recv() : a.partial;
+      if (a.as_real) { if ((rc = download_real(a.host, (const R *)src, a.sum->count()))) return rc; }
+      else if (a.host) HIPCHK(hipMemcpyAsync(a.host, src, a.sum->bytes(), hipMemcpyDeviceToHost, stream));
+    }
+    for (const Fetch &a : accs)
+      if (a.clear) HIPCHK(hipMemsetAsync(a.partial, 0, a.sum->bytes(), stream));
+    HIPCHK(hipStreamSynchronize(stream));
     return 0;
   }
   // [live particles, numpart] of this rank and summed over the ranks: the reduction of numpart the reference's root does at
@@ -3598,40 +3603,27 @@ struct Engine : EngineBase {
   }
   int get_grids(void *gridunc, void *drygridunc, int allreduce, int clear) override {
     if (!Gp.on) return fail(FPX_ERR_STATE, "get_grids: fpx_outgrid_init first");
-    const R *g3 = Gp.gridunc;
-    const float *gd = Gp.drygridunc;
-    if (allreduce && comm_ranks > 1) {
-      // the one collective of the path (mpi_mod.f90:2471-2492): the sums land in gridunc0 / drygridunc0, the
-      // partial sums stay where they are -- drygridunc keeps accumulating and is reduced again at the next output
-      int rc;
-      if ((rc = reduce_into(Gp.gridunc, &gridunc0, n_grid3, "get_grids")) || (rc = reduce_into(Gp.drygridunc, &drygridunc0, n_grid2, "get_grids"))) return rc;
-      red_valid[RG_GRID] = red_valid[RG_DRY] = true;
-      g3 = gridunc0; gd = drygridunc0;
-    }
-    int rc = download_real(gridunc, g3, n_grid3);
-    if (rc) return rc;
-    if (drygridunc) HIPCHK(hipMemcpyAsync(drygridunc, gd, n_grid2 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    // the one collective of the path (mpi_mod.f90:2471-2492): the sums land in gridunc0 / drygridunc0, the partial sums
+    // stay where they are -- drygridunc keeps accumulating and is reduced again at the next output.
     // concoutput.f90:719-720 zeroes gridunc (and creceptor: fpx_get_receptors) only; the deposition grids are
     // cumulative over the run (zeroed once, outgrid_init.f90:317-318)
-    if (clear) HIPCHK(hipMemsetAsync(Gp.gridunc, 0, n_grid3 * sizeof(R), stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    return 0;
+    return fetch({{&sum_grid, Gp.gridunc, gridunc, true, clear != 0}, {&sum_dry, Gp.drygridunc, drygridunc, false, false}}, allreduce, "get_grids");
   }
 
   // ---- gross mass fluxes (fpx_calcfluxes.hpp; fpx_config.device_flux) ------------------------------------------
   // flux and everything the kernels compare a position with are kept in the host's real kind H, whatever the engine
   // computes in: calcfluxes.f90 declares them default real.
-  void *fx_flux = nullptr, *fx_flux0 = nullptr;        // flux_mod's flux; the receive buffer of its reduction
+  void *fx_flux = nullptr;                             // flux_mod's flux (its sums over the ranks: sum_flux)
   void *fx_outh = nullptr, *fx_outhh = nullptr;        // outheight, outheighthalf in H
   void *fx_xold = nullptr, *fx_yold = nullptr, *fx_zold = nullptr, *fx_mass = nullptr;
   unsigned char *fx_due = nullptr;
   size_t n_flux = 0;
   double fx_geo[4] = {};                               // dxout, dyout, xoutshift, youtshift as the host passed them
-  bool fx_red_valid = false;
   IntervalTimer<4> fx_timer{{0, 1}, {2, 3}};           // around k_flux_save | around k_calcfluxes
   template <typename H>
   int flux_init_t(const fpx_outgrid *g, const void *outheight) {
     n_flux = (size_t)6 * g->numxgrid * g->numygrid * g->numzgrid * cfg.nspec * g->maxpointspec_act * g->nageclass;
+    sum_flux.shape(n_flux, sizeof(H));
     fx_geo[0] = g->dxout; fx_geo[1] = g->dyout; fx_geo[2] = g->xoutshift; fx_geo[3] = g->youtshift;
     std::vector<H> oh((const H *)outheight, (const H *)outheight + g->numzgrid), ohh(g->numzgrid);
     {
@@ -3688,7 +3680,7 @@ struct Engine : EngineBase {
     else cf::k_calcfluxes<H, R><<<nb, 256, 0, stream>>>(A, P.xt, P.yt, P.zt, P.npoint, P.itramem, numpart, itime);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(fe[after ? 3 : 1], stream));
-    if (after) { fx_timer.commit(); fx_red_valid = false; }   // the partial sums move on
+    if (after) { fx_timer.commit(); sum_flux.invalidate(); }   // k_calcfluxes adds to flux: the partial sums move on
     return 0;
   }
   int calcfluxes_time(double *ms, long long *launches, int reset) override {
@@ -3697,27 +3689,10 @@ struct Engine : EngineBase {
     if (ms) *ms = t[0] + t[1];
     return 0;
   }
-  template <typename H>
-  int flux_reduce_t() {
-    H *recv = (H *)fx_flux0;
-    const int rc = reduce_into((const H *)fx_flux, &recv, n_flux, "get_flux");
-    fx_flux0 = recv;
-    if (!rc) fx_red_valid = true;
-    return rc;
-  }
   int get_flux(void *flux, int allreduce, int clear) override {
     if (!cfg.device_flux) return fail(FPX_ERR_STATE, "get_flux: the engine was created without device_flux");
     if (!Gp.on || !fx_flux) return fail(FPX_ERR_STATE, "get_flux: fpx_outgrid_init first");
-    const void *src = fx_flux;
-    if (allreduce && comm_ranks > 1) {
-      const int rc = cfg.host_real_bytes == 4 ? flux_reduce_t<float>() : flux_reduce_t<double>();
-      if (rc) return rc;
-      src = fx_flux0;
-    }
-    if (flux) HIPCHK(hipMemcpyAsync(flux, src, n_flux * cfg.host_real_bytes, hipMemcpyDeviceToHost, stream));
-    if (clear) HIPCHK(hipMemsetAsync(fx_flux, 0, n_flux * cfg.host_real_bytes, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    return 0;
+    return fetch({{&sum_flux, fx_flux, flux, false, clear != 0}}, allreduce, "get_flux");   // flux is in the host's kind already
   }
   // fluxoutput.f90:46-283 on the host from the downloaded grid (the grid is small next to the particles, and the file is
   // written record by record anyway), in the host's real kind
@@ -3737,25 +3712,16 @@ struct Engine : EngineBase {
     const int yyyymmdd = gv_caldate<H>(f->bdate + (double)itime / 86400., &hhmiss);
     char name[1200];
     snprintf(name, sizeof name, "%sgrid_flux_%08d%06d", prefix, yyyymmdd, hhmiss);
-    FILE *fh = fopen(name, "wb");
-    if (!fh) return fail(FPX_ERR_ARG, std::string("fluxoutput: cannot open ") + name);
-    std::vector<unsigned char> rec;                    // one unformatted sequential record: length, payload, length
-    bool ok = true;
-    auto put = [&](const void *q, size_t n) { const unsigned char *c = (const unsigned char *)q; rec.insert(rec.end(), c, c + n); };
-    auto flush = [&]() {
-      const int32_t len = (int32_t)rec.size();
-      ok = ok && fwrite(&len, 4, 1, fh) == 1 && (rec.empty() || fwrite(rec.data(), 1, rec.size(), fh) == rec.size()) && fwrite(&len, 4, 1, fh) == 1;
-      rec.clear();
-    };
-    auto put_int = [&](int32_t v) { put(&v, 4); flush(); };
+    RecFile file(name);
+    if (!file.is_open()) return fail(FPX_ERR_ARG, std::string("fluxoutput: cannot open ") + name);
     // :61-134: cells per (species, age class) over all kp, and the sparse test
     std::vector<int> ncells((size_t)6 * ns * na, 0);
     for (int k = 0; k < ns; k++) for (int kp = 0; kp < nkp; kp++) for (int nage = 0; nage < na; nage++)
       for (int jy = 0; jy < nyg; jy++) for (int ix = 0; ix < nxg; ix++) for (int kz = 1; kz <= nzg; kz++)
         for (int i = 1; i <= 6; i++) if (at(i, ix, jy, kz, k, kp, nage) > (H)0) ncells[(size_t)(i - 1) + 6 * ((size_t)k + (size_t)ns * nage)]++;
-    put_int(itime);
+    file.scalar((int32_t)itime);
     const int order[6] = {2, 1, 3, 4, 5, 6};           // eastward, westward, south, north, up, down (:146-276)
-    for (int k = 0; k < ns && ok; k++) for (int kp = 0; kp < nkp && ok; kp++) for (int nage = 0; nage < na && ok; nage++)
+    for (int k = 0; k < ns && file.ok(); k++) for (int kp = 0; kp < nkp && file.ok(); kp++) for (int nage = 0; nage < na && file.ok(); nage++)
       for (int d = 0; d < 6; d++) {
         const int i = order[d];
         auto value = [&](int ix, int jy, int kz) -> H {
@@ -3764,25 +3730,22 @@ struct Engine : EngineBase {
           return (H)1.e12 * at(i, ix, jy, kz, k, kp, nage) / a / outstep;
         };
         if (4 * ncells[(size_t)(i - 1) + 6 * ((size_t)k + (size_t)ns * nage)] < nxg * nyg * nzg) {
-          put_int(1);
+          file.scalar((int32_t)1);
           for (int kz = 1; kz <= nzg; kz++) for (int jy = 0; jy < nyg; jy++) for (int ix = 0; ix < nxg; ix++)
             if (at(i, ix, jy, kz, k, kp, nage) > (H)0) {
               const int32_t idx = ix + jy * nxg + kz * nxg * nyg;
-              const H v = value(ix, jy, kz);
-              put(&idx, 4); put(&v, sizeof(H)); flush();
+              file.put(idx); file.put(value(ix, jy, kz)); file.end();
             }
-          const int32_t m = -999; const H e = (H)999.;
-          put(&m, 4); put(&e, sizeof(H)); flush();
+          file.put((int32_t)-999); file.put((H)999.); file.end();
         } else {
-          put_int(2);
+          file.scalar((int32_t)2);
           for (int kz = 1; kz <= nzg; kz++) for (int ix = 0; ix < nxg; ix++) {
-            for (int jy = 0; jy < nyg; jy++) { const H v = value(ix, jy, kz); put(&v, sizeof(H)); }
-            flush();
+            for (int jy = 0; jy < nyg; jy++) file.put(value(ix, jy, kz));
+            file.end();
           }
         }
       }
-    ok = (fclose(fh) == 0) && ok;
-    if (!ok) return fail(FPX_ERR_ARG, std::string("fluxoutput: write error on ") + name);
+    if (!file.close()) return fail(FPX_ERR_ARG, std::string("fluxoutput: write error on ") + name);
     return 0;
   }
   int fluxoutput(int itime, const fpx_fluxout *f, const char *prefix, int reduced) override {
@@ -3791,16 +3754,14 @@ struct Engine : EngineBase {
     if (!f || f->struct_bytes != (int32_t)sizeof(fpx_fluxout)) return fail(FPX_ERR_ARG, "fluxoutput: null or fpx_fluxout size mismatch (ABI)");
     if (!f->area || !f->areaeast || !f->areanorth || !prefix) return fail(FPX_ERR_ARG, "fluxoutput: area, areaeast, areanorth and the path prefix are required");
     if (strlen(prefix) > 1000) return fail(FPX_ERR_ARG, "fluxoutput: prefix too long");
-    const void *src = fx_flux;
-    if (reduced && comm_ranks > 1) {
-      if (!fx_red_valid) return fail(FPX_ERR_STATE, "fluxoutput: reduced = 1 needs fpx_get_flux with allreduce = 1 first");
-      src = fx_flux0;
-    }
-    const int rc = cfg.host_real_bytes == 4 ? fluxoutput_t<float>(itime, f, prefix, src) : fluxoutput_t<double>(itime, f, prefix, src);
+    const void *src;
+    int rc = source(sum_flux, fx_flux, reduced, "fluxoutput", "fpx_get_flux", &src);
+    if (rc) return rc;
+    rc = cfg.host_real_bytes == 4 ? fluxoutput_t<float>(itime, f, prefix, src) : fluxoutput_t<double>(itime, f, prefix, src);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(fx_flux, 0, n_flux * cfg.host_real_bytes, stream));     // :289-303
     HIPCHK(hipStreamSynchronize(stream));
-    fx_red_valid = false;
+    sum_flux.invalidate();                   // flux starts from zero again: the sums just written are not its sums
     return 0;
   }
 
@@ -3880,12 +3841,10 @@ struct Engine : EngineBase {
   template <typename H>
   int partoutput_average_t(int itime, const char *name, int64_t *nrecords) {
     const long long n = numpart;
-    FILE *fh = fopen(name, "wb");
-    if (!fh) return fail(FPX_ERR_ARG, std::string("partoutput_average: cannot open ") + name);
-    FileCloser closer(fh);
+    RecFile file(name);
+    if (!file.is_open()) return fail(FPX_ERR_ARG, std::string("partoutput_average: cannot open ") + name);
     Scratch b_out, b_stat, pin(true);
     unsigned int hs[2] = {0, 0};
-    bool io_ok = true;
     if (n > 0) {
       hipError_t e = b_out.reserve((size_t)n * 24, stream);
       if (e == hipSuccess) e = b_stat.reserve(2 * sizeof(unsigned int), stream);
@@ -3901,16 +3860,15 @@ struct Engine : EngineBase {
       if (e == hipSuccess) e = hipStreamSynchronize(stream);
       const size_t total = (size_t)hs[1] * 24, chunk = (size_t)64 << 20;
       if (e == hipSuccess && total) e = pin.reserve(std::min(chunk, total), stream);
-      for (size_t off = 0; e == hipSuccess && io_ok && off < total; off += chunk) {
+      for (size_t off = 0; e == hipSuccess && file.ok() && off < total; off += chunk) {
         const size_t nbytes = std::min(chunk, total - off);
         e = hipMemcpyAsync(pin.as(), (const char *)out + off, nbytes, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e == hipSuccess) io_ok = fwrite(pin.as(), 1, nbytes, fh) == nbytes;
+        if (e == hipSuccess) file.write(pin.as(), nbytes);      // direct access: no record markers
       }
       if (e != hipSuccess) return fail(FPX_ERR_DEVICE, std::string("partoutput_average: ") + hipGetErrorString(e));
     }
-    io_ok = (closer.close() == 0) && io_ok;
-    if (!io_ok) return fail(FPX_ERR_ARG, std::string("partoutput_average: write error on ") + name);
+    if (!file.close()) return fail(FPX_ERR_ARG, std::string("partoutput_average: write error on ") + name);
     if (nrecords) *nrecords = hs[0];
     return 0;
   }
@@ -3935,16 +3893,16 @@ struct Engine : EngineBase {
   // init_cond and everything the kernels compare a position with are kept in the host's real kind H, whatever the engine
   // computes in: initial_cond_calc.f90 declares them default real.  Allocated by fpx_outgrid_init, zero at creation;
   // nothing but the `clear` of fpx_get_initcond resets it -- it accumulates over the whole run.
-  void *ic_grid = nullptr, *ic_grid0 = nullptr;        // unc_mod's init_cond; the receive buffer of its reduction
+  void *ic_grid = nullptr;                             // unc_mod's init_cond (its sums over the ranks: sum_ic)
   void *ic_outh = nullptr;                             // outheight in H
   size_t n_initcond = 0;
   double ic_geo[4] = {};                               // dxout, dyout, xoutshift, youtshift as the host passed them
   int ic_iofr = 0;
-  bool ic_red_valid = false;
   IntervalTimer<2> ic_timer{{0, 1}}, ic_fin_timer{{0, 1}};   // k_initcond per step; k_initcond_finish
   template <typename H>
   int initcond_init_t(const fpx_outgrid *g, const void *outheight) {
     n_initcond = (size_t)g->numxgrid * g->numygrid * g->numzgrid * cfg.nspec * g->maxpointspec_act;   // outgrid_init.f90:296 (maxspec -> nspec)
+    sum_ic.shape(n_initcond, sizeof(H));
     ic_geo[0] = g->dxout; ic_geo[1] = g->dyout; ic_geo[2] = g->xoutshift; ic_geo[3] = g->youtshift;
     ic_iofr = g->ioutputforeachrelease;
     int rc;
@@ -3975,7 +3933,7 @@ struct Engine : EngineBase {
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ie[1], stream));
     ic_timer.commit();
-    ic_red_valid = false;
+    sum_ic.invalidate();                     // k_initcond adds the particles this step terminated to init_cond
     return 0;
   }
   // the device time of k_initcond and k_initcond_finish; the launches are the steps that ran k_initcond
@@ -4001,31 +3959,14 @@ struct Engine : EngineBase {
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ie[1], stream));
     ic_fin_timer.commit();
-    ic_red_valid = false;
+    sum_ic.invalidate();                     // k_initcond_finish adds every particle still alive to init_cond
     HIPCHK(hipStreamSynchronize(stream));
     return 0;
-  }
-  template <typename H>
-  int initcond_reduce_t() {
-    H *recv = (H *)ic_grid0;
-    const int rc = reduce_into((const H *)ic_grid, &recv, n_initcond, "get_initcond");
-    ic_grid0 = recv;
-    if (!rc) ic_red_valid = true;
-    return rc;
   }
   int get_initcond(void *init_cond, int allreduce, int clear) override {
     if (!cfg.device_initcond) return fail(FPX_ERR_STATE, "get_initcond: the engine was created without device_initcond");
     if (!Gp.on || !ic_grid) return fail(FPX_ERR_STATE, "get_initcond: fpx_outgrid_init first");
-    const void *src = ic_grid;
-    if (allreduce && comm_ranks > 1) {
-      const int rc = cfg.host_real_bytes == 4 ? initcond_reduce_t<float>() : initcond_reduce_t<double>();
-      if (rc) return rc;
-      src = ic_grid0;
-    }
-    if (init_cond) HIPCHK(hipMemcpyAsync(init_cond, src, n_initcond * cfg.host_real_bytes, hipMemcpyDeviceToHost, stream));
-    if (clear) HIPCHK(hipMemsetAsync(ic_grid, 0, n_initcond * cfg.host_real_bytes, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    return 0;
+    return fetch({{&sum_ic, ic_grid, init_cond, false, clear != 0}}, allreduce, "get_initcond");   // init_cond is in the host's kind already
   }
   // initial_cond_output.f90:58-130 on the host from the downloaded grid, in the host's real kind: per species one
   // unformatted sequential file
@@ -4042,20 +3983,14 @@ struct Engine : EngineBase {
     for (int ks = 0; ks < ns; ks++) {
       char name[1200];
       snprintf(name, sizeof name, "%sgrid_initial_%03d", prefix, ks + 1);
-      FileCloser fc(fopen(name, "wb"));
-      FILE *fh = fc.f;
-      if (!fh) return fail(FPX_ERR_ARG, std::string("initial_cond_output: cannot open ") + name);
-      bool ok = true;
-      auto record = [&](const void *q, size_t n) {      // one unformatted sequential record: length, payload, length
-        const int32_t len = (int32_t)n;
-        ok = ok && fwrite(&len, 4, 1, fh) == 1 && (n == 0 || fwrite(q, 1, n, fh) == n) && fwrite(&len, 4, 1, fh) == 1;
-      };
-      const int32_t it = itime, zero = 0;
-      record(&it, 4);
-      for (int kp = 0; kp < nkp && ok; kp++) {
+      RecFile file(name);
+      if (!file.is_open()) return fail(FPX_ERR_ARG, std::string("initial_cond_output: cannot open ") + name);
+      const int32_t zero = 0;
+      file.scalar((int32_t)itime);
+      for (int kp = 0; kp < nkp && file.ok(); kp++) {
         const H fact_recept = o->ind_rel == 1 ? ((const H *)o->rho_rel)[kp] : (H)1.;
         const H xm = (H)rel_xmass_h[(size_t)ks * np + kp];
-        for (int d = 0; d < 2; d++) { record(&zero, 4); record(nullptr, 0); record(&zero, 4); record(nullptr, 0); }   // :83-92
+        for (int d = 0; d < 2; d++) { file.scalar(zero); file.record(nullptr, 0); file.scalar(zero); file.record(nullptr, 0); }   // :83-92
         di.clear(); dr.clear();
         H sp_fact = (H)-1.;
         bool sp_zer = true;
@@ -4072,11 +4007,10 @@ struct Engine : EngineBase {
           } else sp_zer = true;
         }
         const int32_t ci = (int32_t)di.size(), cr = (int32_t)dr.size();
-        record(&ci, 4); record(di.data(), di.size() * 4);
-        record(&cr, 4); record(dr.data(), dr.size() * sizeof(H));
+        file.scalar(ci); file.record(di.data(), di.size() * 4);
+        file.scalar(cr); file.record(dr.data(), dr.size() * sizeof(H));
       }
-      ok = (fc.close() == 0) && ok;
-      if (!ok) return fail(FPX_ERR_ARG, std::string("initial_cond_output: write error on ") + name);
+      if (!file.close()) return fail(FPX_ERR_ARG, std::string("initial_cond_output: write error on ") + name);
     }
     return 0;
   }
@@ -4089,11 +4023,9 @@ struct Engine : EngineBase {
     if (o->ind_rel == 1 && !o->rho_rel) return fail(FPX_ERR_ARG, "initial_cond_output: ind_rel = 1 needs rho_rel");
     if (V.numpoint < Gp.maxpointspec_act || rel_xmass_h.size() < (size_t)cfg.nspec * V.numpoint)
       return fail(FPX_ERR_STATE, "initial_cond_output: xmass of every release point is needed (fpx_set_release_points)");
-    const void *src = ic_grid;
-    if (reduced && comm_ranks > 1) {
-      if (!ic_red_valid) return fail(FPX_ERR_STATE, "initial_cond_output: reduced = 1 needs fpx_get_initcond with allreduce = 1 first");
-      src = ic_grid0;
-    }
+    const void *src;
+    const int rc = source(sum_ic, ic_grid, reduced, "initial_cond_output", "fpx_get_initcond", &src);
+    if (rc) return rc;
     return cfg.host_real_bytes == 4 ? initial_cond_output_t<float>(itime, o, prefix, src) : initial_cond_output_t<double>(itime, o, prefix, src);
   }
 
@@ -4236,12 +4168,10 @@ struct Engine : EngineBase {
       if (path) text += pt::pt_record<H>(j + 1, (int)(itime - (pt_start[j] + pt_end[j]) / 2), S.val);
     }
     if (path) {
-      FILE *fh = fopen(path, "ab");
-      if (!fh) return fail(FPX_ERR_ARG, std::string("plumetraj: cannot open ") + path);
-      FileCloser closer(fh);
-      bool ok = fwrite(text.data(), 1, text.size(), fh) == text.size();
-      ok = (closer.close() == 0) && ok;
-      if (!ok) return fail(FPX_ERR_ARG, std::string("plumetraj: write error on ") + path);
+      RecFile file(path, "ab");
+      if (!file.is_open()) return fail(FPX_ERR_ARG, std::string("plumetraj: cannot open ") + path);
+      file.write(text.data(), text.size());               // formatted text: no record markers
+      if (!file.close()) return fail(FPX_ERR_ARG, std::string("plumetraj: write error on ") + path);
     }
     if (nrecords) *nrecords = (int32_t)pt_rec_j.size();
     return 0;
@@ -4538,18 +4468,15 @@ struct Engine : EngineBase {
     int rc = domainfill_acc(acc[0].data(), acc[1].data(), nullptr, nullptr);
     if (rc) return rc;
     const size_t total = (dfl_nc_we.size() + dfl_nc_sn.size()) * 4 + 2 * (dfl_acc_bytes(0) + dfl_acc_bytes(1));
-    if (total > 0x7fffffffull) return fail(FPX_ERR_UNSUPPORTED, "boundcond_output: the record exceeds 2 GiB (the reference's compiler would split it into subrecords)");
-    FILE *fh = fopen(path, "wb");
-    if (!fh) return fail(FPX_ERR_ARG, std::string("boundcond_output: cannot open ") + path);
-    FileCloser closer(fh);
-    const uint32_t marker = (uint32_t)total;               // :568-572, one sequential unformatted record
-    bool ok = fwrite(&marker, 4, 1, fh) == 1;
-    ok = ok && fwrite(dfl_nc_we.data(), 4, dfl_nc_we.size(), fh) == dfl_nc_we.size() && fwrite(dfl_nc_sn.data(), 4, dfl_nc_sn.size(), fh) == dfl_nc_sn.size();
-    ok = ok && fwrite(dfl_zc_we.data(), 1, dfl_zc_we.size(), fh) == dfl_zc_we.size() && fwrite(dfl_zc_sn.data(), 1, dfl_zc_sn.size(), fh) == dfl_zc_sn.size();
-    ok = ok && fwrite(acc[0].data(), 1, acc[0].size(), fh) == acc[0].size() && fwrite(acc[1].data(), 1, acc[1].size(), fh) == acc[1].size();
-    ok = ok && fwrite(&marker, 4, 1, fh) == 1;
-    ok = (closer.close() == 0) && ok;
-    if (!ok) return fail(FPX_ERR_ARG, std::string("boundcond_output: write error on ") + path);
+    if (total > RecFile::kMaxRecord) return fail(FPX_ERR_UNSUPPORTED, "boundcond_output: the record exceeds 2 GiB (the reference's compiler would split it into subrecords)");
+    RecFile file(path);
+    if (!file.is_open()) return fail(FPX_ERR_ARG, std::string("boundcond_output: cannot open ") + path);
+    // :568-572, one sequential unformatted record
+    file.put(dfl_nc_we.data(), dfl_nc_we.size() * 4); file.put(dfl_nc_sn.data(), dfl_nc_sn.size() * 4);
+    file.put(dfl_zc_we.data(), dfl_zc_we.size()); file.put(dfl_zc_sn.data(), dfl_zc_sn.size());
+    file.put(acc[0].data(), acc[0].size()); file.put(acc[1].data(), acc[1].size());
+    file.end();
+    if (!file.close()) return fail(FPX_ERR_ARG, std::string("boundcond_output: write error on ") + path);
     return 0;
   }
   double domainfill_ms() override { return dfl_last_ms; }
@@ -4670,7 +4597,7 @@ struct Engine : EngineBase {
     if (!height_set || !window_set) return fail(FPX_ERR_STATE, "wetdepo: height / wind-time window not set");
     if (numpart == 0) return 0;
     const int nb = (int)((numpart + kBlock - 1) / kBlock);
-    red_valid[RG_WET] = red_valid[RG_WETN] = false;
+    sum_wet.invalidate(); sum_wetn.invalidate();           // k_wetdepo adds to wetgridunc / wetgriduncn
     // (wave_kernel_add needs every lane of the wave: whole blocks of kBlock, no early return in the kernel)
     k_wetdepo<R><<<nb, kBlock, 0, stream>>>(V, Gp, Wp, P, numpart, itime, ltsample, loutnext);
     HIPCHK(hipGetLastError());
@@ -4678,16 +4605,7 @@ struct Engine : EngineBase {
   }
   int get_wetgrid(void *wetgridunc, int allreduce) override {
     if (!Gp.on) return fail(FPX_ERR_STATE, "get_wetgrid: fpx_outgrid_init first");
-    const float *gw = Gp.wetgridunc;
-    if (allreduce && comm_ranks > 1) {
-      int rc = reduce_into(Gp.wetgridunc, &wetgridunc0, n_grid2, "get_wetgrid");   // mpi_mod.f90:2486-2488, into wetgridunc0
-      if (rc) return rc;
-      red_valid[RG_WET] = true;
-      gw = wetgridunc0;
-    }
-    if (wetgridunc) HIPCHK(hipMemcpyAsync(wetgridunc, gw, n_grid2 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    return 0;
+    return fetch({{&sum_wet, Gp.wetgridunc, wetgridunc, false, false}}, allreduce, "get_wetgrid");   // mpi_mod.f90:2486-2488, into wetgridunc0
   }
 
   void *stream_ptr() override { return (void *)stream; }

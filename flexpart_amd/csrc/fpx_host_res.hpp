@@ -1,11 +1,13 @@
 // fpx_host_res.hpp -- the owners of the engine's host-side HIP resources (no device code).
 //
-// A buffer or an event that outlives a statement has an owner: one of the move-only types below, as a member of the
+// A buffer or an event that outlives a statement has an owner: one of the types below (none can be copied), as a member of the
 // engine (what lives between calls) or as a local variable (what lives for one call; every return path frees it).
 //   Scratch            a grow-only device buffer, or its pinned-host twin
 //   Events<N>          N events created together
 //   IntervalTimer<N>   the per-step event sets of one timer and the times they add up to
-//   FileCloser         a FILE * that is closed on every return path
+//   RankSum            the sums over the ranks of one output accumulator: receive buffer, extent, validity
+//   FileCloser         a FILE * that is closed on every return path (the files the engine reads, and the checkpoint;
+//                      every other file it writes has its owner in fpx_recfile.hpp)
 // The buffers that live as long as the engine itself stay in its `owned` list (Engine::dalloc).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -128,6 +130,32 @@ class IntervalTimer {
     if (reset) { std::fill(acc_.begin(), acc_.end(), 0.); launches_ = 0; }
     return hipSuccess;
   }
+};
+
+// What goes with one output accumulator (gridunc, drygridunc, ..., flux, init_cond) once several ranks share a run: the
+// receive buffer of its reduction (the reference's gridunc0, drygridunc0, ...: mpi_mod.f90:2451-2492,2543-2569), allocated
+// with the first reduction, the accumulator's extent, and whether the buffer holds the sums of the partial sums as they
+// are now.  The partial sums themselves stay where the kernels read them.  Who reduces, who reads and what makes the
+// sums stale is the engine's business (Engine::reduce, source, and the invalidate() calls next to the kernels' launches).
+class RankSum {
+  void *recv_ = nullptr;
+  size_t n_ = 0, elem_ = 0;
+  bool valid_ = false;
+
+ public:
+  RankSum() = default;
+  RankSum(const RankSum &) = delete;
+  RankSum &operator=(const RankSum &) = delete;
+  ~RankSum() { if (recv_) (void)hipFree(recv_); }
+  void shape(size_t count, size_t elem_bytes) { n_ = count; elem_ = elem_bytes; }   // once, when the accumulator is allocated
+  size_t count() const { return n_; }
+  size_t elem() const { return elem_; }       // 4 or 8: the element is a float or a double
+  size_t bytes() const { return n_ * elem_; }
+  hipError_t reserve() { return recv_ ? hipSuccess : hipMalloc(&recv_, std::max<size_t>(bytes(), 1)); }
+  void *recv() const { return recv_; }
+  bool valid() const { return valid_; }
+  void filled() { valid_ = true; }
+  void invalidate() { valid_ = false; }
 };
 
 struct FileCloser {

@@ -134,3 +134,8 @@ def test_kernels_that_read_their_arguments_in_place_have_them_first():
     # fpx_engine.hip is host code only: every kernel and device function lives in the header of its feature
     engine = open(os.path.join(csrc, "fpx_engine.hip")).read()
     assert "__global__" not in engine and "__device__" not in engine
+    # ... and so are the headers of the host-side owners; the record writer does not even see HIP
+    for name in ("fpx_host_res.hpp", "fpx_recfile.hpp"):
+        text = open(os.path.join(csrc, name)).read()
+        assert "__global__" not in text and "__device__" not in text, name
+    assert "hip" not in open(os.path.join(csrc, "fpx_recfile.hpp")).read().split("#pragma once")[1]

@@ -3,7 +3,8 @@
 RCCL refuses two ranks on the same device, so on a one-GPU box the reduction runs through the engine's second
 transport, the host-supplied all-reduce of fpx_comm_init_host (what an MPI host passes; here gloo).  Everything else
 is the code the 8-GPU run executes: particle shards with global particle numbers as RNG keys, per-rank partial sums in
-device memory, receive buffers for the reduced grids, two output times with cumulative deposition grids."""
+device memory, receive buffers for the reduced grids, two output times with cumulative deposition grids; the output files
+written from the receive buffers (reduced = 1) and the rule that says when those buffers are stale."""
 import os
 import subprocess
 import sys
@@ -212,3 +213,274 @@ def test_bench_two_ranks_is_the_single_rank_job(built, tmp_path):
     a, b = one["config"]["gridunc_sum_all_ranks"], two["config"]["gridunc_sum_all_ranks"]
     assert a > 0 and abs(a - b) <= 1e-6 * a, (a, b)
     assert abs(two["config"]["particle_steps_timed"] - one["config"]["particle_steps_timed"]) <= 2
+
+
+# ---- the reduced = 1 writers and the rule that says when a reduction is stale ---------------------------------------
+# One script per leg, started as rank 0 and rank 1 of a two-rank run and once more as a run of its own (world = 1).  Each
+# process pickles what it wrote and what it was refused; the test compares.
+
+REDUCED_COMMON = textwrap.dedent("""
+    import pickle
+    sys.path.insert(1, %(tests)r)
+    from flexpart_amd._lib import FpxError
+    rank, world = int(sys.argv[1]), int(sys.argv[2])
+    if world > 1:
+        import torch.distributed as dist
+        dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%(port)d", rank=rank, world_size=world)
+    files, refused, counter = {}, {}, [0]
+
+    def fresh():                                  # every call of a writer gets a prefix of its own
+        counter[0] += 1
+        d = %(out)r + f"_w{world}r{rank}_{counter[0]:03d}"
+        os.mkdir(d)
+        return d + os.sep
+
+    def refuses(what, call):
+        # FPX_ERR_STATE with the text that names the getter to call first -- and nothing else counts
+        try:
+            call()
+            refused[what] = "the call succeeded"
+        except FpxError as e:
+            refused[what] = True if e.code == -3 and "reduced = 1 needs" in str(e) else str(e)
+
+    def finish(**arrays):
+        with open(%(out)r + f"_w{world}r{rank}.pkl", "wb") as f:
+            pickle.dump(dict(files=files, refused=refused, **arrays), f)
+        eng.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+""")
+
+REDUCED_FORWARD = COMMON + REDUCED_COMMON + textwrap.dedent("""
+    import calcfluxes_ref as cr
+    from oracle import oracle as orc
+    sc = scenario()
+    sc.update(iflux=1, device_flux=1)
+    if world > 1:
+        sc = sharding.shard_scenario(sc, world, rank)
+    eng = Engine(sc, compute_real_bytes=8, host_real_bytes=4, rng_mode=RNG_PHILOX, seed=4711)   # concoutput: 4-byte hosts only
+    if world > 1:
+        eng.comm_init_host(dist, world, rank)
+    na, nc, mp, nsp, nzg, nyg, nxg = eng.gshape
+    nyn, nxn = eng.gshape_nest[5:7]
+    assert (na, nc, mp) == (1, 1, 1)
+    OUTNUM = 2.0
+    case = {False: syn.concoutput_case(nxg=nxg, nyg=nyg, nzg=nzg, nspec=nsp), True: syn.concoutput_case(nxg=nxn, nyg=nyn, nzg=nzg, nspec=nsp)}
+    areas = (1.0e8 * (1.0 + (np.arange(nyg * nxg).reshape(nyg, nxg) %% 7) / 8.0),
+             1.0e6 * (1.0 + (np.arange(nzg * nyg * nxg).reshape(nzg, nyg, nxg) %% 5) / 8.0),
+             1.0e6 * (1.0 + (np.arange(nzg * nyg * nxg).reshape(nzg, nyg, nxg) %% 3) / 4.0))
+
+    def conc(nest, reduced, wet=True, dry=True):
+        prefix = fresh()
+        eng.concoutput(3600, prefix, case[nest]["area"], case[nest]["volume"], outnum=OUTNUM, wetdep=wet, drydep=dry, nest=nest, reduced=reduced)
+        return [open(prefix + "%%03d" %% (k + 1), "rb").read() for k in range(nsp)]
+
+    def conc_oracle(nest, g, d, w):              # as tests/test_concoutput.py feeds the oracle
+        c = case[nest]
+        geom = c["outgeom"].copy(); geom[4] = OUTNUM
+        co = dict(outgrid=np.array([nxn if nest else nxg, nyn if nest else nyg, nzg, nsp, 1, 1, 3600], np.int32), outgeom=geom,
+                  outheight=c["outheight"], area=c["area"], volume=c["volume"], gridunc=g[0, 0, 0], wetgridunc=w[0, 0, 0], drygridunc=d[0, 0, 0])
+        got = orc.co_oracle(co)
+        return [got["_%%03d" %% (k + 1)] for k in range(nsp)]
+
+    def flux(reduced):
+        return open(eng.fluxoutput(eng.itime, fresh(), *areas, outstep=3600.0, bdate=syn.GV_BDATE, reduced=reduced), "rb").read()
+
+    def flux_ref(fl):                            # as tests/test_calcfluxes.py feeds the restatement's writer
+        return cr.fluxoutput(fl, "r4", eng.itime, *areas, 3600.0)
+
+    def sync_step():
+        if eng.itime != 0:
+            eng.wetdepo()
+        eng.step()
+        eng.conccalc(eng.itime, 1.0)
+
+    def reduce_all():
+        g, d = eng.grids(allreduce=True)
+        w = eng.wetgrid(allreduce=True)
+        gn, dn, wn = eng.grids_nest(allreduce=True)
+        return dict(g=g, d=d, w=w, gn=gn, dn=dn, wn=wn, fl=eng.get_flux(allreduce=True))
+
+    ck = %(out)r + f"_w{world}r{rank}.ckpt"
+    if world == 1:
+        # a single rank: reduced = 1 needs no call before it and writes the partial sums, which are the sums
+        for _ in range(2):
+            sync_step()
+        eng.checkpoint_write(ck)
+        for nest in (False, True):
+            files[f"conc{nest:d}_red"] = conc(nest, True)
+            files[f"conc{nest:d}_own"] = conc(nest, False)
+        files["flux_own"] = flux(False)          # zeroes flux ...
+        eng.checkpoint_read(ck)                  # ... and this brings it back
+        files["flux_red"] = flux(True)
+        finish()
+        sys.exit(0)
+
+    for nest in (False, True):
+        refuses(f"before the first all-reduce: concoutput nest={nest:d}", lambda: conc(nest, True))
+    refuses("before the first all-reduce: fluxoutput", lambda: flux(True))
+    for _ in range(2):
+        sync_step()
+    eng.checkpoint_write(ck)
+    red = reduce_all()
+    for nest in (False, True):
+        files[f"conc{nest:d}_own"] = conc(nest, False)
+        files[f"conc{nest:d}_red"] = conc(nest, True)
+        files[f"conc{nest:d}_ref"] = conc_oracle(nest, *((red["gn"], red["dn"], red["wn"]) if nest else (red["g"], red["d"], red["w"])))
+    files["flux_ref"] = flux_ref(red["fl"])
+    files["flux_red"] = flux(True)
+    refuses("fluxoutput has zeroed flux: fluxoutput", lambda: flux(True))
+
+    # conccalc moves gridunc / griduncn on; the sums of the deposition grids stay good
+    eng.conccalc(eng.itime, 1.0)
+    for nest in (False, True):
+        refuses(f"conccalc: concoutput nest={nest:d}", lambda: conc(nest, True, wet=False, dry=False))
+    reduce_all()
+    for nest in (False, True):
+        conc(nest, True)                         # everything is valid again
+    # a step moves drygridunc / drygriduncn and flux on, and nothing else
+    eng.step()
+    for nest in (False, True):
+        refuses(f"step: concoutput drydep nest={nest:d}", lambda: conc(nest, True, wet=False, dry=True))
+        conc(nest, True, wet=True, dry=False)
+    refuses("step: fluxoutput", lambda: flux(True))
+    # wetdepo moves wetgridunc / wetgriduncn on, and nothing else
+    eng.wetdepo()
+    for nest in (False, True):
+        refuses(f"wetdepo: concoutput wetdep nest={nest:d}", lambda: conc(nest, True, wet=True, dry=False))
+        conc(nest, True, wet=False, dry=False)
+    # a restored checkpoint replaces every partial sum
+    reduce_all()
+    for nest in (False, True):
+        conc(nest, True)
+    eng.checkpoint_read(ck)
+    for nest in (False, True):
+        refuses(f"checkpoint_read: concoutput nest={nest:d}", lambda: conc(nest, True, wet=False, dry=False))
+        refuses(f"checkpoint_read: concoutput drydep nest={nest:d}", lambda: conc(nest, True, wet=False, dry=True))
+        refuses(f"checkpoint_read: concoutput wetdep nest={nest:d}", lambda: conc(nest, True, wet=True, dry=False))
+    refuses("checkpoint_read: fluxoutput", lambda: flux(True))
+    # flux is what it was when the reduced file was written: the partial sums of this rank, through the same writer
+    own = eng.get_flux()
+    files["flux_own_ref"] = flux_ref(own)
+    files["flux_own"] = flux(False)
+    finish(own=own, **red)
+""")
+
+REDUCED_BACKWARD = textwrap.dedent("""
+    import os, sys
+    sys.path.insert(0, %(root)r)
+    import numpy as np
+    from flexpart_amd import sharding
+""") + REDUCED_COMMON + textwrap.dedent("""
+    import initcond_ref as ir
+    import test_initcond as tic
+    sc = tic.ic_scenario(1)
+    if world > 1:
+        sc = sharding.shard_scenario(sc, world, rank)
+    eng = tic.make_engine(sc, 8, 8)
+    if world > 1:
+        eng.comm_init_host(dist, world, rank)
+    rho_rel = np.array([1.125, 0.9375, 1.0625])
+
+    def write(reduced):
+        return [open(n, "rb").read() for n in eng.initial_cond_output(eng.itime, fresh(), ind_rel=1, rho_rel=rho_rel, reduced=reduced)]
+
+    if world == 1:
+        for _ in range(tic.NSTEPS):
+            eng.step()
+        eng.initcond_finish()
+        files["red"] = write(True)
+        files["own"] = write(False)
+        finish()
+        sys.exit(0)
+
+    ck = %(out)r + f"_w{world}r{rank}.ckpt"
+    refuses("before the first all-reduce", lambda: write(True))
+    for _ in range(tic.NSTEPS):
+        eng.step()
+    eng.initcond_finish()
+    eng.checkpoint_write(ck)
+    red = eng.get_initcond(allreduce=True)
+    own = eng.get_initcond()
+    files["own"] = write(False)
+    files["red"] = write(True)
+    files["ref"] = ir.initial_cond_output(red, "r8", eng.itime, sc["xmass"], 1, rho_rel)
+    eng.step()
+    refuses("step", lambda: write(True))
+    eng.get_initcond(allreduce=True)
+    write(True)
+    eng.initcond_finish()
+    refuses("initcond_finish", lambda: write(True))
+    eng.get_initcond(allreduce=True)
+    write(True)
+    eng.checkpoint_read(ck)
+    refuses("checkpoint_read", lambda: write(True))
+    assert np.array_equal(eng.get_initcond(), own)
+    finish(own=own, red=red)
+""")
+
+
+def run_reduced(tmp_path, script, port):
+    """rank 0 and rank 1 of a two-rank run and a single-rank run of `script`, side by side: what each pickled."""
+    import pickle
+    out = str(tmp_path / "rw")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    ws = tmp_path / "reduced_worker.py"
+    ws.write_text(script % dict(root=ROOT, tests=os.path.join(ROOT, "tests"), port=port, out=out))
+    procs = [subprocess.Popen([sys.executable, str(ws), str(r), str(w)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
+             for r, w in ((0, 2), (1, 2), (0, 1))]
+    outs = [p.communicate(timeout=600)[0] for p in procs]
+    assert all(p.returncode == 0 for p in procs), "\n".join(outs)
+    return [pickle.load(open(out + f"_w{w}r{r}.pkl", "rb")) for r, w in ((0, 2), (1, 2), (0, 1))]
+
+
+def test_reduced_forward_files_and_staleness(built, tmp_path):
+    """fpx_concoutput (mother and nested output grid, with both deposition grids) and fpx_fluxoutput with reduced = 1 on two
+    ranks (concoutput_mpi.f90:279,298: the root writes from gridunc0 / drygridunc0 / wetgridunc0): both ranks write the same
+    bytes; they are the bytes the reference writers make of the reduced arrays the rank fetched (no tolerance: the same
+    numbers go into both); reduced = 0 on the same rank writes other bytes; the grids hold data.  Then the rule that says
+    when a receive buffer is stale, as the engine has it: every case below is refused with FPX_ERR_STATE, and the calls the
+    same event must not touch still succeed (the worker would fail).  A single rank needs no reduction and writes the same
+    bytes either way."""
+    a, b, s = run_reduced(tmp_path, REDUCED_FORWARD, 39500 + (os.getpid() % 2000))
+    for r in (a, b):
+        f = r["files"]
+        for key in ("conc0", "conc1", "flux"):
+            assert f[key + "_red"] == f[key + "_ref"], key
+            assert f[key + "_red"] != f[key + "_own"], key
+        assert f["flux_own"] == f["flux_own_ref"]
+    for key in ("conc0_red", "conc1_red", "flux_red"):
+        assert a["files"][key] == b["files"][key], key
+    assert (a["g"] > 0).sum() > 100 and (a["gn"] > 0).sum() > 100
+    for k in ("d", "w", "dn", "wn", "fl"):
+        assert np.count_nonzero(a[k]) > 0, k
+    for k in ("g", "d", "w", "gn", "dn", "wn", "fl"):
+        assert np.array_equal(a[k], b[k]), k
+    assert np.count_nonzero(a["own"]) > 0 and np.count_nonzero(b["own"]) > 0 and np.array_equal(a["own"] + b["own"], a["fl"])
+    want = {f"{why}: concoutput nest={n}" for why in ("before the first all-reduce", "conccalc") for n in (0, 1)}
+    want |= {f"{why}: fluxoutput" for why in ("before the first all-reduce", "fluxoutput has zeroed flux", "step", "checkpoint_read")}
+    want |= {f"step: concoutput drydep nest={n}" for n in (0, 1)} | {f"wetdepo: concoutput wetdep nest={n}" for n in (0, 1)}
+    want |= {f"checkpoint_read: concoutput{dep} nest={n}" for dep in ("", " drydep", " wetdep") for n in (0, 1)}
+    for r in (a, b):
+        assert set(r["refused"]) == want
+        assert all(v is True for v in r["refused"].values()), r["refused"]
+    f = s["files"]
+    for key in ("conc0", "conc1", "flux"):
+        assert f[key + "_red"] == f[key + "_own"] and all(len(x) > 200 for x in ([f[key + "_red"]] if key == "flux" else f[key + "_red"])), key
+
+
+def test_reduced_backward_files_and_staleness(built, tmp_path):
+    """fpx_initial_cond_output with reduced = 1 on two ranks of the backward run of tests/test_initcond.py, after
+    fpx_get_initcond(allreduce = 1): the same three properties against the restatement's writer, and the staleness rule of
+    init_cond: a step, fpx_initcond_finish and a restored checkpoint each make the reduction stale."""
+    a, b, s = run_reduced(tmp_path, REDUCED_BACKWARD, 41500 + (os.getpid() % 2000))
+    for r in (a, b):
+        f = r["files"]
+        assert f["red"] == f["ref"] and f["red"] != f["own"] and len(f["red"]) == 2
+        assert set(r["refused"]) == {"before the first all-reduce", "step", "initcond_finish", "checkpoint_read"}
+        assert all(v is True for v in r["refused"].values()), r["refused"]
+    assert a["files"]["red"] == b["files"]["red"]
+    assert np.array_equal(a["red"], b["red"]) and np.count_nonzero(a["red"]) > 50
+    assert np.count_nonzero(a["own"]) > 0 and np.count_nonzero(b["own"]) > 0
+    assert s["files"]["red"] == s["files"]["own"] and all(len(x) > 200 for x in s["files"]["red"])
