@@ -258,10 +258,93 @@ static __device__ const double kExpTab[32] = {
   1.681792830507429, 1.718619298122478, 1.7562521603732995, 1.7947090750031072,
   1.8340080864093424, 1.8741676341103, 1.9152065613971474, 1.9571441241754002
 };
+// 2**(j/256), j = 0 .. 255, correctly rounded (m_exp_tab<256, 4>; every eighth entry is kExpTab's)
+static __device__ const double kExpTab256[256] = {
+  1.0, 1.0027112750502025, 1.0054299011128027, 1.0081558981184175,
+  1.0108892860517005, 1.0136300849514894, 1.016378314910953, 1.019133996077738,
+  1.0218971486541166, 1.0246677928971357, 1.0274459491187637, 1.030231637686041,
+  1.0330248790212284, 1.0358256936019572, 1.0386341019613787, 1.041450124688316,
+  1.0442737824274138, 1.0471050958792898, 1.0499440858006872, 1.0527907730046264,
+  1.0556451783605572, 1.0585073227945128, 1.061377227289262, 1.0642549128844645,
+  1.0671404006768237, 1.0700337118202419, 1.0729348675259756, 1.075843889062791,
+  1.0787607977571199, 1.0816856149932152, 1.0846183622133092, 1.0875590609177697,
+  1.0905077326652577, 1.0934643990728858, 1.0964290818163769, 1.099401802630222,
+  1.102382583307841, 1.1053714457017412, 1.1083684117236787, 1.1113735033448175,
+  1.1143867425958924, 1.1174081515673693, 1.1204377524096067, 1.12347556733302,
+  1.1265216186082418, 1.129575928566288, 1.1326385195987192, 1.1357094141578055,
+  1.1387886347566916, 1.1418762039695616, 1.1449721444318042, 1.148076478840179,
+  1.1511892299529827, 1.154310420590216, 1.1574400736337511, 1.1605782120274988,
+  1.1637248587775775, 1.1668800369524817, 1.1700437696832502, 1.1732160801636373,
+  1.1763969916502812, 1.1795865274628758, 1.182784710984341, 1.1859915656609938,
+  1.189207115002721, 1.1924313825831512, 1.1956643920398273, 1.1989061670743806,
+  1.202156731452703, 1.2054161090051239, 1.2086843236265816, 1.2119613992768012,
+  1.215247359980469, 1.2185422298274085, 1.2218460329727576, 1.2251587936371455,
+  1.22848053610687, 1.2318112847340759, 1.2351510639369334, 1.2384998981998165,
+  1.241857812073484, 1.245224830175258, 1.2486009771892048, 1.2519862778663162,
+  1.255380757024691, 1.2587844395497165, 1.2621973503942507, 1.2656195145788063,
+  1.2690509571917332, 1.2724917033894028, 1.275941778396392, 1.2794012075056693,
+  1.2828700160787783, 1.2863482295460256, 1.2898358734066657, 1.2933329732290895,
+  1.2968395546510096, 1.3003556433796506, 1.3038812651919358, 1.3074164459346773,
+  1.3109612115247644, 1.3145155879493546, 1.318079601266064, 1.3216532776031575,
+  1.3252366431597413, 1.3288297242059544, 1.3324325470831615, 1.3360451382041458,
+  1.339667524053303, 1.3432997311868353, 1.3469417862329458, 1.3505937158920345,
+  1.3542555469368927, 1.3579273062129011, 1.3616090206382248, 1.365300717204012,
+  1.3690024229745905, 1.3727141650876684, 1.3764359707545302, 1.380167867260238,
+  1.383909881963832, 1.387662042298529, 1.3914243757719262, 1.3951969099662003,
+  1.3989796725383112, 1.4027726912202048, 1.4065759938190154, 1.4103896082172707,
+  1.4142135623730951, 1.4180478843204152, 1.4218926021691656, 1.4257477441054942,
+  1.42961333839197, 1.433489413367789, 1.4373759974489824, 1.4412731191286257,
+  1.4451808069770467, 1.449099089642035, 1.4530279958490526, 1.4569675544014438,
+  1.460917794180647, 1.4648787441464057, 1.4688504333369818, 1.4728328908693675,
+  1.4768261459394993, 1.4808302278224719, 1.4848451658727524, 1.488870989524397,
+  1.4929077282912648, 1.4969554117672355, 1.5010140696264256, 1.5050837316234065,
+  1.5091644275934228, 1.5132561874526098, 1.5173590411982147, 1.5214730189088146,
+  1.5255981507445384, 1.529734466947287, 1.533881997840956, 1.5380407738316568,
+  1.5422108254079407, 1.5463921831410214, 1.550584877685, 1.5547889397770887,
+  1.559004400237837, 1.5632312899713576, 1.567469639965553, 1.5717194812923414,
+  1.5759808451078865, 1.5802537626528246, 1.5845382652524937, 1.588834384317164,
+  1.593142151342267, 1.597461597908627, 1.6017927556826934, 1.606135656416771,
+  1.6104903319492543, 1.6148568142048607, 1.6192351351948637, 1.6236253270173289,
+  1.6280274218573478, 1.632441451987275, 1.6368674497669644, 1.6413054476440063,
+  1.645755478153965, 1.6502175739206177, 1.6546917676561943, 1.6591780921616162,
+  1.6636765803267364, 1.6681872651305825, 1.6727101796415966, 1.6772453570178785,
+  1.681792830507429, 1.6863526334483934, 1.6909247992693053, 1.6955093614893326,
+  1.7001063537185235, 1.7047158096580513, 1.709337763100463, 1.713972247929926,
+  1.718619298122478, 1.723278947746274, 1.7279512309618377, 1.732636182022311,
+  1.7373338352737062, 1.7420442251551564, 1.746767386199169, 1.7515033530318782,
+  1.7562521603732995, 1.761013843037584, 1.7657884359332727, 1.7705759740635547,
+  1.7753764925265212, 1.7801900265154245, 1.785016611318935, 1.789856282321401,
+  1.7947090750031072, 1.7995750249405351, 1.804454167806624, 1.809346539371032,
+  1.8142521755003989, 1.8191711121586085, 1.8241033854070534, 1.8290490314048973,
+  1.8340080864093424, 1.8389805867758937, 1.843966568958626, 1.8489660695104508,
+  1.8539791250833855, 1.8590057724288205, 1.864046048397789, 1.8690999899412386,
+  1.8741676341103, 1.8792490180565602, 1.8843441790323345, 1.8894531543909392,
+  1.8945759815869656, 1.8997126981765553, 1.9048633418176741, 1.9100279502703899,
+  1.9152065613971474, 1.9203992131630474, 1.925605943636125, 1.930826790987627,
+  1.9360617934922943, 1.9413109895286405, 1.9465744175792332, 1.9518521162309783,
+  1.9571441241754002, 1.9624504802089273, 1.9677712232331759, 1.9731063922552343,
+  1.978456026387951, 1.9838201648502194, 1.9891988469672663, 1.9945921121709402
+};
+// Do the instances that carry the error-function table (stash_has_erf_tab: the fp64 gas kernels) also take their exponentials
+// from the 256-entry table?  0 puts them back on the 32-entry form: the A/B partner for the finer error-function table alone.
+#ifndef FPX_EXP_TAB_FINE
+#define FPX_EXP_TAB_FINE 1
+#endif
 // The two tables as the Langevin kernel reads them: a copy per block in LDS, [0..63] = kLogTab, [64..95] = kExpTab.  768 bytes:
 // the kernel's 25-slot stash + height column + these must stay under 53248 B per block for three blocks per CU (the hardware
 // allocates LDS in coarser units than hipOccupancyMaxActiveBlocksPerMultiprocessor assumes: 54352 B was measured to hold two).
+// The fp64 gas kernels (19 stash slots in one launch, 20 in the time-sliced twin; both get the same tables, so that their
+// arithmetic stays the same) spend what their shorter stash leaves on finer tables, which shorten the polynomials of every
+// sub-step: [64..319] = kExpTab256 and the 104-row table of the error-function pair (fpx_erfcx_tab.hpp), 512 + 2048 + 8320 =
+// 10880 B of static LDS.  With 8 nz for the height column that is 50896 B at nz = 138 for the one-launch instance and 52944 B
+// for its twin: three blocks per CU up to nz = 432 and nz = 176; above that the kernels run two to a CU.
 constexpr int kLdsTabDoubles = 96, kLdsExpTabAt = 64;
+constexpr int lds_tab_doubles(bool fine) { return fine ? kLdsExpTabAt + 256 : kLdsTabDoubles; }
+constexpr int kLdsBlockLimit = 53248;   // bytes of LDS per block at three blocks per CU
+constexpr int kLdsGasStaticBytes = 8 * (lds_tab_doubles(true) + kErfcxIntervals * kErfcxRow);
+static_assert(kLdsGasStaticBytes == 10880, "static LDS of an fp64 gas instance: log table, 256-entry exp table, erf table");
+static_assert(kLdsGasStaticBytes + 20 * 2048 + 8 * 138 <= kLdsBlockLimit, "the time-sliced fp64 gas kernel (20 slots) at nz = 138: three blocks per CU");
+static_assert((kLdsBlockLimit - kLdsGasStaticBytes - 19 * 2048) / 8 == 432 && (kLdsBlockLimit - kLdsGasStaticBytes - 20 * 2048) / 8 == 176, "the nz limits stated above");
 typedef __attribute__((address_space(3))) const double *lds_tab_ptr;
 template <typename TP>
 FPX_DEV double m_log_abs(double x, TP tab /* kLogTab layout: [32][2] */) {
@@ -278,40 +361,68 @@ FPX_DEV double m_log_abs(double x, TP tab /* kLogTab layout: [32][2] */) {
   return fma((double)e, 6.93147180559945309417e-01, lc) + f * p;
 }
 FPX_DEV double m_log_abs(double x) { return m_log_abs(x, &kLogTab[0][0]); }
-// exp(x) with a 32-entry table of 2**(j/32) (Tang's scheme): k = rint(x*32/ln2), r = x - k*ln2/32 (two-part constant, |r| <= 0.011),
-// exp(x) = 2**(k>>5) * T[k&31] * (1 + r + r^2/2 + .. + r^6/720) (truncation r^7/5040 < 4e-18).  16 instructions against the 21 of
-// m_expp; about 1 ulp.  Saturates like m_expp (v_ldexp_f64), NaN propagates.
-template <typename TP>
-FPX_DEV double m_exp_tab(double x, TP tab /* kExpTab layout */) {
-  const double k = rint(x * 46.16624130844683);
-  double r = fma(k, -0.02166084938653512, x);
-  r = fma(k, -5.9631716539705866e-12, r);
-  const int ki = (int)k;
-  const double t = tab[ki & 31];
+// exp(x) with an N-entry table of 2**(j/N) (Tang's scheme): k = rint(x*N/ln2), r = x - k*ln2/N (two-part constant),
+// exp(x) = 2**(k/N rounded down) * T[k mod N] * (1 + r + r^2/2 + .. + r^DEG/DEG!).  Saturates like m_expp (v_ldexp_f64), NaN propagates.
+//   <32, 6>:  |r| <= 0.011, truncation r^7/5040 < 4e-18.  16 instructions against the 21 of m_expp; about 1 ulp.
+//   <256, 4>: |r| <= ln2/512 = 0.00135, truncation r^5/120 < 3.8e-17 (under 2^-53); two steps fewer, the same error: on 3500
+//             points of -700 .. 0 against mpmath the worst is 1.84 x 2^-53 against 1.71, 99.9 % of the points within 1.68 against
+//             1.67, the median 0.41 against 0.39 (tests/test_fine_tables.py).  The table is 2 KB: for the kernels whose block
+//             has the LDS for it.
+// The constants of the 256-entry form are those of the 32-entry one times or over 8, so k*hi is exact in both (hi has 29 bits).
+template <int N> struct ExpTabConst;
+template <> struct ExpTabConst<32> { static constexpr double per_ln2 = 46.16624130844683, hi = 0.02166084938653512, lo = 5.9631716539705866e-12; static constexpr int bits = 5; };
+template <> struct ExpTabConst<256> { static constexpr double per_ln2 = 369.3299304675746, hi = 0.00270760617331689, lo = 7.453964567463233e-13; static constexpr int bits = 8; };
+template <int DEG> FPX_DEV double m_exp_tab_poly(double r);   // (exp(r) - 1)/r to r^(DEG-1)
+template <> FPX_DEV double m_exp_tab_poly<6>(double r) {
   double p = m_fma_k(r, 1.3888888888888888889e-03, 8.3333333333333333333e-03);
   p = m_fma_k(r, p, 4.1666666666666666667e-02);
   p = m_fma_k(r, p, 1.6666666666666666667e-01);
   p = fma(r, p, 0.5);
-  p = fma(r, p, 1.0);
-  return ldexp(fma(t, r * p, t), ki >> 5);
+  return fma(r, p, 1.0);
+}
+template <> FPX_DEV double m_exp_tab_poly<4>(double r) {
+  double p = m_fma_k(r, 4.1666666666666666667e-02, 1.6666666666666666667e-01);
+  p = fma(r, p, 0.5);
+  return fma(r, p, 1.0);
+}
+template <int N = 32, int DEG = 6, typename TP>
+FPX_DEV double m_exp_tab(double x, TP tab /* kExpTab layout (N = 32), kExpTab256 layout (N = 256) */) {
+  typedef ExpTabConst<N> C;
+  const double k = rint(x * C::per_ln2);
+  double r = fma(k, -C::hi, x);
+  r = fma(k, -C::lo, r);
+  const int ki = (int)k;
+  const double t = tab[ki & (N - 1)];
+  const double p = m_exp_tab_poly<DEG>(r);
+  return ldexp(fma(t, r * p, t), ki >> C::bits);
 }
 // exp(-u/2) = m_exp_tab(-(0.5*u)) without the multiplication in front: the factor -1/2 sits in the constants.  k is the same
 // integer (the scaled product rounds alike), r here is -2 times the r there and every coefficient carries the matching power of
 // -1/2 (one more for the product r*p), all of them powers of two: each intermediate is the other form's times a power of two,
 // so the result has the same bits.
-template <typename TP>
-FPX_DEV double m_exp_tab_nh(double u, TP tab /* kExpTab layout */) {
-  const double k = rint(u * -23.083120654223414);
-  double r = fma(k, 0.04332169877307024, u);
-  r = fma(k, 1.1926343307941173e-11, r);
-  const int ki = (int)k;
-  const double t = tab[ki & 31];
+template <int DEG> FPX_DEV double m_exp_tab_poly_nh(double r);   // m_exp_tab_poly(-r/2) times -1/2
+template <> FPX_DEV double m_exp_tab_poly_nh<6>(double r) {
   double p = m_fma_k(r, 1.3888888888888888889e-03 / 64.0, -8.3333333333333333333e-03 / 32.0);
   p = m_fma_k(r, p, 4.1666666666666666667e-02 / 16.0);
   p = m_fma_k(r, p, -1.6666666666666666667e-01 / 8.0);
   p = fma(r, p, 0.125);
-  p = fma(r, p, -0.5);
-  return ldexp(fma(t, r * p, t), ki >> 5);
+  return fma(r, p, -0.5);
+}
+template <> FPX_DEV double m_exp_tab_poly_nh<4>(double r) {
+  double p = m_fma_k(r, 4.1666666666666666667e-02 / 16.0, -1.6666666666666666667e-01 / 8.0);
+  p = fma(r, p, 0.125);
+  return fma(r, p, -0.5);
+}
+template <int N = 32, int DEG = 6, typename TP>
+FPX_DEV double m_exp_tab_nh(double u, TP tab /* as m_exp_tab */) {
+  typedef ExpTabConst<N> C;
+  const double k = rint(u * (-0.5 * C::per_ln2));
+  double r = fma(k, 2.0 * C::hi, u);
+  r = fma(k, 2.0 * C::lo, r);
+  const int ki = (int)k;
+  const double t = tab[ki & (N - 1)];
+  const double p = m_exp_tab_poly_nh<DEG>(r);
+  return ldexp(fma(t, r * p, t), ki >> C::bits);
 }
 // is x a positive number the f32 seeds below can hold (2^-122 <= x < 2^122)?  One integer subtraction and one unsigned compare on
 // the high word instead of two fp64 compares: zero, negative numbers, subnormals, infinities and NaN all fall outside.
@@ -1232,7 +1343,7 @@ struct Stash {
   // an LDS (address space 3) pointer, so that the accesses are ds_read/ds_write and not flat memory operations
   typedef __attribute__((address_space(3))) volatile R *lds_ptr;
   lds_ptr p;       // &lds[0][threadIdx.x]
-  lds_tab_ptr tab; // the block's copy of kLogTab | kExpTab (fp64 build only)
+  lds_tab_ptr tab; // the block's copy of kLogTab | kExpTab (fp64 build only; kLogTab | kExpTab256 under a StashErfTab)
   FPX_DEV double logabs(double x) const { return m_log_abs(x, tab); }
   FPX_DEV double expt(double x) const { return m_exp_tab(x, tab + kLdsExpTabAt); }
   FPX_DEV float logabs(float x) const { return m_logp(x); }
@@ -1250,6 +1361,11 @@ struct Stash {
 // pair from whichever stash type it is handed.
 struct StashErfTab : Stash<double> {
   lds_erft_ptr erft;   // the block's copy of kErfcxTab
+#if FPX_EXP_TAB_FINE
+  // ... and for the 256-entry table of the exponential, which sits where the 32-entry one does in the other instances' copy
+  FPX_DEV double expt(double x) const { return m_exp_tab<256, 4>(x, tab + kLdsExpTabAt); }
+  FPX_DEV double exp_nh(double u) const { return m_exp_tab_nh<256, 4>(u, tab + kLdsExpTabAt); }   // exp(-u/2), the bits of expt(-(0.5*u))
+#endif
   FPX_DEV void erf_pair(double xa, double Ea, double xb, double Eb, double &ra, double &rb) const { m_erf_tab2(xa, Ea, xb, Eb, erft, ra, rb); }
 };
 template <typename R, bool ERFTAB> struct StashFor { typedef Stash<R> type; };
@@ -1261,6 +1377,10 @@ FPX_DEV typename StashFor<R, ERFTAB>::type make_stash(typename Stash<R>::lds_ptr
 }
 // does a Langevin kernel instance carry the table?  (the kernel sizes its static LDS by the same rule)
 template <typename R> constexpr bool stash_has_erf_tab(bool lean) { return lean && sizeof(R) == 8; }
+// The block's copy of kLogTab | kExpTab256, the layout a StashErfTab reads (all threads of the block; the caller synchronises).
+FPX_DEV void lds_tab_fill_fine(double *lds_tab /* [lds_tab_doubles(true)] */) {
+  for (int k = threadIdx.x; k < lds_tab_doubles(true); k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab256[k - kLdsExpTabAt];
+}
 
 // The step's invariants of a lane of the Langevin kernel live in three stash slots and no register.  The flags travel in the
 // signs: 1/ust > 0 is the neutral regime, 1/ol < 0 the unstable one, 0 the stable one (ust and ol finite), and the sign bit of

@@ -4898,7 +4898,7 @@ int fpx_receptors_init(fpx_handle h, int32_t numreceptor, const void *xreceptor,
 int fpx_get_receptors(fpx_handle h, void *creceptor, int32_t ld, int32_t allreduce, int32_t clear) { FPX_GUARD(h); return h->impl->get_receptors(creceptor, ld, allreduce, clear); }
 
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n) {
-  if (fn < 0 || fn > 31 || !x || !y || n < 0) return FPX_ERR_ARG;
+  if (fn < 0 || fn > 33 || !x || !y || n < 0) return FPX_ERR_ARG;
   if (n == 0) return FPX_OK;
   const int64_t nin = (fn == 12 || fn == 13) ? 2 * n : n;   // fn 12, 13: x[0 .. n) the points, x[n .. 2n) their exp(-x*x)
   fpx::Scratch bx, by;

@@ -48,6 +48,8 @@ __global__ void k_math_probe(int fn, const double *__restrict__ x, double *__res
     case 28: m_sqrt_rsqrt(v, c, ic2); r = c; break;
     case 29: m_sqrt_rsqrt(v, c, ic2); r = ic2; break;
     case 30: r = m_divf(3.0, v); break;
+    case 32: r = m_exp_tab<256, 4>(v, &kExpTab256[0]); break;             // the 256-entry pair of 9 and 14 (the fp64 gas kernels' exponential)
+    case 33: r = m_exp_tab_nh<256, 4>(v, &kExpTab256[0]); break;
     default: m_cuberoot_parts(v, c, ic2); r = ic2; break;
   }
   y[i] = r;
@@ -111,14 +113,15 @@ __global__ void __launch_bounds__(kBlock) k_hanna_probe(int which, const double 
 }
 
 // diagnostics (fpx_cbl_probe): cbl() of a fine sub-step on plain arrays, called as the fp64 gas kernels of k_pbl_loop call it -- a
-// StashErfTab over the block's LDS copies of the exp table and the error-function table.  in[10i .. 10i+9] = wp, z (= zp/h), wt
+// StashErfTab over the block's LDS copies of the exp table (the 256-entry one, as there) and the error-function table.  in[10i .. 10i+9] = wp, z (= zp/h), wt
 // (= wst^3 * transition), 1/h, rhograd/rhoa, sigmaw, 1/sigmaw, dsigmawdz, tlw, ldirect; out[3i .. 3i+2] = ath, bth, flagrein.
 // FORM 0: the body in the reference's dimensional variables, 1: the normalised one; an instance each, whatever FPX_CBL_NORMALISED is.
 template <int FORM>
 __global__ void __launch_bounds__(kBlock) k_cbl_probe(const double *__restrict__ in, double *__restrict__ out, long long n) {
-  __shared__ double lds_tab[kLdsTabDoubles];
+  __shared__ double lds_tab[lds_tab_doubles(FPX_EXP_TAB_FINE != 0)];
   __shared__ __align__(16) double lds_erft[kErfcxIntervals * kErfcxRow];
-  for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
+  if (FPX_EXP_TAB_FINE) lds_tab_fill_fine(lds_tab);
+  else for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
   for (int k = threadIdx.x; k < kErfcxIntervals * kErfcxRow; k += blockDim.x) lds_erft[k] = kErfcxTab[k];
   __syncthreads();
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

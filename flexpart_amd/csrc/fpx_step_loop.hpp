@@ -69,14 +69,17 @@ __global__ void __launch_bounds__(kBlock, sizeof(R) == 4 ? FPX_LOOP_WAVES_F32 : 
   R *hgt = stash_mem + stash_slots<R>(LEAN, SUSP) * kStashStride;   // (the host sizes the block's LDS alike: loop_smem_bytes)
   for (int k = threadIdx.x; k < V.nz; k += blockDim.x) hgt[k] = V.height[k];
   // the block's copy of the lookup tables of the fp64 logarithm and exponential (m_log_abs, m_exp_tab): 768 B
-  __shared__ double lds_tab[sizeof(R) == 8 ? kLdsTabDoubles : 1];
-  if (sizeof(R) == 8)
-    for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
-  // ... and, where the block has the room (the fp64 gas kernels), of the table of the error-function pair (m_erf_tab2): 2.4 KB,
-  // static like the tables above, so the host's rule for the dynamic part (loop_smem_bytes) does not change.  With it a
-  // one-launch fp64 gas kernel has 19 x 2 KB + 8 nz + 768 B + 2496 B per block: 43.3 KB at nz = 138, three blocks per CU
-  // (53248 B each) up to nz = 1380.
+  // ... and, where the block has the room (the fp64 gas kernels), of the 256-entry table of the exponential in place of the
+  // 32-entry one (2.5 KB with the logarithm's) and of the table of the error-function pair (m_erf_tab2, 8.1 KB): static like
+  // the tables above, so the host's rule for the dynamic part (loop_smem_bytes) does not change.  With them a one-launch fp64
+  // gas kernel has 19 x 2 KB + 8 nz + 10880 B per block: 50896 B at nz = 138, three blocks per CU (53248 B each) up to
+  // nz = 432; its time-sliced twin (20 slots) 52944 B, three up to nz = 176 (kLdsGasStaticBytes in fpx_device.hpp).
   constexpr bool ERFTAB = stash_has_erf_tab<R>(LEAN);
+  constexpr bool EXPFINE = ERFTAB && FPX_EXP_TAB_FINE != 0;
+  __shared__ double lds_tab[sizeof(R) == 8 ? lds_tab_doubles(EXPFINE) : 1];
+  if (EXPFINE) lds_tab_fill_fine(lds_tab);
+  else if (sizeof(R) == 8)
+    for (int k = threadIdx.x; k < kLdsTabDoubles; k += blockDim.x) lds_tab[k] = k < kLdsExpTabAt ? kLogTab[k >> 1][k & 1] : kExpTab[k - kLdsExpTabAt];
   __shared__ __align__(16) double lds_erft[ERFTAB ? kErfcxIntervals * kErfcxRow : 2];
   if (ERFTAB)
     for (int k = threadIdx.x; k < kErfcxIntervals * kErfcxRow; k += blockDim.x) lds_erft[k] = kErfcxTab[k];

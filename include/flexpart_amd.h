@@ -953,7 +953,8 @@ void *fpx_stream(fpx_handle h);
  * 15 .. 18 the raw seeds the root helpers refine (v_rcp_f64, v_rsq_f64, the f32 paths of x**(-1/3) and x**(-1/5)); 19 .. 27 the
  * forms with two quadratic Newton steps of m_rcp, m_rsqrt, m_sqrtp, m_sqrt_rsqrt (22 the root, 23 its reciprocal), m_rcbrt,
  * m_pow08, m_cuberoot_parts (26, 27 as 5, 6) and 31 of m_divf(3, x); 28, 29 the two results of m_sqrt_rsqrt and 30 m_divf(3, x)
- * as the kernels call them.  No reference counterpart; used by the parity tests to bound
+ * as the kernels call them; 32 and 33 the 256-entry forms of 9 and 14 (m_exp_tab<256, 4>, m_exp_tab_nh<256, 4>: the exponential
+ * of the fp64 gas kernels).  No reference counterpart; used by the parity tests to bound
  * the helpers against libm.  Returns 0 or a negative fpx_status. */
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n);
 /* Diagnostics: the turbulence profiles of one Langevin pass (hanna.f90) for n points in[5i..5i+4] = h, ol, ust, wst, z: ten values

@@ -9,10 +9,14 @@ polynomial in d = x - centre through the Chebyshev nodes of the interval, in 40-
 the table is [centre, c_n, c_(n-1), .., c_0], padded with zeros to a multiple of 16 bytes so that rows stay aligned for
 128-bit LDS loads (the kernel reads 64 bits at a time at present: it has no registers for wider reads in flight).
 
-The script tries a few (width, degree) pairs, reports for each the worst |1 - E*p(x) - erf(x)| of the double-precision Horner
-evaluation (E = exp(-x*x) rounded to double, as the caller has it) over a grid that contains every interval edge and an ulp
-either side of it, and takes the smallest table (in padded bytes) whose worst error is at or below 5e-16 -- the bound m_erf_e
-documents.
+The width of an interval is set by the LDS budget of the kernel's block, the degree by the bound.  The fp64 gas instances have
+about 10 KB of static LDS to spend at three blocks per CU (see kLdsTabDoubles in fpx_device.hpp): 104 intervals of width 1/16
+fit (8320 B at degree 7), 208 of width 1/32 do not (13312 B at degree 6), and every halving of the width takes one to two
+steps off the Horner chain that each sub-step of the kernel runs twice (width 1/4: degree 10, 2496 B; 1/8: degree 9, 4992 B).
+So the script tries the degrees around the bound at width 1/16, reports for each the worst |1 - E*p(x) - erf(x)| of the
+double-precision Horner evaluation (E = exp(-x*x) rounded to double, as the caller has it) over a grid that contains every
+interval edge and an ulp either side of it, and takes the smallest table (in padded bytes) whose worst error is at or below
+5e-16 -- the bound m_erf_e documents.
 
     python tools/fit_erfcx_table.py            # prints the header to stdout
     python tools/fit_erfcx_table.py --report   # prints the error report of every candidate instead
@@ -28,7 +32,7 @@ mp.mp.dps = 40
 
 XMAX = 6.5
 BOUND = 5e-16
-CANDIDATES = [(4, 9), (4, 10), (8, 8), (8, 9)]   # (intervals per unit of x, degree)
+CANDIDATES = [(16, 6), (16, 7), (16, 8)]   # (intervals per unit of x, degree): the width-1/16 family
 
 
 def g(x):
