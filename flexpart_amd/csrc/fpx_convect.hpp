@@ -1531,6 +1531,35 @@ __global__ void k_conv_redist(const int *__restrict__ pcol, const int4 *__restri
   }
 }
 
+// Diagnostics (fpx_conv_columns), not on the path of fpx_convmix: what the last call left in its scratch for the requested
+// columns col[0 .. nreq) (numbered through all domains), one block per column.  lconv -1: the call did not visit the column.
+// For a convective column fmassfrac(k, kk), 1 <= k, kk <= nl = nconvlev + 1, as [kk][k], un-laid-out from the form the matrix kernel
+// stored -- 0: interleaved (k_conv_column_b, k_conv_matrix), 1: walk-major (k_conv_matrix_walk), 2: transposed walk-major
+// (k_conv_matrix_walk_t) -- and uvzlev(1 .. nconvtop+1); zero beyond nconvtop (nconvtop + 1) and for every other column.
+// colflag / rank: column -> active column (k_conv_mark, its scan); srank: active column -> matrix slot of the one batch.
+template <typename H>
+__global__ void k_conv_columns(const int *__restrict__ col, int ncol, const unsigned int *__restrict__ colflag, const unsigned int *__restrict__ rank,
+                               const unsigned int *__restrict__ srank, const int *__restrict__ lconv, const int *__restrict__ ntop,
+                               H *__restrict__ vbuf, H *__restrict__ mbuf, int nv, int nact, int Bm, int nl, int form,
+                               int *__restrict__ lconv_out, int *__restrict__ ntop_out, H *__restrict__ fm_out, H *__restrict__ uvz_out) {
+  const int i = blockIdx.x;
+  const int c = col[i];
+  int lc = -1, nt = 0, r = 0;
+  if (nact > 0 && c >= 0 && c < ncol && colflag[c]) { r = (int)rank[c]; lc = lconv[r]; nt = lc == 1 ? I_MIN(ntop[r], nl) : 0; }
+  if (threadIdx.x == 0) { lconv_out[i] = lc; ntop_out[i] = nt; }
+  const bool on = lc == 1;                               // a convective column survived CONVECT's early exits: it has a matrix slot
+  const Scr<H> Sx{vbuf, mbuf, nact, r, nv, Bm, on ? (int)srank[r] : 0};
+  H *const fm = fm_out + (size_t)i * nl * nl, *const uz = uvz_out + (size_t)i * (nl + 1);
+  for (int e = threadIdx.x; e < nl * nl; e += blockDim.x) {
+    const int kk = e / nl + 1, k = e % nl + 1;
+    H v = HK(0.);
+    if (on && k <= nt && kk <= nt)
+      v = form == 0 ? MM(fmass, k, kk) : form == 1 ? Sx.fm_walk()[(size_t)k * nv + kk] : Sx.fm_walk()[(size_t)kk * nv + k];
+    fm[e] = v;
+  }
+  for (int kz = 1 + (int)threadIdx.x; kz <= nl + 1; kz += blockDim.x) uz[kz - 1] = on && kz <= nt + 1 ? VV(uvzlev, kz) : HK(0.);
+}
+
 #undef VV
 #undef MM
 #undef HK

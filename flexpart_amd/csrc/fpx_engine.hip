@@ -160,6 +160,7 @@ struct EngineBase {
   virtual int upload_conv_nest_fields(int nest, int slot, const fpx_conv_fields *f) = 0;
   virtual int cbaseflux_nest_io(int nest, void *host, bool set) = 0;
   virtual double conv_ms() = 0;
+  virtual int conv_columns(const int32_t *col, int ncol, int32_t *lconv, int32_t *nconvtop, void *fmassfrac, void *uvzlev) = 0;
   virtual int checkpoint_write(const char *path, int itime, int numparticlecount) = 0;
   virtual int checkpoint_read(const char *path, int32_t *itime, int64_t *numpart_out, int32_t *numparticlecount) = 0;
 };
@@ -2335,12 +2336,19 @@ struct Engine : EngineBase {
   }
   Scratch conv_alive;
   int conv_last_active = 0, conv_last_survivors = 0;
+  // what fpx_conv_columns needs to know of the last call of fpx_convmix, whose scratch stays as that call left it
+  struct ConvLast {
+    bool valid = false;
+    int ncol = 0, nact = 0, Bm = 0, batches = 0;
+    int form = 0;                            // of the stored matrices: 0 interleaved, 1 walk-major (forward), 2 transposed walk-major (backward)
+  } conv_last;
 
   template <typename H>
   int convmix_t(int itime, int64_t *nmoved_out) {
     const long long n = numpart;
     const int nx = cfg.nx, ny = cfg.ny;
     const int nv = conv_nuvz + 2;
+    conv_last = ConvLast{};
     // wind-field domains: the mother grid and the nests (fpx_nests_init); columns numbered through all of them
     conv::Fields<H> F;
     int off[conv::kConvMaxDom + 1];
@@ -2394,7 +2402,7 @@ struct Engine : EngineBase {
     HIPCHK(hipMemcpyAsync(&last_flag, conv_flag + (ncol - 1), 4, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     const int nact = (int)(last_rank + last_flag);
-    if (nact == 0) { if (nmoved_out) *nmoved_out = 0; conv_last_ms = 0; return 0; }
+    if (nact == 0) { if (nmoved_out) *nmoved_out = 0; conv_last_ms = 0; conv_last.valid = true; conv_last.ncol = ncol; return 0; }
     conv::k_conv_list<<<nbc, kBlock, 0, stream>>>(conv_flag, conv_rank, ncol, conv_act);
     HIPCHK(hipGetLastError());
     // scratch: the vectors of every column that holds particles; the matrices only for the columns that get past CONVECT's
@@ -2424,7 +2432,7 @@ struct Engine : EngineBase {
     const bool seq = cfg.rng_mode == FPX_RNG_TABLE_SEQ;
     const bool conv_one_lane = opt.conv_one_lane != 0;     // the one-lane-per-column kernel (kept as the check of the level-parallel ones)
     // fmassfrac stored along the rows (forward runs) / columns (backward) the particles walk (k_conv_matrix_walk, _walk_t);
-    // FPX_CONV_NO_WALK=1: the interleaved form
+    // fpx_set_option "conv_no_walk": the interleaved form
     const bool conv_walk = !conv_one_lane && !opt.conv_no_walk;
     const bool conv_rows_plain = opt.conv_rows_plain != 0;  // k_conv_rows without the LDS staging of its operands
     conv::k_conv_column_a<H><<<conv::serial_grid(nact), 64, 0, stream>>>(F, vbuf, cst, nv, conv_act, nact, alive);
@@ -2442,10 +2450,12 @@ struct Engine : EngineBase {
       conv::k_conv_survivors<<<(nact + kBlock - 1) / kBlock, kBlock, 0, stream>>>(alive, srank, nact, surv);
       HIPCHK(hipGetLastError());
       const int Bm = std::min(nsurv, Bm_cap);
-      if (seq && nsurv > Bm) return fail(FPX_ERR_UNSUPPORTED, "convmix: the serial-stream parity mode needs all convective columns in one scratch batch (raise FPX_CONV_SCRATCH_MB)");
+      if (seq && nsurv > Bm) return fail(FPX_ERR_UNSUPPORTED, "convmix: the serial-stream parity mode needs all convective columns in one scratch batch (raise the option \"conv_scratch_mb\" of fpx_set_option)");
       // parity mode: the random numbers come from the shared serial stream in the reference's visiting order, which needs to
       // know who draws -- a probe pass records that, the host replays the stream, then the particles are moved
+      conv_last.Bm = Bm;
       for (int m0 = 0; m0 < nsurv; m0 += Bm) {
+        conv_last.batches++;
         if (conv_one_lane) {
           conv::k_conv_column_b<H><<<(Bm + 63) / 64, 64, 0, stream>>>(F, vbuf, mbuf, cst, nv, nact, conv_act, surv, m0, Bm, nsurv, conv_lconv, conv_ntop);
         } else {
@@ -2491,7 +2501,53 @@ struct Engine : EngineBase {
     float ms = 0;
     if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) conv_last_ms = ms;
     if (nmoved_out) *nmoved_out = (int64_t)moved;
+    conv_last.ncol = ncol; conv_last.nact = nact;
+    conv_last.form = !conv_walk ? 0 : cfg.ldirect == 1 ? 1 : 2;
+    conv_last.valid = true;
     return 0;
+  }
+
+  // fpx_conv_columns: one gather kernel over the scratch of the last call; nothing of fpx_convmix runs
+  template <typename H>
+  int conv_columns_t(const int32_t *col, int ncol_req, int32_t *lconv, int32_t *nconvtop, void *fmassfrac, void *uvzlev) {
+    const int nl = conv_nconvlev + 1, nv = conv_nuvz + 2;      // nconvtop <= nconvlev + 1 (CONVECT's inb <= nconvlev), uvzlev(nconvtop + 1) < nv
+    const ConvLast &L = conv_last;
+    const size_t nfm = (size_t)ncol_req * nl * nl, nuz = (size_t)ncol_req * (nl + 1);
+    Scratch ibuf, rbuf;
+    hipError_t e = ibuf.reserve((size_t)ncol_req * 3 * sizeof(int), stream);
+    if (e == hipSuccess) e = rbuf.reserve((nfm + nuz) * sizeof(H), stream);
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("conv_columns: ") + hipGetErrorString(e));
+    int *d_col = ibuf.as<int>(), *d_lconv = d_col + ncol_req, *d_ntop = d_lconv + ncol_req;
+    H *d_fm = rbuf.as<H>(), *d_uz = d_fm + nfm;
+    HIPCHK(hipMemcpyAsync(d_col, col, (size_t)ncol_req * sizeof(int), hipMemcpyHostToDevice, stream));
+    H *vbuf = nullptr, *mbuf = nullptr;
+    const unsigned int *srank = nullptr;
+    if (L.nact > 0) {                                      // the layout of convmix_t's scratch
+      const size_t vec_elems = conv::vec_elems_per_column<H>(nv) * conv::group_round((size_t)L.nact);
+      const size_t cst_elems = conv::group_round((size_t)conv::C_COUNT * L.nact);
+      vbuf = conv_scr.as<H>(); mbuf = vbuf + vec_elems + cst_elems;
+      srank = conv_alive.as<unsigned int>() + L.nact;
+    }
+    conv::k_conv_columns<H><<<ncol_req, 64, 0, stream>>>(d_col, L.ncol, conv_flag, conv_rank, srank, conv_lconv, conv_ntop, vbuf, mbuf, nv, L.nact,
+                                                        L.Bm, nl, L.form, d_lconv, d_ntop, d_fm, d_uz);
+    HIPCHK(hipGetLastError());
+    if (lconv) HIPCHK(hipMemcpyAsync(lconv, d_lconv, (size_t)ncol_req * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (nconvtop) HIPCHK(hipMemcpyAsync(nconvtop, d_ntop, (size_t)ncol_req * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (fmassfrac) HIPCHK(hipMemcpyAsync(fmassfrac, d_fm, nfm * sizeof(H), hipMemcpyDeviceToHost, stream));
+    if (uvzlev) HIPCHK(hipMemcpyAsync(uvzlev, d_uz, nuz * sizeof(H), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  int conv_columns(const int32_t *col, int ncol_req, int32_t *lconv, int32_t *nconvtop, void *fmassfrac, void *uvzlev) override {
+    if (!conv_on) return fail(FPX_ERR_STATE, "conv_columns: fpx_conv_init first");
+    if (!conv_last.valid) return fail(FPX_ERR_STATE, "conv_columns: no completed call of fpx_convmix to report");
+    if (conv_last.batches > 1) return fail(FPX_ERR_STATE, "conv_columns: the last call of fpx_convmix ran " + std::to_string(conv_last.batches) + " matrix batches; only the matrices of the last one exist (raise the option \"conv_scratch_mb\" of fpx_set_option)");
+    if (ncol_req < 0 || (ncol_req > 0 && !col)) return fail(FPX_ERR_ARG, "conv_columns: ncol < 0 or col is null");
+    for (int i = 0; i < ncol_req; i++)
+      if (col[i] < 0 || col[i] >= conv_last.ncol) return fail(FPX_ERR_ARG, "conv_columns: column out of range (mother grid first, then the nests)");
+    if (ncol_req == 0) return 0;
+    return cfg.host_real_bytes == 4 ? conv_columns_t<float>(col, ncol_req, lconv, nconvtop, fmassfrac, uvzlev)
+                                    : conv_columns_t<double>(col, ncol_req, lconv, nconvtop, fmassfrac, uvzlev);
   }
 
   int convmix(int itime, int64_t *nmoved) override {
@@ -2502,7 +2558,7 @@ struct Engine : EngineBase {
     if (1 + V.numbnests > conv::kConvMaxDom) return fail(FPX_ERR_UNSUPPORTED, "convmix: too many nests");
     if (!window_set) return fail(FPX_ERR_STATE, "convmix: fpx_set_windtime first");
     if (!height_set) return fail(FPX_ERR_STATE, "convmix: set_height first");
-    if (numpart == 0) { if (nmoved) *nmoved = 0; return 0; }
+    if (numpart == 0) { if (nmoved) *nmoved = 0; conv_last = ConvLast{}; return 0; }
     return cfg.host_real_bytes == 4 ? convmix_t<float>(itime, nmoved) : convmix_t<double>(itime, nmoved);
   }
 
@@ -3173,6 +3229,7 @@ struct Engine : EngineBase {
     else if (n == "domainfill_cand_us") *value = (int64_t)(dfl_stage_ms[2] * 1000.);
     else if (n == "domainfill_place_us") *value = (int64_t)(dfl_stage_ms[3] * 1000.);
     else if (n == "domainfill_candidates") *value = dfl_last_ncand;
+    else if (n == "conv_batches") *value = conv_last.valid ? conv_last.batches : -1;   // matrix batches of the last fpx_convmix
     else if (n == "plumetraj_sweeps") { int m = 0; for (int v : pt_rec_it) m = std::max(m, v); *value = m; }
     else if (n == "pbl_list_length") {   // the four class counts k_list_counts left for the first launch of the last step
       unsigned int hc[4] = {0u, 0u, 0u, 0u};
@@ -4803,6 +4860,10 @@ int fpx_conv_init(fpx_handle h, const fpx_conv_config *c) { FPX_GUARD(h); return
 int fpx_upload_conv_fields(fpx_handle h, int32_t slot, const fpx_conv_fields *f) { FPX_GUARD(h); return h->impl->upload_conv_fields(slot, f); }
 int fpx_convmix(fpx_handle h, int32_t itime, int64_t *nmoved) { FPX_GUARD(h); return h->impl->convmix(itime, nmoved); }
 int fpx_convmix_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return FPX_ERR_ARG; *ms = h->impl->conv_ms(); return 0; }
+int fpx_conv_columns(fpx_handle h, const int32_t *col, int32_t ncol, int32_t *lconv, int32_t *nconvtop, void *fmassfrac, void *uvzlev) {
+  FPX_GUARD(h);
+  return h->impl->conv_columns(col, ncol, lconv, nconvtop, fmassfrac, uvzlev);
+}
 int fpx_upload_diag_nest_fields(fpx_handle h, int32_t nest, int32_t slot, const fpx_diag_fields *f) { FPX_GUARD(h); return h->impl->upload_diag_nest_fields(nest, slot, f); }
 int fpx_upload_conv_nest_fields(fpx_handle h, int32_t nest, int32_t slot, const fpx_conv_fields *f) { FPX_GUARD(h); return h->impl->upload_conv_nest_fields(nest, slot, f); }
 int fpx_get_cbaseflux_nest(fpx_handle h, int32_t nest, void *cb) { FPX_GUARD(h); return h->impl->cbaseflux_nest_io(nest, cb, false); }

@@ -516,7 +516,7 @@ class Engine:
         for k, a in keep.items():
             setattr(c, k, a.ctypes.data)
         check(self.lib.fpx_conv_init(self.h, C.byref(c)), "fpx_conv_init")
-        self.conv_nuvz = c.nuvz
+        self.conv_nuvz, self.conv_nconvlev = c.nuvz, c.nconvlev
         self.has_conv = True
 
     def upload_conv_fields(self, slot, ps, tt2, td2, tth, qvh, nuvzmax=None):
@@ -573,6 +573,19 @@ class Engine:
         check(self.lib.fpx_convmix_time(self.h, C.byref(ms)), "fpx_convmix_time")
         self.convmix_device_ms = ms.value
         return int(n.value)
+
+    def conv_columns(self, cols):
+        """fpx_conv_columns: what the last convmix() left for the columns `cols` (numbered through all wind-field domains, mother
+        grid first) -> lconv [n] (-1: not visited), nconvtop [n], fmassfrac [n][nconvlev+1][nconvlev+1] ((k, kk) at [kk-1][k-1]) and
+        uvzlev [n][nconvlev+2] as float64, zero beyond nconvtop (nconvtop + 1).  Raises FpxError (code -3) when the call ran more
+        than one matrix batch."""
+        col = np.ascontiguousarray(cols, np.int32).ravel()
+        n, nl = int(col.size), self.conv_nconvlev + 1
+        lconv = np.zeros(n, np.int32); ntop = np.zeros(n, np.int32)
+        fm = np.zeros((n, nl, nl), self.hreal); uvz = np.zeros((n, nl + 1), self.hreal)
+        check(self.lib.fpx_conv_columns(self.h, col.ctypes.data, n, lconv.ctypes.data, ntop.ctypes.data, fm.ctypes.data, uvz.ctypes.data),
+              "fpx_conv_columns")
+        return lconv, ntop, fm.astype(np.float64), uvz.astype(np.float64)
 
     def cbaseflux(self, new=None):
         a = np.zeros((self.ny, self.nx), self.hreal)

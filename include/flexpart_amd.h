@@ -441,6 +441,19 @@ int fpx_conv_init(fpx_handle h, const fpx_conv_config *c);
 int fpx_upload_conv_fields(fpx_handle h, int32_t slot, const fpx_conv_fields *f);
 int fpx_convmix(fpx_handle h, int32_t itime, int64_t *nmoved);
 int fpx_convmix_time(fpx_handle h, double *ms);
+/* Diagnostics: what the last call of fpx_convmix left for the columns col[0 .. ncol), numbered through all wind-field domains
+ * (mother grid first: jy * nx + ix, then nest 1 from nx * ny on, ...).  Every output may be NULL.
+ *   lconv[i]      -1: the call did not visit the column (no particle due in it), 0: not convective, 1: convective
+ *   nconvtop[i]   conv_mod nconvtop of a convective column, else 0
+ *   fmassfrac     [ncol][nconvlev+1][nconvlev+1] in the host's real kind (nconvtop can reach nconvlev + 1: CONVECT's inb goes
+ *                 up to nconvlev): fmassfrac(k, kk), 1 <= k, kk <= nconvlev + 1, of column i at [i][kk-1][k-1]; zero beyond
+ *                 nconvtop and for columns that are not convective.  Un-laid-out from the form the call stored (interleaved,
+ *                 walk-major, transposed walk-major: "conv_no_walk", "conv_one_lane", ldirect)
+ *   uvzlev        [ncol][nconvlev+2]: the half-level heights uvzlev(1 .. nconvtop+1) of redist.f90:83-121, zero beyond
+ * Reads the scratch of that call; runs none of its kernels.  FPX_ERR_STATE if there was no such call, or if it ran more than
+ * one matrix batch (fpx_get_info "conv_batches"; only the matrices of the last batch exist: raise "conv_scratch_mb");
+ * FPX_ERR_ARG for a column out of range.  No reference counterpart; used by the tests to pin the matrices. */
+int fpx_conv_columns(fpx_handle h, const int32_t *col, int32_t ncol, int32_t *lconv, int32_t *nconvtop, void *fmassfrac, void *uvzlev);
 int fpx_upload_conv_nest_fields(fpx_handle h, int32_t nest, int32_t slot, const fpx_conv_fields *f);
 int fpx_get_cbaseflux_nest(fpx_handle h, int32_t nest, void *cbasefluxn);
 int fpx_set_cbaseflux_nest(fpx_handle h, int32_t nest, const void *cbasefluxn);
@@ -998,7 +1011,8 @@ int fpx_set_option(fpx_handle h, const char *name, const char *value);
  * (launches of the Langevin kernel per step = time slices + 1), "pbl_grid" (its persistent grid, blocks; 0 before the
  * first step; after "pbl_grid_blocks"), "pbl_blocks_per_cu" (resident blocks of four waves per CU the grid was sized for),
  * "pbl_list_length" (boundary-layer particles in the work list of the last step: one synchronising copy, diagnostics and
- * tests only).  Unknown names return FPX_ERR_ARG. */
+ * tests only), "conv_batches" (matrix batches of the last fpx_convmix, 0 when no column got past CONVECT's early exits, -1
+ * before the first call).  Unknown names return FPX_ERR_ARG. */
 int fpx_get_info(fpx_handle h, const char *name, int64_t *value);
 
 #ifdef __cplusplus

@@ -24,9 +24,30 @@
 #endif
 typedef ORC_REAL real;
 #define K(x) ((real)(x))
-#define R_POW(a, b) ((real)(sizeof(real) == 4 ? powf((float)(a), (float)(b)) : pow((double)(a), (double)(b))))
-#define R_EXP(a) ((real)(sizeof(real) == 4 ? expf((float)(a)) : exp((double)(a))))
-#define R_LOG(a) ((real)(sizeof(real) == 4 ? logf((float)(a)) : log((double)(a))))
+/* Every libm result whose last bits another libm may give differently goes through cvo_libm(): with the perturbation off
+ * (the default) the value is returned untouched; otherwise it is moved by a whole number of ulps of `real`, so that a test can
+ * measure from the reference side alone how far a result may move under a libm that keeps its documented error bound. */
+static int cvo_pert_mode = 0;                 /* 0 off, 1 random in {-2 .. +2}, 2 all +2, 3 all -2 */
+static uint64_t cvo_pert_state = 0;
+void cvo_set_libm_perturbation(int mode, unsigned int seed) {
+  cvo_pert_mode = mode;
+  cvo_pert_state = 0x9E3779B97F4A7C15ull ^ ((uint64_t)seed * 0xD1342543DE82EF95ull);
+}
+static real cvo_libm(real v) {
+  int n, i;
+  if (cvo_pert_mode == 0) return v;
+  if (cvo_pert_mode == 1) {
+    cvo_pert_state = cvo_pert_state * 6364136223846793005ull + 1442695040888963407ull;
+    n = (int)((cvo_pert_state >> 33) % 5u) - 2;
+  } else n = cvo_pert_mode == 2 ? 2 : -2;
+  if (!(v - v == (real)0) || v == (real)0) return v;          /* inf, nan, zero: left alone */
+  for (i = 0; i < (n < 0 ? -n : n); i++)
+    v = sizeof(real) == 4 ? (real)nextafterf((float)v, n > 0 ? INFINITY : -INFINITY) : (real)nextafter((double)v, n > 0 ? INFINITY : -INFINITY);
+  return v;
+}
+#define R_POW(a, b) cvo_libm((real)(sizeof(real) == 4 ? powf((float)(a), (float)(b)) : pow((double)(a), (double)(b))))
+#define R_EXP(a) cvo_libm((real)(sizeof(real) == 4 ? expf((float)(a)) : exp((double)(a))))
+#define R_LOG(a) cvo_libm((real)(sizeof(real) == 4 ? logf((float)(a)) : log((double)(a))))
 #define R_SQRT(a) ((real)(sizeof(real) == 4 ? sqrtf((float)(a)) : sqrt((double)(a))))
 #define R_ABS(a) ((a) < 0 ? -(a) : (a))
 #define R_MAX(a, b) ((a) > (b) ? (a) : (b))
@@ -712,8 +733,8 @@ typedef struct {
   double *rn;
   int32_t *lconv_col;
   int32_t *nconvtop_col;
-  double *fmassfrac_col;                        /* [ncap][nconvlev][nconvlev] of the first ncap convective columns, (k,kk) -> [kk][k] */
-  int32_t *fm_col_id;                           /* [ncap] column index of each stored matrix */
+  double *fmassfrac_col;                        /* [ncap][fm_dim][fm_dim] of the first ncap convective columns, (k,kk) -> [kk][k] */
+  int32_t *fm_col_id;                           /* [ncap] column index of each stored matrix; the nest's columns follow the mother grid's (nx*ny + c) */
   int32_t fm_cap, fm_count;
   int32_t ran3_seeded;                          /* in/out: the shared stream is already initialised (second call) */
   int32_t state_words[60];                      /* in/out: ma[1..55], inext, inextp, iff, iseed */
@@ -724,6 +745,10 @@ typedef struct {
   const double *psn, *tt2n, *td2n;              /* [2][nyn][nxn] */
   const double *tthn, *qvhn;                    /* [2][nuvz][nyn][nxn] */
   double *cbasefluxn;                           /* [nyn][nxn], in/out */
+  /* more diagnostics (may be NULL): uvzlev(1 .. nconvtop+1) of every stored matrix, zero beyond; lconv / nconvtop of the nest's columns */
+  double *uvzlev_col;                           /* [ncap][fm_dim+1] */
+  int32_t *lconv_coln, *nconvtop_coln;          /* [nyn][nxn] */
+  int32_t fm_dim, pad2_;                        /* rows and columns of a stored matrix; 0: nconvlev (nconvtop can be nconvlev + 1) */
 } cvo_args;
 
 static int cvo_nint(double x) { return (int)(x < 0 ? x - 0.5 : x + 0.5); }
@@ -737,7 +762,7 @@ void cvo_convmix(cvo_args *A) {
   real *akm = (real *)malloc((nuvz + 1) * sizeof(real)), *bkm = (real *)malloc((nuvz + 1) * sizeof(real));
   const size_t n2 = (size_t)nx * ny;
   real dt1, dt2, dtt, delt;
-  int lconv = 0, ktop = 0, igrold, igr, ix = 0, jy = 0, kz;
+  int lconv = 0, ktop = 0, igrold, igr, ix = 0, jy = 0, kz, rec = -1;
   long ipart, kpart;
   A->status = 0;
   A->fm_count = 0;
@@ -782,6 +807,7 @@ void cvo_convmix(cvo_args *A) {
       }
     }
     if (A->lconv_col) for (size_t c = 0; c < n2; c++) A->lconv_col[c] = -1;
+    if (A->nest_on && A->lconv_coln) for (size_t c = 0; c < (size_t)A->nxn * A->nyn; c++) A->lconv_coln[c] = -1;
     for (int pass = 0; pass <= (A->nest_on ? 1 : 0); pass++) {
       const int gnx = pass ? A->nxn : nx, gny = pass ? A->nyn : ny;
       const size_t g2 = (size_t)gnx * gny, g3 = g2 * nuvz;
@@ -812,15 +838,18 @@ void cvo_convmix(cvo_args *A) {
               lconv = cvo_calcmatrix(S, nuvz, akz, bkz, akm, bkm, delt, &cb);
               cbf[c] = (double)cb;
             }
-            if (!pass) {
-              if (A->lconv_col) A->lconv_col[c] = lconv;
-              if (A->nconvtop_col) A->nconvtop_col[c] = lconv ? S->nconvtop : 0;
+            {
+              int32_t *lc = pass ? A->lconv_coln : A->lconv_col, *nt = pass ? A->nconvtop_coln : A->nconvtop_col;
+              if (lc) lc[c] = lconv;
+              if (nt) nt[c] = lconv ? S->nconvtop : 0;
+              rec = -1;
               if (lconv && A->fmassfrac_col && A->fm_count < A->fm_cap) {
-                const int nl = S->nconvlev;
+                const int nl = A->fm_dim > 0 ? A->fm_dim : S->nconvlev;
                 double *dst = A->fmassfrac_col + (size_t)A->fm_count * nl * nl;
                 for (int kk = 1; kk <= nl; kk++)
                   for (int k = 1; k <= nl; k++) dst[(size_t)(kk - 1) * nl + (k - 1)] = (k <= S->nconvtop && kk <= S->nconvtop) ? (double)A2(S->fmassfrac, k, kk) : 0.0;
-                A->fm_col_id[A->fm_count++] = (int32_t)c;
+                rec = A->fm_count;
+                A->fm_col_id[A->fm_count++] = (int32_t)((pass ? n2 : 0) + c);
               }
             }
           }
@@ -829,7 +858,13 @@ void cvo_convmix(cvo_args *A) {
         }
         if (lconv) {
           real zt = (real)A->ztra1[ipart - 1], rn = K(-1.);
+          const int first = ktop <= 1;            /* redist computes the half-level heights with the first particle of a column */
           const int drew = cvo_redist(S, &zt, &ktop, A->ldirect, A->lsynctime, (real)A->height_nz, &rn);
+          if (first && rec >= 0 && A->uvzlev_col) {
+            const int nl = A->fm_dim > 0 ? A->fm_dim : S->nconvlev;
+            double *dst = A->uvzlev_col + (size_t)rec * (nl + 1);
+            for (kz = 1; kz <= nl + 1; kz++) dst[kz - 1] = kz <= S->nconvtop + 1 ? (double)S->uvzlev[kz] : 0.0;
+          }
           A->ztra1[ipart - 1] = (double)zt;
           if (A->rn && drew) A->rn[ipart - 1] = (double)rn;
         }

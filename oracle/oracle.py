@@ -728,12 +728,20 @@ class _CvoArgs(C.Structure):
                 ("nest_on", C.c_int32), ("nxn", C.c_int32), ("nyn", C.c_int32), ("pad_", C.c_int32),
                 ("xln", C.c_double), ("yln", C.c_double), ("xrn", C.c_double), ("yrn", C.c_double), ("xresoln", C.c_double), ("yresoln", C.c_double),
                 ("eps", C.c_double), ("psn", C.c_void_p), ("tt2n", C.c_void_p), ("td2n", C.c_void_p), ("tthn", C.c_void_p), ("qvhn", C.c_void_p),
-                ("cbasefluxn", C.c_void_p)]
+                ("cbasefluxn", C.c_void_p), ("uvzlev_col", C.c_void_p), ("lconv_coln", C.c_void_p), ("nconvtop_coln", C.c_void_p),
+                ("fm_dim", C.c_int32), ("pad2_", C.c_int32)]
 
 
-def conv_oracle(cs, kind="r8", fm_cap=8, ran3_words=None, between=None):
-    """convmix on a synthetic.convection_case() dict, one entry per call: ztra1, cbaseflux, lconv / nconvtop per column,
-    the random number each particle drew (-1: none), the redistribution matrices of the first fm_cap convective columns.
+LIBM_OFF, LIBM_RANDOM, LIBM_UP, LIBM_DOWN = 0, 1, 2, 3      # cvo_set_libm_perturbation modes
+
+
+def conv_oracle(cs, kind="r8", fm_cap=8, ran3_words=None, between=None, libm=(LIBM_OFF, 0), fm_dim=None):
+    """convmix on a synthetic.convection_case() dict, one entry per call: ztra1, cbaseflux, lconv / nconvtop per column
+    (lconvn / nconvtopn: the nest's), the random number each particle drew (-1: none), the redistribution matrices and the
+    half-level heights uvzlev(1 .. nconvtop+1) of the first fm_cap convective columns (fm_col: their column numbers, the
+    nest's columns counted on from nx*ny; fm_dim: rows and columns kept of a matrix, default nconvlev -- nconvtop can be
+    nconvlev + 1, which takes fm_dim = nconvlev + 1).  libm = (mode, seed): every exp / log / pow result of the scheme is moved by a
+    whole number of ulps of the real kind -- LIBM_RANDOM: drawn from {-2 .. +2}, LIBM_UP / LIBM_DOWN: all +2 / all -2.
     ran3_words: the state of the module's ran3 stream to start from (Oracle.ran3_words(); redist's own seed, word 59, is
     set to its initial -88); default: an unseeded stream.  between(ic, arrays, words): called after every call with the
     particle arrays {x, y, z} and the stream state, all of which it may change in place (a test runs the trajectory step
@@ -743,6 +751,7 @@ def conv_oracle(cs, kind="r8", fm_cap=8, ran3_words=None, between=None):
     nx, ny, nuvz = (int(v) for v in cs["grid"])
     n = int(cs["npart"])
     nl = int(cs["nconvlev"])
+    nd = nl if fm_dim is None else int(fm_dim)
     keep = {k: _f64(cs[k]) for k in ("akz", "bkz", "akm", "bkm", "ps", "tt2", "td2", "tth", "qvh", "xtra1", "ytra1")}
     if between is not None:                                  # the callback moves the particles: not in the caller's arrays
         keep["xtra1"], keep["ytra1"] = keep["xtra1"].copy(), keep["ytra1"].copy()
@@ -760,6 +769,7 @@ def conv_oracle(cs, kind="r8", fm_cap=8, ran3_words=None, between=None):
     a.numpart = n
     a.ztra1 = z.ctypes.data
     a.fm_cap = fm_cap
+    a.fm_dim = nd
     a.ran3_seeded = 0
     if ran3_words is not None:
         a.ran3_seeded = 1
@@ -782,15 +792,23 @@ def conv_oracle(cs, kind="r8", fm_cap=8, ran3_words=None, between=None):
         itra1 = np.where(np.asarray(cs["due"])[:, ic], itime, itime + 12345).astype(np.int32)
         rn = np.zeros(n)
         lc = np.zeros((ny, nx), np.int32); nt = np.zeros((ny, nx), np.int32)
-        fm = np.zeros((fm_cap, nl, nl)); fid = np.full(fm_cap, -1, np.int32)
+        fm = np.zeros((fm_cap, nd, nd)); fid = np.full(fm_cap, -1, np.int32); uvz = np.zeros((fm_cap, nd + 1))
         a.itime = itime
         a.itra1 = itra1.ctypes.data
         a.rn, a.lconv_col, a.nconvtop_col = rn.ctypes.data, lc.ctypes.data, nt.ctypes.data
-        a.fmassfrac_col, a.fm_col_id = fm.ctypes.data, fid.ctypes.data
-        lib.cvo_convmix(C.byref(a))
-        out.append(dict(ztra1=z.copy(), cbaseflux=cb.copy(), lconv=lc, nconvtop=nt, rn=rn, fmassfrac=fm, fm_col=fid, fm_count=int(a.fm_count)))
+        a.fmassfrac_col, a.fm_col_id, a.uvzlev_col = fm.ctypes.data, fid.ctypes.data, uvz.ctypes.data
         if cbn is not None:
-            out[-1]["cbasefluxn"] = cbn.copy()
+            lcn = np.zeros((int(a.nyn), int(a.nxn)), np.int32); ntn = np.zeros((int(a.nyn), int(a.nxn)), np.int32)
+            a.lconv_coln, a.nconvtop_coln = lcn.ctypes.data, ntn.ctypes.data
+        lib.cvo_set_libm_perturbation(int(libm[0]), C.c_uint(int(libm[1]) + 7919 * ic))
+        try:
+            lib.cvo_convmix(C.byref(a))
+        finally:
+            lib.cvo_set_libm_perturbation(LIBM_OFF, C.c_uint(0))     # the library is shared by every caller in the process
+        out.append(dict(ztra1=z.copy(), cbaseflux=cb.copy(), lconv=lc, nconvtop=nt, rn=rn, fmassfrac=fm, fm_col=fid, fm_count=int(a.fm_count),
+                        uvzlev=uvz))
+        if cbn is not None:
+            out[-1].update(cbasefluxn=cbn.copy(), lconvn=lcn, nconvtopn=ntn)
         if between is not None:
             words = np.array(a.state_words[:], np.int32)
             between(ic, dict(x=keep["xtra1"], y=keep["ytra1"], z=z), words)
