@@ -26,6 +26,7 @@
 #include "fpx_tu.hpp"
 #include "fpx_device.hpp"
 #include "fpx_verttransform.hpp"
+#include "fpx_verttransform_gfs.hpp"
 #include "fpx_calcpar.hpp"
 #include "fpx_getvdep.hpp"
 #include "fpx_calcpv.hpp"
@@ -72,6 +73,7 @@ struct EngineBase {
   virtual int upload_fields(int slot, const fpx_fields *f) = 0;
   virtual int verttransform(int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) = 0;
   virtual int verttransform_nest(int nest, int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) = 0;
+  virtual int verttransform_gfs(int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out, void *pplev_out) = 0;
   virtual int calcpar(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) = 0;
   virtual int calcpar_nest(int nest, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) = 0;
   virtual double cp_ms() = 0;
@@ -968,6 +970,7 @@ struct Engine : EngineBase {
   bool vdep_pending[2] = {false, false};
   bool nest_vdep_pending[kMaxNests][2] = {};
   int calcpar(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) override {
+    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "calcpar: NCEP GFS fields: the NCEP branch of calcpar.f90:109-121,145-149 (first level above ground, mixing height from the GRIB file) is not computed by this engine");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "calcpar: slot must be 1 or 2");
     if (!c || !c->surfstr || !c->sshf || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "calcpar: surfstr, sshf, akm, bkm are required");
     if (c->lsubgrid == 1 && !c->excessoro) return fail(FPX_ERR_ARG, "calcpar: excessoro required with lsubgrid = 1");
@@ -976,6 +979,7 @@ struct Engine : EngineBase {
     return cfg.host_real_bytes == 4 ? calcpar_t<float>(0, slot, c, out) : calcpar_t<double>(0, slot, c, out);
   }
   int calcpar_nest(int nest, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) override {
+    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "calcpar_nest: NCEP GFS fields: the NCEP branch of calcpar.f90:109-121,145-149 is not computed by this engine, and the reference has no GFS nests");
     if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "calcpar_nest: nest out of range (fpx_nests_init first)");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "calcpar_nest: slot must be 1 or 2");
     if (!c || !c->surfstr || !c->sshf || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "calcpar_nest: surfstrn, sshfn, akm, bkm are required");
@@ -1202,7 +1206,174 @@ struct Engine : EngineBase {
   double vt_ms() override { return vt_last_ms; }
   double cp_ms() override { return cp_last_ms; }
 
+  // ---- verttransform_gfs on the device (fpx_verttransform_gfs.hpp) ----------------------------------------------
+  // NCEP GFS pressure-level input -> z-level fields.  The same buffers, calcpv launch and repacking as verttransform_t;
+  // the kernels, the per-slot persistent ww and pplev are its own.
+  enum { MET_NONE = 0, MET_ECMWF = 1, MET_GFS = 2 };
+  int met_format = MET_NONE;              // set by the first successful transform of the handle
+  void *gfs_ww[2] = {nullptr, nullptr};   // ww(:,:,:,n) of com_mod in the host's layout and kind: zero at first use, cells the
+  void *gfs_pplev = nullptr;              // routine does not write keep their content (verttransform_gfs.f90:271-285); pplev of the last call
+  template <typename H>
+  int verttransform_gfs_t(int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out, void *pplev_out) {
+    const int nz = cfg.nz;
+    const HostGrid HG = host_grid(0);
+    const int gnx = HG.nx, gny = HG.ny, gnxmax = HG.nxmax, gnymax = HG.nymax;
+    void **vt_dev = vt_sets[0];
+    const size_t n2 = (size_t)gnxmax * gnymax, n3 = n2 * nz;
+    int rc;
+    enum { UUH, VVH, PVH, WWH, TTH, QVH, PS, TT2, TD2, AKZ, BKZ, AKN, BKN, HGT,
+           UU, VV, WW, TT, QV, PV, RHO, DRHO, UPOL, VPOL, UVZ, WZ, RHOH, PINM, KUV, KW, NBUF };
+    if (!vt_set_ready[0]) {               // the buffer set of verttransform_t (fpx_get_pvh reads its PVH)
+      for (int i = 0; i < NBUF; i++) {
+        const size_t n = (i >= PS && i <= TD2) ? n2 : (i >= AKZ && i <= HGT) ? (size_t)nz : n3;
+        H *q = nullptr;
+        if ((rc = dalloc(&q, n))) return rc;
+        HIPCHK(hipMemsetAsync(q, 0, n * sizeof(H), stream));
+        vt_dev[i] = q;
+      }
+      vt_set_ready[0] = true;
+    }
+    for (int i = 0; i < 3; i++) {
+      void *&dst = i < 2 ? gfs_ww[i] : gfs_pplev;
+      if (dst) continue;
+      H *q = nullptr;
+      if ((rc = dalloc(&q, n3))) return rc;
+      HIPCHK(hipMemsetAsync(q, 0, n3 * sizeof(H), stream));
+      dst = q;
+    }
+    auto D = [&](int i) { return (H *)vt_dev[i]; };
+    const int s = slot - 1;
+    H *d_ww = (H *)gfs_ww[s], *d_pplev = (H *)gfs_pplev;
+    if (m->init || !height_set) {         // verttransform_gfs.f90:84-139: the same code as the ECMWF routine's
+      std::vector<H> hgt;
+      int nmixz = 0;
+      if ((rc = vt_init_height<H>(m, hgt, nmixz))) return rc;
+      if ((rc = set_height(hgt.data(), nz))) return rc;
+      V.nmixz = nmixz;
+      cfg.nmixz = nmixz;
+    }
+    {
+      std::vector<H> hh(nz);
+      for (int k = 0; k < nz; k++) hh[k] = (H)height_host[k];
+      HIPCHK(hipMemcpyAsync(D(HGT), hh.data(), nz * sizeof(H), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+    const void *src[13] = {m->uuh, m->vvh, m->pvh, m->wwh, m->tth, m->qvh, m->ps, m->tt2, m->td2, m->akz, m->bkz, m->aknew, m->bknew};
+    for (int i = 0; i < 13; i++) {
+      if (i == PVH && !m->pvh) continue;
+      const size_t n = (i >= PS && i <= TD2) ? n2 : (i >= AKZ) ? (size_t)nz : n3;
+      if (m->pin_host && n >= n2) pin_host_range(src[i], n * sizeof(H));
+      HIPCHK(hipMemcpyAsync(D(i), src[i], n * sizeof(H), hipMemcpyHostToDevice, stream));
+    }
+    vt::Geo<H> G;
+    G.nx = gnx; G.ny = gny; G.nz = nz; G.nuvz = nz; G.nwz = nz; G.nxmax = gnxmax; G.nymax = gnymax;
+    G.dx = (H)cfg.dx; G.dy = (H)cfg.dy; G.xlon0 = (H)cfg.xlon0; G.ylat0 = (H)cfg.ylat0;
+    {   // gridcheck_gfs.f90:241-242
+      const H pi = (H)3.14159265, r_earth = (H)6.371e6;
+      G.dxconst = (H)180. / (G.dx * r_earth * pi);
+      G.dyconst = (H)180. / (G.dy * r_earth * pi);
+    }
+    G.xres = (H)1.; G.yres = (H)1.;
+    G.nglobal = cfg.nglobal; G.sglobal = cfg.sglobal;
+    G.switchnorthg = (H)cfg.switchnorthg; G.switchsouthg = (H)cfg.switchsouthg;
+    for (int i = 0; i < 9; i++) { G.northpolemap[i] = (H)cfg.northpolemap[i]; G.southpolemap[i] = (H)cfg.southpolemap[i]; }
+    vt::In<H> I{D(UUH), D(VVH), D(PVH), D(WWH), D(TTH), D(QVH), D(PS), D(TT2), D(TD2), D(AKZ), D(BKZ), D(AKN), D(BKN), D(HGT)};
+    vt::Out<H> O{D(UU), D(VV), d_ww, D(TT), D(QV), D(PV), D(RHO), D(DRHO), D(UPOL), D(VPOL), D(UVZ), D(WZ), D(RHOH), D(PINM)};
+    Events<2> pev, ev;
+    if (!m->pvh) {                        // calcpv.f90 has no format branch: ppml = akz + bkz*ps
+      pv::Args<H> P;
+      P.nx = gnx; P.ny = gny; P.nuvz = nz; P.nxmax = gnxmax; P.nymax = gnymax;
+      P.xglobal = cfg.xglobal; P.nglobal = cfg.nglobal; P.sglobal = cfg.sglobal;
+      P.dx = (H)cfg.dx; P.dy = G.dy; P.ylat0 = G.ylat0;
+      P.uuh = D(UUH); P.vvh = D(VVH); P.tth = D(TTH); P.ps = D(PS); P.akz = D(AKZ); P.bkz = D(BKZ);
+      P.ppml = D(UVZ); P.theta = D(WZ); P.pvh = D(PVH);
+      HIPCHK(pev.create());
+      HIPCHK(hipEventRecord(pev[0], stream));
+      const dim3 gp((gnx * gny + 255) / 256, nz);
+      pv::k_theta<H><<<gp, 256, 0, stream>>>(P);
+      pv::k_pv<H><<<gp, 256, 0, stream>>>(P);
+      if (P.nglobal || P.sglobal) pv::k_pole<H><<<dim3((nz + 63) / 64, 2), 64, 0, stream>>>(P);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(pev[1], stream));
+    }
+    HIPCHK(ev.create());
+    HIPCHK(hipEventRecord(ev[0], stream));
+    const int nb = (gnx * gny + 255) / 256;
+    vt::k_vg_levels<H><<<nb, 256, 0, stream>>>(G, I, O);
+    vt::k_vg_column<H><<<nb, 256, (size_t)5 * nz * sizeof(H), stream>>>(G, I, O, d_pplev);
+    const size_t smrow = (size_t)(gnx + 3) * sizeof(H);
+    if (G.nglobal) {
+      const int jy0 = std::max(0, (int)G.switchnorthg - 2), jy1 = cfg.ny - 1;
+      if (jy1 >= jy0) vt::k_vt_polar<H><<<dim3((cfg.nx + 255) / 256, jy1 - jy0 + 1, nz), 256, 0, stream>>>(G, O, jy0, jy1, 0);
+      vt::k_vg_polerow<H><<<nz, 64, smrow, stream>>>(G, O, 0);
+    }
+    if (G.sglobal) {
+      const int jy0 = 0, jy1 = std::min(cfg.ny - 1, (int)G.switchsouthg + 3);
+      if (jy1 >= jy0) vt::k_vt_polar<H><<<dim3((cfg.nx + 255) / 256, jy1 - jy0 + 1, nz), 256, 0, stream>>>(G, O, jy0, jy1, 1);
+      vt::k_vg_polerow<H><<<nz, 64, smrow, stream>>>(G, O, 1);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], stream));
+    // repack into the gather layout, as verttransform_t does
+    auto pk = [&](const H *in, const R *outp, int stride, int off) -> int {
+      dim3 grid((gnx + 31) / 32, (nz + 31) / 32, gny), block(32, 8);
+      k_pack3<H, R><<<grid, block, 0, stream>>>(in, (R *)outp, gnx, gny, nz, gnxmax, gnymax, stride, off);
+      HIPCHK(hipGetLastError());
+      return 0;
+    };
+    const WindDst T = wind_dst(0);
+    if ((rc = pk(D(UU), T.w3, 6, s * 3 + 0)) || (rc = pk(D(VV), T.w3, 6, s * 3 + 1)) || (rc = pk(d_ww, T.w3, 6, s * 3 + 2))) return rc;
+    if (T.w3pol)
+      if ((rc = pk(D(UPOL), T.w3pol, 6, s * 3 + 0)) || (rc = pk(D(VPOL), T.w3pol, 6, s * 3 + 1)) || (rc = pk(d_ww, T.w3pol, 6, s * 3 + 2))) return rc;
+    if ((rc = pk(D(RHO), T.r2, 4, s * 2 + 0)) || (rc = pk(D(DRHO), T.r2, 4, s * 2 + 1))) return rc;
+    if (slot == 1 && T.rhott)
+      if ((rc = pk(D(RHO), T.rhott, 2, 0)) || (rc = pk(D(TT), T.rhott, 2, 1))) return rc;
+    if (wet_on && Wp.ttw) { if ((rc = pk(D(TT), Wp.ttw, 2, s))) return rc; }
+    if ((rc = upload_wind2(0, slot, sfc))) return rc;
+    if ((rc = diag_alloc())) return rc;
+    if ((rc = diag3(D(PV), true, 0, s)) || (rc = diag3(D(QV), true, 1, s)) || (rc = diag3(D(TT), true, 2, s))) return rc;
+    k_hcell<R><<<(gnx * gny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(T.sfc, (R *)T.hcell, gnx, gny);
+    HIPCHK(hipGetLastError());
+    if (out) {
+      void *dst[10] = {out->uu, out->vv, out->ww, out->tt, out->qv, out->pv, out->rho, out->drhodz, out->uupol, out->vvpol};
+      for (int i = 0; i < 10; i++)
+        if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], i == 2 ? d_ww : D(UU + i), n3 * sizeof(H), hipMemcpyDeviceToHost, stream));
+      if (out->height) for (int k = 0; k < nz; k++) ((H *)out->height)[k] = (H)height_host[k];
+      if (out->nmixz) *out->nmixz = V.nmixz;
+    }
+    if (pplev_out) HIPCHK(hipMemcpyAsync(pplev_out, d_pplev, n3 * sizeof(H), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    vt_last_ms = ms;
+    pv_last_ms = 0;
+    if (!m->pvh) {
+      HIPCHK(hipEventElapsedTime(&ms, pev[0], pev[1]));
+      pv_last_ms = ms;
+    }
+    pvh_on_device[0] = true;
+    slot_loaded[s] = true; vdep_pending[s] = false;
+    vt_slot_on_device[0] = slot;
+    return 0;
+  }
+  int verttransform_gfs(int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out, void *pplev_out) override {
+    if (met_format == MET_ECMWF) return fail(FPX_ERR_UNSUPPORTED, "verttransform_gfs: this handle has run an ECMWF transform (fpx_verttransform_ecmwf / fpx_verttransform_nest): GFS fields are refused on it");
+    if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "verttransform_gfs: slot must be 1 or 2");
+    if (!m || !m->uuh || !m->vvh || !m->wwh || !m->tth || !m->qvh || !m->ps || !m->tt2 || !m->td2 || !m->akz || !m->bkz || !m->aknew || !m->bknew)
+      return fail(FPX_ERR_ARG, "verttransform_gfs: uuh, vvh, wwh, tth, qvh, ps, tt2, td2, akz, bkz, aknew, bknew are required (pvh = NULL: calcpv on the device)");
+    if (m->nuvz != cfg.nz || m->nwz != cfg.nz) return fail(FPX_ERR_ARG, "verttransform_gfs: nuvz = nwz = nz expected (gridcheck_gfs.f90:439-491 sets them equal)");
+    if (cfg.nz < 4 || cfg.nz > 65535 || cfg.ny > 65535) return fail(FPX_ERR_ARG, "verttransform_gfs: 4 <= nz <= 65535, ny <= 65535");
+    if (!sfc) return fail(FPX_ERR_UNSUPPORTED, "verttransform_gfs: sfc = NULL: the NCEP branch of calcpar.f90:109-121,145-149 is not computed by this engine; pass the host's hmix, ustar, wstar, oli, tropopause");
+    if (!sfc->hmix || !sfc->ustar || !sfc->wstar || !sfc->oli || !sfc->tropopause) return fail(FPX_ERR_ARG, "verttransform_gfs: the 2-D fields hmix, ustar, wstar, oli, tropopause are required");
+    if (cfg.drydep && !sfc->vdep) return fail(FPX_ERR_ARG, "verttransform_gfs: vdep required with DRYDEP");
+    if (!m->pvh && (cfg.nx < 3 || cfg.ny < 4)) return fail(FPX_ERR_ARG, "verttransform_gfs: calcpv on the device (pvh = NULL) needs nx >= 3, ny >= 4");
+    const int rc = cfg.host_real_bytes == 4 ? verttransform_gfs_t<float>(slot, m, sfc, out, pplev_out) : verttransform_gfs_t<double>(slot, m, sfc, out, pplev_out);
+    if (!rc) met_format = MET_GFS;
+    return rc;
+  }
+
   int verttransform(int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) override {
+    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "verttransform: this handle takes NCEP GFS fields (fpx_verttransform_gfs has run): the ECMWF transform is refused on it");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "verttransform: slot must be 1 or 2");
     if (!m || !m->uuh || !m->vvh || !m->wwh || !m->tth || !m->qvh || !m->ps || !m->tt2 || !m->td2 || !m->akz || !m->bkz || !m->aknew || !m->bknew)
       return fail(FPX_ERR_ARG, "verttransform: uuh, vvh, wwh, tth, qvh, ps, tt2, td2, akz, bkz, aknew, bknew are required (pvh = NULL: calcpv on the device)");
@@ -1211,9 +1382,12 @@ struct Engine : EngineBase {
     if (sfc && (!sfc->hmix || !sfc->ustar || !sfc->wstar || !sfc->oli || !sfc->tropopause)) return fail(FPX_ERR_ARG, "verttransform: the 2-D fields hmix, ustar, wstar, oli, tropopause are required (or sfc = NULL and fpx_calcpar)");
     if (sfc && cfg.drydep && !sfc->vdep) return fail(FPX_ERR_ARG, "verttransform: vdep required with DRYDEP");
     if (!m->pvh && (cfg.nx < 3 || cfg.ny < 4)) return fail(FPX_ERR_ARG, "verttransform: calcpv on the device (pvh = NULL) needs nx >= 3, ny >= 4");
-    return cfg.host_real_bytes == 4 ? verttransform_t<float>(0, slot, m, sfc, out) : verttransform_t<double>(0, slot, m, sfc, out);
+    const int rc = cfg.host_real_bytes == 4 ? verttransform_t<float>(0, slot, m, sfc, out) : verttransform_t<double>(0, slot, m, sfc, out);
+    if (!rc) met_format = MET_ECMWF;
+    return rc;
   }
   int verttransform_nest(int nest, int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) override {
+    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "verttransform_nest: this handle takes NCEP GFS fields (fpx_verttransform_gfs has run): the reference has no GFS nests");
     if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "verttransform_nest: nest out of range (fpx_nests_init first)");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "verttransform_nest: slot must be 1 or 2");
     if (!height_set) return fail(FPX_ERR_STATE, "verttransform_nest: the z levels come from the mother grid's first transform (or fpx_set_height)");
@@ -2188,6 +2362,7 @@ struct Engine : EngineBase {
   double conv_ms() override { return conv_last_ms; }
 
   int conv_init(const fpx_conv_config *c) override {
+    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "conv_init: NCEP GFS fields: convmix.f90:100-116,173-189 (pplev-based columns) and the NCEP branch of calcmatrix.f90 are not computed by this engine");
     if (!c || c->struct_bytes != (int32_t)sizeof(fpx_conv_config)) return fail(FPX_ERR_ARG, "conv_init: null or fpx_conv_config size mismatch (ABI)");
     if (c->nuvz < 4 || c->nconvlev < 2 || c->nconvlev > c->nuvz - 2) return fail(FPX_ERR_ARG, "conv_init: need 2 <= nconvlev <= nuvz - 2");
     if (!c->akz || !c->bkz || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "conv_init: akz, bkz, akm, bkm are required");
@@ -2551,6 +2726,7 @@ struct Engine : EngineBase {
   }
 
   int convmix(int itime, int64_t *nmoved) override {
+    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "convmix: NCEP GFS fields: convmix.f90:100-116,173-189 (pplev-based columns) and the NCEP branch of calcmatrix.f90 are not computed by this engine");
     if (!conv_on) return fail(FPX_ERR_STATE, "convmix: fpx_conv_init first");
     if (!conv_slot[0][0] || !conv_slot[0][1]) return fail(FPX_ERR_STATE, "convmix: fpx_upload_conv_fields of both slots first");
     for (int l = 1; l <= V.numbnests; l++)
@@ -4766,6 +4942,7 @@ int fpx_set_height(fpx_handle h, const void *height, int32_t n) { FPX_GUARD(h); 
 int fpx_upload_fields(fpx_handle h, int32_t slot, const fpx_fields *f) { FPX_GUARD(h); return h->impl->upload_fields(slot, f); }
 int fpx_verttransform_ecmwf(fpx_handle h, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) { FPX_GUARD(h); return h->impl->verttransform(slot, m, sfc, out); }
 int fpx_verttransform_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out) { FPX_GUARD(h); return h->impl->verttransform_nest(nest, slot, m, sfc, out); }
+int fpx_verttransform_gfs(fpx_handle h, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out, void *pplev_out) { FPX_GUARD(h); return h->impl->verttransform_gfs(slot, m, sfc, out, pplev_out); }
 int fpx_upload_diag_fields(fpx_handle h, int32_t slot, const fpx_diag_fields *f) { FPX_GUARD(h); return h->impl->upload_diag_fields(slot, f); }
 int fpx_partoutput(fpx_handle h, int32_t itime, const char *path, int64_t *nparticles) { FPX_GUARD(h); return h->impl->partoutput(itime, path, nparticles); }
 int fpx_readpartpositions(fpx_handle h, const char *path, const fpx_restart *r, int64_t *numpart, int32_t *numparticlecount, int32_t *itimein) {

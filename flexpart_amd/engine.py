@@ -257,6 +257,69 @@ class Engine:
         out["call_ms"] = call_s * 1e3
         return out
 
+    def verttransform_gfs(self, slot, m, sfc, *, init=False,
+                          want=("uu", "vv", "ww", "tt", "qv", "pv", "rho", "drhodz", "uupol", "vvpol", "pplev"), device_pv=False):
+        """fpx_verttransform_gfs: m = synthetic.gfs_levels() dict (compact [nz][ny][nx] arrays, akz = the pressures of the
+        levels), sfc = dict of compact 2-D fields (hmix, ustar, wstar, oli, tropopause[, vdep]) of this slot; sfc = None is
+        passed through as NULL (the library refuses it).  device_pv: pvh = NULL, calcpv runs on the device.
+        Returns the z-level arrays asked for (compact; "pplev" is the GFS extra), height and nmixz."""
+        from ._lib import FpxModelLevels, FpxFieldsOut
+        rt = self.hreal
+        keep = {}
+        ml = FpxModelLevels()
+        for k in ("uuh", "vvh", "pvh", "wwh", "tth", "qvh"):
+            if k == "pvh" and device_pv:
+                continue
+            keep[k] = np.zeros((self.nzmax, self.nymax, self.nxmax), rt)
+            keep[k][: self.nz, : self.ny, : self.nx] = m[k]
+            setattr(ml, k, keep[k].ctypes.data)
+        for k in ("ps", "tt2", "td2"):
+            keep[k] = np.zeros((self.nymax, self.nxmax), rt)
+            keep[k][: self.ny, : self.nx] = m[k]
+            setattr(ml, k, keep[k].ctypes.data)
+        for k in ("akz", "bkz", "aknew", "bknew"):
+            keep[k] = np.ascontiguousarray(np.asarray(m[k]).astype(rt))
+            setattr(ml, k, keep[k].ctypes.data)
+        ml.nuvz = ml.nwz = int(m.get("nuvz", self.nz))
+        ml.init = int(init)
+        f = FpxFields()
+        if sfc is not None:
+            for k in ("hmix", "ustar", "wstar", "oli", "tropopause"):
+                a = np.zeros((self.nymax, self.nxmax), rt)
+                a[: self.ny, : self.nx] = sfc[k]
+                keep["s" + k] = a
+                setattr(f, k, a.ctypes.data)
+            if "vdep" in sfc:
+                v = np.zeros((self.nspec, self.nymax, self.nxmax), rt)
+                v[:, : self.ny, : self.nx] = sfc["vdep"]
+                keep["svdep"] = v
+                f.vdep = v.ctypes.data
+        o = FpxFieldsOut()
+        res = {}
+        for k in want:
+            res[k] = np.zeros((self.nzmax, self.nymax, self.nxmax), rt)
+            if k != "pplev":
+                setattr(o, k, res[k].ctypes.data)
+        hgt = np.zeros(self.nz, rt)
+        o.height = hgt.ctypes.data
+        nmixz = C.c_int32(0)
+        o.nmixz = C.pointer(nmixz)
+        import time as _time
+        t0 = _time.perf_counter()
+        check(self.lib.fpx_verttransform_gfs(self.h, int(slot), C.byref(ml), C.byref(f) if sfc is not None else None, C.byref(o),
+                                             res["pplev"].ctypes.data if "pplev" in res else None), "fpx_verttransform_gfs")
+        call_s = _time.perf_counter() - t0
+        out = {k: v[: self.nz, : self.ny, : self.nx].astype(np.float64) for k, v in res.items()}
+        out["height"] = hgt.astype(np.float64)
+        out["nmixz"] = int(nmixz.value)
+        ms = C.c_double(0)
+        check(self.lib.fpx_verttransform_time(self.h, C.byref(ms)), "fpx_verttransform_time")
+        out["device_ms"] = ms.value
+        check(self.lib.fpx_calcpv_time(self.h, C.byref(ms)), "fpx_calcpv_time")
+        out["calcpv_ms"] = ms.value
+        out["call_ms"] = call_s * 1e3
+        return out
+
     def calcpv_init(self, dxn):
         """fpx_calcpv_init: dxn = com_mod's dxn(1:numbnests), for verttransform(.., nest=.., device_pv=True)."""
         from ._lib import FpxCalcpvCfg

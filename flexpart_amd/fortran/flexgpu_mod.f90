@@ -343,6 +343,16 @@ module flexgpu_mod
       type(c_ptr), value :: sfc            ! c_loc of a type(fpx_fields), or c_null_ptr: flexgpu_calcpar follows
       type(fpx_fields_out), intent(in) :: o
     end function fpx_verttransform_ecmwf
+    ! NCEP GFS fields on pressure levels (verttransform_gfs.f90): sfc is required, pplev_out = c_loc(pplev(0,0,1,n)) or c_null_ptr
+    integer(c_int) function fpx_verttransform_gfs(h, slot, m, sfc, o, pplev_out) bind(C, name='fpx_verttransform_gfs')
+      import :: c_ptr, c_int, c_int32_t, fpx_model_levels, fpx_fields_out
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: slot
+      type(fpx_model_levels), intent(in) :: m
+      type(c_ptr), value :: sfc            ! c_loc of a type(fpx_fields)
+      type(fpx_fields_out), intent(in) :: o
+      type(c_ptr), value :: pplev_out
+    end function fpx_verttransform_gfs
     integer(c_int) function fpx_upload_diag_fields(h, slot, f) bind(C, name='fpx_upload_diag_fields')
       import :: c_ptr, c_int, c_int32_t, fpx_diag_fields
       type(c_ptr), value :: h

@@ -538,6 +538,63 @@ def model_levels(nx=361, ny=181, nz=138, *, global_grid=True, polar=False, phase
 
 
 # --------------------------------------------------------------------------
+# pressure-level input of verttransform_gfs (NCEP GFS)
+# --------------------------------------------------------------------------
+# the pressure levels of the GFS GRIB files [hPa], bottom up (the 26 classic ones are 1000 ... 10 without 40, 15, 7 ...)
+GFS_PLEV_HPA = (1000., 975., 950., 925., 900., 850., 800., 750., 700., 650., 600., 550., 500., 450., 400., 350., 300., 250., 200.,
+                150., 100., 70., 50., 40., 30., 20., 15., 10., 7., 5., 3., 2., 1., 0.7, 0.4, 0.2, 0.1, 0.07, 0.04, 0.02, 0.01)
+
+
+def gfs_levels(nx=361, ny=181, nz=34, *, global_grid=True, polar=False, phase=0, terrain=0.0):
+    """NCEP-GFS-shaped pressure-level input as readwind_gfs / gridcheck_gfs leave it: akz = the pressures of the lowest nz
+    GFS levels (descending), bkz = 0, aknew = akz, bknew = 0, nuvz = nwz = nz (gridcheck_gfs.f90:439-491).  Arrays are
+    compact [nz][ny][nx]; levels below the ground carry (extrapolated) values, as in the GRIB files; `phase` shifts the
+    pattern (another wind field).
+    terrain: depth [Pa] of the deepest surface-pressure depression ('mountain').  terrain = 0: every ps lies between akz[1]
+    and akz[0] = 1000 hPa except one column above 1000 hPa (the column the z levels are built from); terrain > 0: ps runs
+    from about 1030 hPa down to about 1030 hPa - terrain, so the first level above ground (llev of verttransform_gfs.f90:
+    149-154) differs from column to column and low-ps columns end below the top of the reference column.
+    Half of the columns have a lapse rate near zero, so that both outcomes of |tv - tvold| > 0.2 (:174) occur."""
+    if not 4 <= nz <= len(GFS_PLEV_HPA):
+        raise ValueError("gfs_levels: 4 <= nz <= %d" % len(GFS_PLEV_HPA))
+    per = nx - 1
+    i = np.arange(nx, dtype=np.int64)[None, None, :] + int(phase)
+    j = np.arange(ny, dtype=np.int64)[None, :, None]
+    k = np.arange(nz, dtype=np.int64)[:, None, None]
+    s = np.arange(ny, dtype=np.float64)[None, :, None] / float(ny - 1)
+    clat = 4.0 * s * (1.0 - s)
+    ak = 100.0 * np.array(GFS_PLEV_HPA[:nz], np.float64)
+    # 'mountain ranges' in rows 4 ... 3 + (ny-1)/2 only: the rows next to the pole rows stay flat
+    mount = np.maximum(0.0, _wave(2 * i[0] + 3 * j[0], per)) * np.maximum(0.0, _wave(j[0] - 3, ny - 1))
+    if terrain > 0.0:
+        ps = 102200.0 + 800.0 * _wave(i[0] + 2 * j[0], per) - float(terrain) * mount * mount
+    else:
+        ps = 98900.0 + 600.0 * _wave(i[0] + 2 * j[0], per) + 0.0 * j[0]
+        ps[1, 1] = 100600.0
+    zapprox = -7400.0 * np.log(ak / 101325.0)[:, None, None]
+    lam = np.maximum(0.0, _wave(i + 3 * j, per))                                   # lapse-rate factor: 0 over half the columns
+    tth = 288.0 - 0.0065 * zapprox * lam + 3.0 * _wave(i + j, per) + 10.0 * (clat - 0.5) + 0.0 * k
+    qvh = 0.004 * np.exp(-zapprox / 2500.0) * (0.6 + 0.4 * _wave(2 * i + j, per))
+    uuh = 25.0 * clat * (1.0 + 0.3 * _wave(k, nz)) + 6.0 * _wave(3 * i, per) + 0.0 * j
+    vvh = 6.0 * _wave(2 * i + 0 * j, per) * clat + 2.0 * _wave(k + 3 * j, 10) + 0.0 * i   # both signs on the pole rows
+    wwh = 0.4 * _wave(i, per) * _wave(2 * j + 0 * i, ny - 1) * (ak / 101325.0)[:, None, None]
+    pvh = 1.0e-6 * (1.0 + 0.5 * _wave(i + k, per)) * np.exp(zapprox / 12000.0) * (2.0 * s - 1.0)
+    tt2 = tth[0] + 0.5 * _wave(3 * i[0] + j[0], per)
+    td2 = tt2 - 3.0 - 2.0 * (1.0 + _wave(i[0] + 5 * j[0], per))
+    out = dict(akz=ak, bkz=np.zeros(nz), aknew=ak.copy(), bknew=np.zeros(nz), ps=ps, tt2=tt2, td2=td2,
+               tth=tth, qvh=qvh, uuh=uuh, vvh=vvh, pvh=pvh, wwh=wwh)
+    if xcyclic_ok(nx) and global_grid:
+        for key in ("ps", "tt2", "td2", "tth", "qvh", "uuh", "vvh", "pvh", "wwh"):
+            out[key][..., nx - 1] = out[key][..., 0]
+    dx = 360.0 / (nx - 1) if global_grid else 1.0
+    dy = 180.0 / (ny - 1) if global_grid else 1.0
+    out["grid"] = np.array([nx, ny, nz], np.int32)
+    out["geom"] = np.array([dx, dy, -180.0 if global_grid else -20.0, -90.0 if global_grid else 20.0], np.float64)
+    out["globalflags"] = np.array([int(global_grid), int(global_grid and polar), int(global_grid and polar)], np.int32)
+    return out
+
+
+# --------------------------------------------------------------------------
 # particle dump (partoutput.f90): the extra fields it interpolates
 # --------------------------------------------------------------------------
 def add_partoutput_fields(sc, itime=None, dead_every=7):

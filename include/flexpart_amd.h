@@ -257,6 +257,26 @@ int fpx_verttransform_ecmwf(fpx_handle h, int32_t slot, const fpx_model_levels *
  * nest's slot is "not loaded" and fpx_step / fpx_releaseparticles refuse it (FPX_ERR_STATE).  nest_dy, nest_ylat0 of
  * this call are remembered per nest (the latitude of calcpar_nests.f90:73). */
 int fpx_verttransform_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out);
+/* ---- verttransform_gfs on the device: NCEP GFS fields on pressure levels --------------------------------------
+ * Replaces `call verttransform_gfs(memind(k),uuh,vvh,wwh,pvh)` (getfields.f90; the routine: verttransform_gfs.f90:84-494)
+ * followed by fpx_upload_fields of that slot.  fpx_model_levels is reused: akz holds the pressures of the levels
+ * (gridcheck_gfs.f90:439-491: akz = akm, bkz = 0, aknew = akz, nz = nuvz = nwz), nuvz == nwz == nz is required, nest_dy and
+ * nest_ylat0 are ignored, init and pin_host act as for ECMWF (the height initialisation :84-139 is the same code).
+ * What the routine does differently from the ECMWF one is reproduced: the vertical structure of a column starts at its own
+ * level llev (:149-154); pplev; the south pole row's formula (:456); and ww of a z level 2..nz-1 above a column's top is not
+ * written (:271-285), so it keeps what the slot held before the call and the slope term (:354) is added to that -- the engine
+ * keeps a z-level ww per slot for this, zero at first use like com_mod's array (a checkpoint does not carry it).  Where the slope term reads uvwzlev of a
+ * neighbour column below that column's llev (entries of an automatic array the routine never wrote) the device reads 0.
+ * sfc is required: the GFS mixing height comes from the GRIB file and the NCEP branch of calcpar.f90:109-121,145-149 stays
+ * with the host; sfc = NULL returns FPX_ERR_UNSUPPORTED.  pvh = NULL: calcpv on the device first, as for ECMWF (calcpv.f90 has
+ * no format branch); fpx_get_pvh works afterwards.  pplev_out (may be NULL) receives pplev(0:nxmax-1,0:nymax-1,nzmax) of this
+ * slot, which the reference's GFS convection reads (convmix.f90:181-188).  fpx_verttransform_time reports the device time.
+ * Not computed: the cloud block :498-596 (both the readclouds branch and the parameterised one) and clwc, as the ECMWF path
+ * leaves out its cloud diagnostics.
+ * A handle becomes a GFS handle at its first fpx_verttransform_gfs.  On it fpx_calcpar, fpx_calcpar_nest, fpx_conv_init,
+ * fpx_convmix, fpx_verttransform_ecmwf and fpx_verttransform_nest return FPX_ERR_UNSUPPORTED (their ECMWF arithmetic would be
+ * wrong on GFS data), and fpx_verttransform_gfs is refused on a handle that has run an ECMWF transform. */
+int fpx_verttransform_gfs(fpx_handle h, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out, void *pplev_out);
 /* device time of the transform kernels of the last call, milliseconds (without the PV kernels of a call with pvh = NULL) */
 int fpx_verttransform_time(fpx_handle h, double *ms);
 /* ---- calcpv / calcpv_nests on the device (run by the two transforms above when pvh = NULL) -----------------
