@@ -198,6 +198,12 @@ class FpxWetConfig(C.Structure):
                [("readclouds", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+class FpxOhConfig(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("nxOH", C.c_int32), ("nyOH", C.c_int32), ("nzOH", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("lonOH", "latOH", "altOH", "OH_field", "jrate_average", "lonjr", "latjr")] + \
+               [("bdate", C.c_double)] + [(n, C.c_double * FPX_MAXSPEC) for n in ("ohcconst", "ohdconst", "ohnconst")]
+
+
 class FpxWetFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("lsprec", "convprec", "tcc", "ctwc", "tt", "clouds", "cloudsh")]
 
@@ -219,7 +225,7 @@ SYMBOLS = [
     "fpx_step", "fpx_step_async", "fpx_sync", "fpx_counters", "fpx_kernel_time", "fpx_kernel_times", "fpx_sort_particles",
     "fpx_seed_particles", "fpx_stream", "fpx_outgrid_init", "fpx_set_output_times", "fpx_conccalc",
     "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_initcond_finish", "fpx_get_initcond", "fpx_initial_cond_output", "fpx_initcond_time", "fpx_plumetraj_init", "fpx_plumetraj", "fpx_get_plumetraj", "fpx_plumetraj_time", "fpx_domainfill_init", "fpx_boundcond_domainfill", "fpx_get_domainfill_acc", "fpx_set_domainfill_acc", "fpx_boundcond_output", "fpx_domainfill_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
-    "fpx_wetdepo", "fpx_get_wetgrid", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_cbl_probe", "fpx_find_level_probe",
+    "fpx_wetdepo", "fpx_get_wetgrid", "fpx_oh_init", "fpx_ohreaction", "fpx_get_oh_hourly", "fpx_set_oh_hourly", "fpx_ohreaction_time", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_cbl_probe", "fpx_find_level_probe",
     "fpx_outgrid_nest_init", "fpx_get_grids_nest", "fpx_receptors_init", "fpx_get_receptors", "fpx_upload_wet_nest_fields",
     "fpx_verttransform_ecmwf", "fpx_verttransform_nest", "fpx_verttransform_gfs", "fpx_verttransform_time", "fpx_calcpar", "fpx_calcpar_time", "fpx_getvdep_init", "fpx_getvdep", "fpx_getvdep_time", "fpx_calcpar_nest", "fpx_getvdep_nest_init", "fpx_getvdep_nest", "fpx_calcpv_init", "fpx_get_pvh", "fpx_calcpv_time", "fpx_upload_diag_fields", "fpx_partoutput", "fpx_partoutput_time", "fpx_readpartpositions", "fpx_concoutput",
     "fpx_checkpoint_write", "fpx_checkpoint_read",
@@ -227,6 +233,9 @@ SYMBOLS = [
     "fpx_upload_conv_nest_fields", "fpx_get_cbaseflux_nest", "fpx_set_cbaseflux_nest", "fpx_upload_diag_nest_fields",
     "fpx_conv_columns",
 ]
+
+# ... and the one whose name follows the reference routine's spelling (SYMBOLS holds the all-lower-case names)
+SYMBOLS_MIXED_CASE = ["fpx_gethourlyOH"]
 
 _lib = None
 
@@ -350,6 +359,12 @@ def load():
     lib.fpx_upload_wet_fields.argtypes = [vp, C.c_int32, C.POINTER(FpxWetFields)]
     lib.fpx_wetdepo.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
     lib.fpx_get_wetgrid.argtypes = [vp, vp, C.c_int32]
+    lib.fpx_oh_init.argtypes = [vp, C.POINTER(FpxOhConfig)]
+    lib.fpx_gethourlyOH.argtypes = [vp, C.c_int32]
+    lib.fpx_ohreaction.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    lib.fpx_get_oh_hourly.argtypes = [vp, vp, vp]
+    lib.fpx_set_oh_hourly.argtypes = [vp, vp, vp]
+    lib.fpx_ohreaction_time.argtypes = [vp, C.POINTER(C.c_double)]
     lib.fpx_comm_init_host.argtypes = [vp, C.c_int32, C.c_int32, ALLREDUCE_FN, vp]
     lib.fpx_set_release_heights.argtypes = [vp, C.c_int32, vp, vp]
     lib.fpx_count_particles.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]

@@ -33,6 +33,7 @@
 #include "fpx_calcfluxes.hpp"
 #include "fpx_partavg.hpp"
 #include "fpx_initcond.hpp"
+#include "fpx_ohreaction.hpp"
 #include "fpx_plumetraj.hpp"
 #include "fpx_domainfill.hpp"
 #include "fpx_convect.hpp"
@@ -143,6 +144,12 @@ struct EngineBase {
   virtual int upload_wet_nest_fields(int nest, int slot, const fpx_wet_fields *f, int readclouds_nest) = 0;
   virtual int wetdepo(int itime, int ltsample, int loutnext) = 0;
   virtual int get_wetgrid(void *wetgridunc, int allreduce) = 0;
+  virtual int oh_init(const fpx_oh_config *c) = 0;
+  virtual int gethourlyOH(int itime) = 0;
+  virtual int ohreaction(int itime, int ltsample, int loutnext) = 0;
+  virtual int get_oh_hourly(void *oh_hourly, void *memohtime) = 0;
+  virtual int set_oh_hourly(const void *oh_hourly, const void *memohtime) = 0;
+  virtual int ohreaction_ms(double *ms) = 0;
   virtual int outgrid_nest_init(const fpx_outgrid_nest *g) = 0;
   virtual int get_grids_nest(void *griduncn, void *drygriduncn, void *wetgriduncn, int allreduce, int clear) = 0;
   virtual int receptors_init(int n, const void *x, const void *y, const void *area) = 0;
@@ -2889,7 +2896,8 @@ struct Engine : EngineBase {
     h.reserved = cfg.device_flux && fx_flux ? kCkptFlux : 0;      // the flux section follows cbaseflux: a count and the values
     if (cfg.device_partavg) h.reserved |= kCkptPartavg;
     if (cfg.device_initcond && ic_grid) h.reserved |= kCkptInitcond;
-    h.total_bytes = ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h) + ckpt_initcond_bytes(h);
+    if (oh_on) h.reserved |= kCkptOh;
+    h.total_bytes = ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h) + ckpt_initcond_bytes(h) + ckpt_oh_bytes(h);
     if (fwrite(&h, sizeof(h), 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
     CkptRng rs{rng4, rng8, rel_ran1};
     if (fwrite(&rs, sizeof(rs), 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
@@ -2925,6 +2933,7 @@ struct Engine : EngineBase {
       if (fwrite(&cnt, 8, 1, fh) != 1) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
       if ((rc = ckpt_put_plain(fh, (const unsigned char *)ic_grid, n_initcond * cfg.host_real_bytes, buf))) return rc;
     }
+    if ((h.reserved & kCkptOh) && (rc = cfg.host_real_bytes == 4 ? ckpt_put_oh<float>(fh) : ckpt_put_oh<double>(fh))) return rc;
     if (closer.close() != 0) return fail(FPX_ERR_ARG, std::string("checkpoint_write: write error on ") + path);
     return 0;
   }
@@ -2955,14 +2964,17 @@ struct Engine : EngineBase {
         return fail(FPX_ERR_ARG, "checkpoint_read: written on another grid (nx, ny, nz, maxspec or the nest extents differ)");
       if (mine.pad != h.pad) return fail(FPX_ERR_ARG, "checkpoint_read: written with (without) DRYBKDEP / WETBKDEP");
       // the whole file must be there before a single array is touched
-      if ((h.reserved & ~(kCkptFlux | kCkptPartavg | kCkptInitcond)) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: unknown sections in the file");
+      if ((h.reserved & ~(kCkptFlux | kCkptPartavg | kCkptInitcond | kCkptOh)) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: unknown sections in the file");
       if (((h.reserved & kCkptInitcond) != 0) != (cfg.device_initcond && ic_grid))
         return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_initcond; create the engine alike and call fpx_outgrid_init first");
+      if (((h.reserved & kCkptOh) != 0) != oh_on)
+        return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) OH chemistry; call fpx_oh_init first (or not at all)");
       if (((h.reserved & kCkptPartavg) != 0) != (cfg.device_partavg != 0))
         return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_partavg; create the engine alike");
       if (((h.reserved & kCkptFlux) != 0) != (cfg.device_flux && fx_flux))
         return fail(FPX_ERR_STATE, "checkpoint_read: the checkpoint was written with (without) device_flux; create the engine alike and call fpx_outgrid_init first");
-      if (h.total_bytes != ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h) + ckpt_initcond_bytes(h)) return fail(FPX_ERR_ARG, "checkpoint_read: inconsistent header");
+      if (h.total_bytes != ckpt_total_bytes(h) + ckpt_flux_bytes(h) + ckpt_partavg_bytes(h) + ckpt_initcond_bytes(h) + ckpt_oh_bytes(h))
+        return fail((h.reserved & kCkptOh) ? FPX_ERR_STATE : FPX_ERR_ARG, (h.reserved & kCkptOh) ? "checkpoint_read: inconsistent header, or the OH grid of the checkpoint is not the one of fpx_oh_init" : "checkpoint_read: inconsistent header");
       if (fseek(fh, 0, SEEK_END) != 0) return fail(FPX_ERR_ARG, "checkpoint_read: cannot seek");
       const long long len = (long long)ftell(fh);
       if (len < 0 || (uint64_t)len != h.total_bytes)
@@ -3020,6 +3032,7 @@ struct Engine : EngineBase {
       if ((rc = ckpt_get_plain(fh, (unsigned char *)ic_grid, n_initcond * cfg.host_real_bytes, buf))) return ckpt_invalidate(rc);
       sum_ic.invalidate();                   // init_cond is the file's now
     }
+    if ((h.reserved & kCkptOh) && (rc = cfg.host_real_bytes == 4 ? ckpt_get_oh<float>(fh) : ckpt_get_oh<double>(fh))) return ckpt_invalidate(rc);
     invalidate_grid_sums();
     rng4 = rs.r4; rng8 = rs.r8; rel_ran1 = rs.rel;
     step_counter = h.step_counter;
@@ -3414,6 +3427,15 @@ struct Engine : EngineBase {
         HIPCHK(hipStreamSynchronize(stream));
       }
       *value = (int64_t)hc[0] + hc[1] + hc[2] + hc[3];
+    }
+    else if (n == "oh_branch") *value = oh_branch;
+    else if (n == "oh_skipped") {
+      unsigned int c = 0;
+      if (oh_on) {
+        HIPCHK(hipMemcpyAsync(&c, oh_d_skipped, sizeof(c), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+      }
+      *value = c;
     }
     else return fail(FPX_ERR_ARG, "fpx_get_info: unknown name: " + n);
     return 0;
@@ -4718,6 +4740,7 @@ struct Engine : EngineBase {
   int nest_nxmaxn = 0, nest_nymaxn = 0;
   bool nest_loaded[kMaxNests][2] = {};
   NestDesc<R> h_nest[kMaxNests] = {};   // host copy of the device table V.nest
+  double nest_geo[kMaxNests][6] = {};   // xln, yln, xrn, yrn, xresoln, yresoln as the host gave them (fpx_ohreaction compares in the host's kind)
   int nests_init(const fpx_nests *n) override {
     if (!n || n->struct_bytes != (int32_t)sizeof(fpx_nests)) return fail(FPX_ERR_ARG, "nests_init: null or fpx_nests size mismatch (ABI)");
     if (n->numbnests < 1 || n->numbnests > kMaxNests) return fail(FPX_ERR_ARG, "nests_init: numbnests out of range");
@@ -4732,6 +4755,7 @@ struct Engine : EngineBase {
       N.nx = n->nxn[l]; N.ny = n->nyn[l];
       N.xl = (R)n->xln[l]; N.yl = (R)n->yln[l]; N.xr = (R)n->xrn[l]; N.yr = (R)n->yrn[l];
       N.xres = (R)n->xresoln[l]; N.yres = (R)n->yresoln[l];
+      nest_geo[l][0] = n->xln[l]; nest_geo[l][1] = n->yln[l]; nest_geo[l][2] = n->xrn[l]; nest_geo[l][3] = n->yrn[l]; nest_geo[l][4] = n->xresoln[l]; nest_geo[l][5] = n->yresoln[l];
       const size_t ncol = (size_t)n->nxn[l] * n->nyn[l], nlev = ncol * cfg.nz;
       R *p;
       if ((rc = dalloc(&p, nlev * 6))) return rc; N.w3 = p;
@@ -4841,8 +4865,210 @@ struct Engine : EngineBase {
     return fetch({{&sum_wet, Gp.wetgridunc, wetgridunc, false, false}}, allreduce, "get_wetgrid");   // mpi_mod.f90:2486-2488, into wetgridunc0
   }
 
+  // ---- OH chemistry (fpx_ohreaction.hpp; gethourlyOH.f90, ohreaction.f90) --------------------------------------
+  // Nothing here exists before fpx_oh_init.  oh_mod lives on the host side in the host's real kind (oh4 or oh8), where
+  // gethourlyOH runs; the device holds the two hourly fields, their blend, the three axes and the counter of skipped particles.
+  oh::Hourly<float> oh4;
+  oh::Hourly<double> oh8;
+  bool oh_on = false, oh_have_hourly = false;
+  int oh_branch = -1;
+  void *oh_d_hourly = nullptr, *oh_d_blend = nullptr, *oh_d_axes = nullptr;
+  unsigned int *oh_d_skipped = nullptr;
+  double oh_cc[FPX_MAXSPEC] = {}, oh_dc[FPX_MAXSPEC] = {}, oh_nc[FPX_MAXSPEC] = {};
+  Events<2> oh_ev;
+  bool oh_timed = false, oh_ev_made = false;
+  oh::Hourly<float> &oh_state(float *) { return oh4; }
+  oh::Hourly<double> &oh_state(double *) { return oh8; }
+  template <typename H> oh::Hourly<H> &oh_state() { return oh_state((H *)nullptr); }
+  template <typename H>
+  int oh_init_t(const fpx_oh_config *c) {
+    oh::Hourly<H> &S = oh_state<H>();
+    S.nx = c->nxOH; S.ny = c->nyOH; S.nz = c->nzOH; S.ldirect = cfg.ldirect; S.bdate = c->bdate;
+    const size_t cells = S.cells();
+    auto take = [](std::vector<H> &v, const void *p, size_t n) { v.assign((const H *)p, (const H *)p + n); };
+    take(S.lon, c->lonOH, S.nx); take(S.lat, c->latOH, S.ny); take(S.alt, c->altOH, S.nz);
+    std::vector<H> axes((size_t)S.nx + S.ny + S.nz);
+    std::copy(S.lon.begin(), S.lon.end(), axes.begin());
+    std::copy(S.lat.begin(), S.lat.end(), axes.begin() + S.nx);
+    oh::alt_tops(S.alt.data(), S.nz, axes.data() + S.nx + S.ny);
+    const char *names[3] = {"lonOH", "latOH", "altOHtop (ohreaction.f90:114-117; its first nzOH-1 entries, the last repeats the one before)"};
+    const int lens[3] = {S.nx, S.ny, S.nz - 1}, offs[3] = {0, S.nx, S.nx + S.ny};
+    for (int a = 0; a < 3; a++)
+      if (const char *why = oh::check_axis(axes.data() + offs[a], lens[a]))
+        return fail(FPX_ERR_UNSUPPORTED, std::string("oh_init: ") + names[a] + " " + why + ": the nearest-index search of fpx_ohreaction bisects a strictly increasing axis");
+    take(S.field, c->OH_field, cells * 12); take(S.jr, c->jrate_average, (size_t)360 * 180 * 12);
+    take(S.lonjr, c->lonjr, 360); take(S.latjr, c->latjr, 180);
+    S.prepare();
+    int rc;
+    H *p;
+    if ((rc = dalloc(&p, cells * 2))) return rc; oh_d_hourly = p;
+    if ((rc = dalloc(&p, cells))) return rc; oh_d_blend = p;
+    if ((rc = dalloc(&p, axes.size()))) return rc; oh_d_axes = p;
+    if ((rc = dalloc(&oh_d_skipped, 1))) return rc;
+    HIPCHK(hipMemcpyAsync(oh_d_axes, axes.data(), axes.size() * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(oh_d_hourly, 0, cells * 2 * sizeof(H), stream));
+    HIPCHK(hipMemsetAsync(oh_d_skipped, 0, sizeof(unsigned int), stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  int oh_init(const fpx_oh_config *c) override {
+    if (!c || c->struct_bytes != (int32_t)sizeof(fpx_oh_config)) return fail(FPX_ERR_ARG, "oh_init: null or fpx_oh_config size mismatch (ABI)");
+    if (oh_on) return fail(FPX_ERR_STATE, "oh_init: already initialised");
+    if (!c->lonOH || !c->latOH || !c->altOH || !c->OH_field || !c->jrate_average || !c->lonjr || !c->latjr) return fail(FPX_ERR_ARG, "oh_init: lonOH, latOH, altOH, OH_field, jrate_average, lonjr, latjr are required");
+    if (c->nxOH < 1 || c->nyOH < 1 || c->nzOH < 2) return fail(FPX_ERR_ARG, "oh_init: nxOH, nyOH >= 1 and nzOH >= 2 are required (altOHtop, ohreaction.f90:114-117)");
+    if ((long long)c->nxOH * c->nyOH * c->nzOH > 0x7FFFFFF0ll) return fail(FPX_ERR_ARG, "oh_init: OH grid too large");
+    if (oh_lds_bytes(c->nxOH, c->nyOH, c->nzOH) > 48 * 1024) return fail(FPX_ERR_UNSUPPORTED, "oh_init: lonOH, latOH, altOHtop and height do not fit the 48 KB of LDS k_ohreaction stages them in");
+    for (int l = 0; l < V.numbnests; l++)
+      if (h_nest[l].nx > cfg.nx || h_nest[l].ny > cfg.ny)
+        return fail(FPX_ERR_UNSUPPORTED, "oh_init: a nest with nxn > nx or nyn > ny: ohreaction.f90:133 reads tt of the mother grid with the nest's indices, there beyond the field");
+    bool any = false;
+    for (int k = 0; k < cfg.nspec; k++) {
+      oh_cc[k] = c->ohcconst[k]; oh_dc[k] = c->ohdconst[k]; oh_nc[k] = c->ohnconst[k];
+      any = any || oh_cc[k] > 0.;
+    }
+    if (!any) return fail(FPX_ERR_ARG, "oh_init: no species has ohcconst > 0: there is no reaction to compute (readreleases.f90:377-380)");
+    const int rc = cfg.host_real_bytes == 4 ? oh_init_t<float>(c) : oh_init_t<double>(c);
+    if (rc) return rc;
+    oh_on = true;
+    return 0;
+  }
+  size_t oh_lds_bytes(int nxo, int nyo, int nzo) const { return ((size_t)nxo + nyo + nzo + 1) * cfg.host_real_bytes + (size_t)cfg.nz * sizeof(R); }
+  template <typename H>
+  int oh_upload(int first, int count) {      // fields first .. first + count - 1 of OH_hourly to the device
+    const oh::Hourly<H> &S = oh_state<H>();
+    HIPCHK(hipMemcpyAsync((H *)oh_d_hourly + (size_t)first * S.cells(), S.hourly.data() + (size_t)first * S.cells(), (size_t)count * S.cells() * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  template <typename H>
+  int gethourlyOH_t(int itime) {
+    oh::Hourly<H> &S = oh_state<H>();
+    oh_branch = S.step(itime);
+    if (oh_branch == oh::BR_ADVANCE) {     // OH_hourly(:,:,:,1) = OH_hourly(:,:,:,2) on the device too; the new field 2 is uploaded
+      HIPCHK(hipMemcpyAsync(oh_d_hourly, (const H *)oh_d_hourly + S.cells(), S.cells() * sizeof(H), hipMemcpyDeviceToDevice, stream));
+      return oh_upload<H>(1, 1);
+    }
+    if (oh_branch == oh::BR_INIT) return oh_upload<H>(0, 2);
+    return 0;
+  }
+  int gethourlyOH(int itime) override {
+    if (!oh_on) return fail(FPX_ERR_STATE, "gethourlyOH: fpx_oh_init first");
+    const int rc = cfg.host_real_bytes == 4 ? gethourlyOH_t<float>(itime) : gethourlyOH_t<double>(itime);
+    if (!rc) oh_have_hourly = true;
+    return rc;
+  }
+  template <typename H>
+  int oh_hourly_io(void *field, void *mt, bool set) {
+    oh::Hourly<H> &S = oh_state<H>();
+    if (set) {
+      if (field) std::copy((const H *)field, (const H *)field + 2 * S.cells(), S.hourly.begin());
+      if (mt) { S.memtime[0] = ((const H *)mt)[0]; S.memtime[1] = ((const H *)mt)[1]; }
+      return field ? oh_upload<H>(0, 2) : 0;
+    }
+    if (field) std::copy(S.hourly.begin(), S.hourly.end(), (H *)field);
+    if (mt) { ((H *)mt)[0] = S.memtime[0]; ((H *)mt)[1] = S.memtime[1]; }
+    return 0;
+  }
+  int get_oh_hourly(void *oh_hourly, void *memohtime) override {
+    if (!oh_on) return fail(FPX_ERR_STATE, "get_oh_hourly: fpx_oh_init first");
+    return cfg.host_real_bytes == 4 ? oh_hourly_io<float>(oh_hourly, memohtime, false) : oh_hourly_io<double>(oh_hourly, memohtime, false);
+  }
+  int set_oh_hourly(const void *oh_hourly, const void *memohtime) override {
+    if (!oh_on) return fail(FPX_ERR_STATE, "set_oh_hourly: fpx_oh_init first");
+    if (!oh_hourly || !memohtime) return fail(FPX_ERR_ARG, "set_oh_hourly: OH_hourly and memOHtime are required");
+    const int rc = cfg.host_real_bytes == 4 ? oh_hourly_io<float>((void *)oh_hourly, (void *)memohtime, true) : oh_hourly_io<double>((void *)oh_hourly, (void *)memohtime, true);
+    if (!rc) oh_have_hourly = true;
+    return rc;
+  }
+  template <typename H>
+  int ohreaction_t(int itime, int ltsample) {
+#pragma clang fp contract(off)
+    const oh::Hourly<H> &S = oh_state<H>();
+    if (S.memtime[1] == S.memtime[0]) return fail(FPX_ERR_STATE, "ohreaction: memOHtime(1) == memOHtime(2)");
+    // n of ohreaction.f90:85-87: nint(itime - 0.5*ltsample) in the default kind, the slot itself (not memind(n))
+    const long long interp_time = (long long)std::llround((H)itime - (H)0.5 * (H)ltsample);
+    const int slot = std::llabs((long long)V.memtime0 - interp_time) < std::llabs((long long)V.memtime1 - interp_time) ? 0 : 1;
+    if (!diag_have[DG_TT + slot]) return fail(FPX_ERR_STATE, std::string("ohreaction: tt of time slot ") + (slot ? "2" : "1") + " is not on the device (fpx_upload_diag_fields or a transform); ohreaction.f90:85-87,133 reads that slot, not memind's");
+    oh::Args<H> A;
+    memset(&A, 0, sizeof(A));
+    A.nxOH = S.nx; A.nyOH = S.ny; A.nzOH = S.nz; A.nztop = S.nz - 1;
+    A.lon = (const H *)oh_d_axes; A.lat = A.lon + S.nx; A.alttop = A.lat + S.ny;
+    A.oh = (const H *)oh_d_blend;
+    A.d3 = (const H *)diag_d3;
+    A.nx = cfg.nx; A.ny = cfg.ny; A.nz = cfg.nz;
+    A.slot = slot;
+    A.dx = (H)cfg.dx; A.dy = (H)cfg.dy; A.xlon0 = (H)cfg.xlon0; A.ylat0 = (H)cfg.ylat0;
+    A.numbnests = V.numbnests;
+    for (int l = 0; l < V.numbnests; l++) {
+      A.xl[l] = (H)nest_geo[l][0]; A.yl[l] = (H)nest_geo[l][1]; A.xr[l] = (H)nest_geo[l][2]; A.yr[l] = (H)nest_geo[l][3];
+      A.xres[l] = (H)nest_geo[l][4]; A.yres[l] = (H)nest_geo[l][5];
+    }
+    for (int k = 0; k < cfg.nspec; k++)
+      if (oh_cc[k] > 0.) { A.spec[A.nreact] = k; A.cc[A.nreact] = (H)oh_cc[k]; A.dc[A.nreact] = (H)oh_dc[k]; A.nc[A.nreact] = (H)oh_nc[k]; A.nreact++; }
+    A.tl = (H)std::abs(ltsample);
+    A.small = (H)std::numeric_limits<R>::min();
+    A.skipped = oh_d_skipped;
+    const H tnum = (H)itime - S.memtime[0], tden = S.memtime[1] - S.memtime[0];
+    if (!oh_ev_made) { HIPCHK(oh_ev.create()); oh_ev_made = true; }
+    oh_timed = false;
+    HIPCHK(hipMemsetAsync(oh_d_skipped, 0, sizeof(unsigned int), stream));
+    HIPCHK(hipEventRecord(oh_ev[0], stream));
+    const long long cells = (long long)S.cells();
+    oh::k_oh_blend<H><<<(int)((cells + 255) / 256), 256, 0, stream>>>((const H *)oh_d_hourly, (const H *)oh_d_hourly + cells, tnum, tden, (H *)oh_d_blend, cells);
+    HIPCHK(hipGetLastError());
+    if (numpart > 0) {
+      oh::k_ohreaction<R, H><<<(int)((numpart + 255) / 256), 256, oh_lds_bytes(S.nx, S.ny, S.nz), stream>>>(A, P, V.height, numpart);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(oh_ev[1], stream));
+    oh_timed = true;
+    return 0;
+  }
+  int ohreaction(int itime, int ltsample, int loutnext) override {
+    (void)loutnext;                        // ldeltat of ohreaction.f90:47-51 is never read
+    if (!oh_on) return fail(FPX_ERR_STATE, "ohreaction: fpx_oh_init first");
+    if (!oh_have_hourly) return fail(FPX_ERR_STATE, "ohreaction: no hourly OH fields yet (fpx_gethourlyOH or fpx_set_oh_hourly first)");
+    if (!height_set || !window_set) return fail(FPX_ERR_STATE, "ohreaction: height / wind-time window not set");
+    return cfg.host_real_bytes == 4 ? ohreaction_t<float>(itime, ltsample) : ohreaction_t<double>(itime, ltsample);
+  }
+  int ohreaction_ms(double *ms) override {
+    *ms = 0.;
+    if (!oh_timed) return 0;
+    float t = 0;
+    HIPCHK(hipEventSynchronize(oh_ev[1]));
+    HIPCHK(hipEventElapsedTime(&t, oh_ev[0], oh_ev[1]));
+    *ms = t;
+    return 0;
+  }
+  // checkpoint, bit 3 of header.reserved: last, what gethourlyOH carries from hour to hour -- it cannot be recomputed from itime
+  // (the first call's memOHtime(1) = 0 and its date): uint64 cells of the OH grid, int32 whether hourly fields exist, int32 0,
+  // memOHtime(2) and OH_hourly(nxOH,nyOH,nzOH,2) in the host's real kind
+  static constexpr int32_t kCkptOh = 8;
+  uint64_t oh_cells() const { return cfg.host_real_bytes == 4 ? oh4.cells() : oh8.cells(); }
+  uint64_t ckpt_oh_bytes(const CkptHeader &h) const { return (h.reserved & kCkptOh) ? 16 + (2 + 2 * oh_cells()) * (uint64_t)cfg.host_real_bytes : 0; }
+  template <typename H>
+  int ckpt_put_oh(FILE *fh) {
+    const oh::Hourly<H> &S = oh_state<H>();
+    const uint64_t cnt = S.cells();
+    const int32_t have[2] = {oh_have_hourly ? 1 : 0, 0};
+    if (fwrite(&cnt, 8, 1, fh) != 1 || fwrite(have, 4, 2, fh) != 2 || fwrite(S.memtime, sizeof(H), 2, fh) != 2 ||
+        fwrite(S.hourly.data(), sizeof(H), S.hourly.size(), fh) != S.hourly.size()) return fail(FPX_ERR_ARG, "checkpoint_write: write error");
+    return 0;
+  }
+  template <typename H>
+  int ckpt_get_oh(FILE *fh) {
+    oh::Hourly<H> &S = oh_state<H>();
+    uint64_t cnt = 0;
+    int32_t have[2] = {0, 0};
+    if (fread(&cnt, 8, 1, fh) != 1 || cnt != S.cells() || fread(have, 4, 2, fh) != 2 || fread(S.memtime, sizeof(H), 2, fh) != 2 ||
+        fread(S.hourly.data(), sizeof(H), S.hourly.size(), fh) != S.hourly.size()) return fail(FPX_ERR_ARG, "checkpoint_read: the OH section is short or of another OH grid");
+    oh_have_hourly = have[0] != 0;
+    return oh_upload<H>(0, 2);
+  }
+
   void *stream_ptr() override { return (void *)stream; }
 };
+
 
 FPX_TU_CLOSE
 #if FPX_TU_REAL != 8
@@ -5128,6 +5354,12 @@ int fpx_wet_init(fpx_handle h, const fpx_wet_config *w) { FPX_GUARD(h); return h
 int fpx_upload_wet_fields(fpx_handle h, int32_t slot, const fpx_wet_fields *f) { FPX_GUARD(h); return h->impl->upload_wet_fields(slot, f); }
 int fpx_wetdepo(fpx_handle h, int32_t itime, int32_t ltsample, int32_t loutnext) { FPX_GUARD(h); return h->impl->wetdepo(itime, ltsample, loutnext); }
 int fpx_get_wetgrid(fpx_handle h, void *wetgridunc, int32_t allreduce) { FPX_GUARD(h); return h->impl->get_wetgrid(wetgridunc, allreduce); }
+int fpx_oh_init(fpx_handle h, const fpx_oh_config *c) { FPX_GUARD(h); return h->impl->oh_init(c); }
+int fpx_gethourlyOH(fpx_handle h, int32_t itime) { FPX_GUARD(h); return h->impl->gethourlyOH(itime); }
+int fpx_ohreaction(fpx_handle h, int32_t itime, int32_t ltsample, int32_t loutnext) { FPX_GUARD(h); return h->impl->ohreaction(itime, ltsample, loutnext); }
+int fpx_get_oh_hourly(fpx_handle h, void *OH_hourly_out, void *memOHtime_out) { FPX_GUARD(h); return h->impl->get_oh_hourly(OH_hourly_out, memOHtime_out); }
+int fpx_set_oh_hourly(fpx_handle h, const void *OH_hourly, const void *memOHtime) { FPX_GUARD(h); return h->impl->set_oh_hourly(OH_hourly, memOHtime); }
+int fpx_ohreaction_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return fpx::fail(FPX_ERR_ARG, "fpx_ohreaction_time: null"); return h->impl->ohreaction_ms(ms); }
 void *fpx_stream(fpx_handle h) { return (h && h->impl) ? h->impl->stream_ptr() : nullptr; }
 int fpx_upload_wet_nest_fields(fpx_handle h, int32_t nest, int32_t slot, const fpx_wet_fields *f, int32_t readclouds_nest) { FPX_GUARD(h); return h->impl->upload_wet_nest_fields(nest, slot, f, readclouds_nest); }
 int fpx_outgrid_nest_init(fpx_handle h, const fpx_outgrid_nest *g) { FPX_GUARD(h); return h->impl->outgrid_nest_init(g); }
@@ -5136,9 +5368,9 @@ int fpx_receptors_init(fpx_handle h, int32_t numreceptor, const void *xreceptor,
 int fpx_get_receptors(fpx_handle h, void *creceptor, int32_t ld, int32_t allreduce, int32_t clear) { FPX_GUARD(h); return h->impl->get_receptors(creceptor, ld, allreduce, clear); }
 
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n) {
-  if (fn < 0 || fn > 33 || !x || !y || n < 0) return FPX_ERR_ARG;
+  if (fn < 0 || (fn > 33 && fn < 40) || fn > 43 || !x || !y || n < 0) return FPX_ERR_ARG;
   if (n == 0) return FPX_OK;
-  const int64_t nin = (fn == 12 || fn == 13) ? 2 * n : n;   // fn 12, 13: x[0 .. n) the points, x[n .. 2n) their exp(-x*x)
+  const int64_t nin = (fn == 12 || fn == 13 || fn == 42 || fn == 43) ? 2 * n : n;   // fn 12, 13: x[0 .. n) the points, x[n .. 2n) their exp(-x*x); 42, 43: the exponents
   fpx::Scratch bx, by;
   if (bx.reserve(nin * sizeof(double), nullptr) != hipSuccess || by.reserve(n * sizeof(double), nullptr) != hipSuccess) return FPX_ERR_NOMEM;
   double *dx = bx.as<double>(), *dy = by.as<double>();

@@ -50,6 +50,11 @@ __global__ void k_math_probe(int fn, const double *__restrict__ x, double *__res
     case 30: r = m_divf(3.0, v); break;
     case 32: r = m_exp_tab<256, 4>(v, &kExpTab256[0]); break;             // the 256-entry pair of 9 and 14 (the fp64 gas kernels' exponential)
     case 33: r = m_exp_tab_nh<256, 4>(v, &kExpTab256[0]); break;
+    // 40 .. 43: the device library's exp and pow as k_ohreaction calls them (fpx_ohreaction.hpp); pow of (x[i], x[n + i])
+    case 40: r = exp(v); break;
+    case 41: r = (double)expf((float)v); break;
+    case 42: r = pow(v, x[n + i]); break;
+    case 43: r = (double)powf((float)v, (float)x[n + i]); break;
     default: m_cuberoot_parts(v, c, ic2); r = ic2; break;
   }
   y[i] = r;

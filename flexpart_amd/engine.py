@@ -1164,6 +1164,62 @@ class Engine:
             loutnext = int(self.sc["outtimes"][0]) if "outtimes" in self.sc else 0
         check(self.lib.fpx_wetdepo(self.h, int(itime), int(ltsample), int(loutnext)), "fpx_wetdepo")
 
+    # ---- OH chemistry (gethourlyOH.f90, ohreaction.f90) -------------------------
+    def oh_init(self, c, struct_bytes=None):
+        """fpx_oh_init from the oh_mod arrays of a case (flexpart_amd.synthetic.oh_case): lonOH, latOH, altOH, OH_field
+        [12][nzOH][nyOH][nxOH], jrate_average [12][180][360], lonjr, latjr, bdate, ohcconst, ohdconst, ohnconst."""
+        from ._lib import FpxOhConfig
+        rt = self.hreal
+        keep = {k: np.ascontiguousarray(np.asarray(c[k]).astype(rt)) for k in ("lonOH", "latOH", "altOH", "OH_field", "jrate_average", "lonjr", "latjr")}
+        o = FpxOhConfig()
+        o.struct_bytes = C.sizeof(FpxOhConfig) if struct_bytes is None else int(struct_bytes)
+        o.nxOH, o.nyOH, o.nzOH = keep["lonOH"].size, keep["latOH"].size, keep["altOH"].size
+        assert keep["OH_field"].size == 12 * o.nxOH * o.nyOH * o.nzOH and keep["jrate_average"].size == 12 * 180 * 360
+        for k, a in keep.items():
+            setattr(o, k, a.ctypes.data)
+        o.bdate = float(c["bdate"])
+        for i in range(self.nspec):
+            o.ohcconst[i], o.ohdconst[i], o.ohnconst[i] = float(c["ohcconst"][i]), float(c["ohdconst"][i]), float(c["ohnconst"][i])
+        check(self.lib.fpx_oh_init(self.h, C.byref(o)), "fpx_oh_init")
+        self._oh_shape = (2, o.nzOH, o.nyOH, o.nxOH)
+
+    def upload_tt(self, tt, slots=(1, 2)):
+        """tt [2][nz][ny][nx] (compact) of the given time slots -> fpx_upload_diag_fields with tt alone (what fpx_ohreaction reads)."""
+        from ._lib import FpxDiagFields
+        for m in slots:
+            f = FpxDiagFields()
+            t = self._host3(np.asarray(tt), m - 1)
+            f.tt = t.ctypes.data
+            check(self.lib.fpx_upload_diag_fields(self.h, int(m), C.byref(f)), "fpx_upload_diag_fields")
+
+    def gethourlyOH(self, itime=None):
+        """call gethourlyOH(itime), timemanager.f90:212-216 -> the branch taken (0 nothing, 1 advanced, 2 both fields computed)."""
+        check(self.lib.fpx_gethourlyOH(self.h, self.itime if itime is None else int(itime)), "fpx_gethourlyOH")
+        return self.info("oh_branch")
+
+    def ohreaction(self, itime=None, ltsample=None, loutnext=0):
+        """call ohreaction(itime, lsynctime, loutnext), timemanager.f90:171-172."""
+        check(self.lib.fpx_ohreaction(self.h, self.itime if itime is None else int(itime),
+                                      self.lsynctime if ltsample is None else int(ltsample), int(loutnext)), "fpx_ohreaction")
+
+    def get_oh_hourly(self):
+        """(OH_hourly [2][nzOH][nyOH][nxOH], memOHtime [2]) in the host's real kind."""
+        f, t = np.empty(self._oh_shape, self.hreal), np.empty(2, self.hreal)
+        check(self.lib.fpx_get_oh_hourly(self.h, _vp(f), _vp(t)), "fpx_get_oh_hourly")
+        return f, t
+
+    def set_oh_hourly(self, oh_hourly, memohtime):
+        f = np.ascontiguousarray(np.asarray(oh_hourly).astype(self.hreal))
+        t = np.ascontiguousarray(np.asarray(memohtime).astype(self.hreal))
+        assert f.shape == self._oh_shape and t.size == 2
+        check(self.lib.fpx_set_oh_hourly(self.h, _vp(f), _vp(t)), "fpx_set_oh_hourly")
+
+    def ohreaction_time(self):
+        """Device time (ms) of k_oh_blend + k_ohreaction of the last ohreaction()."""
+        ms = C.c_double()
+        check(self.lib.fpx_ohreaction_time(self.h, C.byref(ms)), "fpx_ohreaction_time")
+        return ms.value
+
     def wetgrid(self, allreduce=False):
         na, nc, mp, nsp, nzg, nyg, nxg = self.gshape
         d = np.empty((na, nc, mp, nsp, nyg, nxg), np.float32)

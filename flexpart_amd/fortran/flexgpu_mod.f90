@@ -34,6 +34,7 @@ module flexgpu_mod
             flexgpu_step, flexgpu_use_table_rng, flexgpu_handle, flexgpu_last_error, &
             flexgpu_outgrid_init, flexgpu_conccalc, flexgpu_get_grids, &
             flexgpu_wet_init, flexgpu_upload_wet_fields, flexgpu_wetdepo, flexgpu_verttransform, &
+            flexgpu_oh_init, flexgpu_gethourlyOH, flexgpu_ohreaction, flexgpu_get_oh_hourly, &
             flexgpu_upload_diag_fields, flexgpu_partoutput, flexgpu_readpartpositions, &
             flexgpu_partoutput_average, flexgpu_get_partavg, &
             flexgpu_initcond_finish, flexgpu_get_initcond, flexgpu_initial_cond_output, &
@@ -614,6 +615,13 @@ module flexgpu_mod
     real(c_double) :: dxoutn, dyoutn, xoutshiftn, youtshiftn
     integer(c_int32_t) :: reserved(4)
   end type
+  type, bind(C) :: fpx_oh_config
+    integer(c_int32_t) :: struct_bytes
+    integer(c_int32_t) :: nxOH, nyOH, nzOH
+    type(c_ptr) :: lonOH, latOH, altOH, OH_field, jrate_average, lonjr, latjr
+    real(c_double) :: bdate
+    real(c_double) :: ohcconst(FPX_MAXSPEC), ohdconst(FPX_MAXSPEC), ohnconst(FPX_MAXSPEC)
+  end type
   type, bind(C) :: fpx_wet_config
     integer(c_int32_t) :: struct_bytes
     integer(c_int32_t) :: wetdepspec(FPX_MAXSPEC)
@@ -717,6 +725,25 @@ module flexgpu_mod
       type(c_ptr), value :: h
       integer(c_int32_t), value :: nest, slot, rc
       type(fpx_wet_fields), intent(in) :: f
+    end function
+    integer(c_int) function fpx_oh_init(h, c) bind(C, name='fpx_oh_init')
+      import :: c_ptr, c_int, fpx_oh_config
+      type(c_ptr), value :: h
+      type(fpx_oh_config), intent(in) :: c
+    end function
+    integer(c_int) function fpx_gethourlyOH(h, itime) bind(C, name='fpx_gethourlyOH')
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: itime
+    end function
+    integer(c_int) function fpx_ohreaction(h, itime, ltsample, loutnext) bind(C, name='fpx_ohreaction')
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: itime, ltsample, loutnext
+    end function
+    integer(c_int) function fpx_get_oh_hourly(h, oh_hourly, memohtime) bind(C, name='fpx_get_oh_hourly')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, oh_hourly, memohtime
     end function
     integer(c_int) function fpx_wetdepo(h, itime, ltsample, loutnext) bind(C, name='fpx_wetdepo')
       import :: c_ptr, c_int, c_int32_t
@@ -1900,5 +1927,49 @@ contains
     integer, intent(out) :: ierr
     ierr = fpx_wetdepo(flexgpu_handle, int(itime, c_int32_t), int(ltsample, c_int32_t), int(loutnext, c_int32_t))
   end subroutine flexgpu_wetdepo
+
+  ! ---- OH chemistry.  The wrappers take the arrays of oh_mod as arguments (the module itself is not used here: a host
+  ! without OH fields links without it). ----
+  ! once, after "call readOHfield" (FLEXPART.f90:348-353): hands oh_mod over
+  subroutine flexgpu_oh_init(nxOH, nyOH, nzOH, lonOH, latOH, altOH, OH_field, jrate_average, lonjr, latjr, ierr)
+    integer, intent(in) :: nxOH, nyOH, nzOH
+    real, intent(in), target :: lonOH(nxOH), latOH(nyOH), altOH(nzOH), OH_field(nxOH,nyOH,nzOH,12)
+    real, intent(in), target :: jrate_average(360,180,12), lonjr(360), latjr(180)
+    integer, intent(out) :: ierr
+    type(fpx_oh_config) :: c
+    integer :: ks
+    c%struct_bytes = int(c_sizeof(c), c_int32_t)
+    c%nxOH = nxOH; c%nyOH = nyOH; c%nzOH = nzOH
+    c%lonOH = c_loc(lonOH); c%latOH = c_loc(latOH); c%altOH = c_loc(altOH); c%OH_field = c_loc(OH_field)
+    c%jrate_average = c_loc(jrate_average); c%lonjr = c_loc(lonjr); c%latjr = c_loc(latjr)
+    c%bdate = bdate
+    c%ohcconst = 0; c%ohdconst = 0; c%ohnconst = 0
+    do ks = 1, min(nspec, FPX_MAXSPEC)
+      c%ohcconst(ks) = real(ohcconst(ks), c_double); c%ohdconst(ks) = real(ohdconst(ks), c_double); c%ohnconst(ks) = real(ohnconst(ks), c_double)
+    end do
+    ierr = fpx_oh_init(flexgpu_handle, c)
+  end subroutine flexgpu_oh_init
+
+  ! replaces "call gethourlyOH(itime)" (timemanager.f90:212-216)
+  subroutine flexgpu_gethourlyOH(itime, ierr)
+    integer, intent(in) :: itime
+    integer, intent(out) :: ierr
+    ierr = fpx_gethourlyOH(flexgpu_handle, int(itime, c_int32_t))
+  end subroutine flexgpu_gethourlyOH
+
+  ! replaces "call ohreaction(itime,lsynctime,loutnext)" (timemanager.f90:171-172)
+  subroutine flexgpu_ohreaction(itime, ltsample, loutnext, ierr)
+    integer, intent(in) :: itime, ltsample, loutnext
+    integer, intent(out) :: ierr
+    ierr = fpx_ohreaction(flexgpu_handle, int(itime, c_int32_t), int(ltsample, c_int32_t), int(loutnext, c_int32_t))
+  end subroutine flexgpu_ohreaction
+
+  ! OH_hourly and memOHtime of oh_mod as the engine holds them (diagnostics; the run does not need it)
+  subroutine flexgpu_get_oh_hourly(nxOH, nyOH, nzOH, OH_hourly, memOHtime, ierr)
+    integer, intent(in) :: nxOH, nyOH, nzOH
+    real, intent(out), target :: OH_hourly(nxOH,nyOH,nzOH,2), memOHtime(2)
+    integer, intent(out) :: ierr
+    ierr = fpx_get_oh_hourly(flexgpu_handle, c_loc(OH_hourly), c_loc(memOHtime))
+  end subroutine flexgpu_get_oh_hourly
 
 end module flexgpu_mod

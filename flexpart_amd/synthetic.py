@@ -1503,3 +1503,86 @@ def domainfill_case(name="fill1"):
               itrasplit=np.full(n, 7200, np.int32), xmass1=((1.0 + (h % np.uint64(64)).astype(np.float64)) * 1.0e10)[None, :],
               numpart=190 if name != "full" else 200, numparticlecount=n)
     return sc
+
+
+OH_DIRECTIONS = (1, -1)
+OH_PAD = (3, 2, 1)                                   # nxmax - nx, nymax - ny, nzmax - nz of the host's arrays
+OH_HOT, OH_WARM = (8, 3, 2), (7, 4, 2)               # (OHx, OHy, OHz), 0-based: the cells of the two special particles
+
+
+def oh_case(ldirect=1):
+    """Inputs for the reference's gethourlyOH and ohreaction, from integer patterns, hashes and IEEE-exact operations only,
+    so that the tests regenerate the fixture's inputs bit for bit.
+    Mother grid 12 x 10 x 8, dx 15, dy 6 from (30, -30): longitudes 30 .. 195, so the wrap of ohreaction.f90:102-104 is taken
+    east of 180.  One nest of 8 x 6 columns at half the spacing from (60, -12): mother x 2 .. 5.5, y 3 .. 5.5.  OH grid
+    9 x 7 x 4: lonOH -180 .. 180 by 45, latOH -45 .. 45 by 15, altOH 500, 2000, 5000, 10000 m -- altOHtop 2750, 6500, 12500,
+    12500: the last two are always equal in the reference (:114-117), so minloc never picks level nzOH.  bdate is 31 January
+    2020 23:10 (ldirect = 1; 1 February 00:10 for ldirect = -1): the second hourly field lies in the other month, and the sun
+    stands over 190 E: the OH columns at 45 E and 90 E are dark (OH exactly 0), those from 135 E eastwards are lit.
+    jrate_average is <= 0 where the OH columns (135 E, -30 N) and (180 E, -15 N) look.  tt differs by at least 8 K between
+    neighbouring cells in every direction and between the slots; OH_field by more than 4 %.
+    837 storage spaces (three blocks of 256, one wave, five lanes): 60 dead with in-domain positions, 270 inside the nest;
+    z below 9000 m (OH levels 1, 2) except two special particles at 11000 m (level 3): space 5 in the cell OH_HOT whose OH is
+    3e4 times the pattern's (ohrate |ltsample| > 800: exp underflows to 0), space 6 in OH_WARM (300 or 175 times: the factor is near
+    0.1) with a mass of 4 tiny in species 1, which oh_masses() sets per real kind.
+    Species 1: ohnconst 2.0, ohdconst 1200; species 2: ohcconst -9.99 (never touched); species 3: ohnconst 1.5, ohdconst -300.
+    calls: the sequence of the time manager -- gethourlyOH(0), ohreaction in the first hour, gethourlyOH at the hour (advance),
+    again inside it (nothing), ohreaction with memind = (2, 1): n of ohreaction.f90:85-87 is 1 in the first and 2 in the second
+    ohreaction, whatever memind says."""
+    if ldirect not in OH_DIRECTIONS:
+        raise ValueError(ldirect)
+    nx, ny, nz, n = 12, 10, 8, 837
+    nxo, nyo, nzo = 9, 7, 4
+    ld = int(ldirect)
+    c = dict(grid=np.array([nx, ny, nz], np.int32), pad=OH_PAD, geom=np.array([15.0, 6.0, 30.0, -30.0], np.float64),
+             height=make_height(nz, top=30000.0, lin=0.15), nest=(8, 6), nestgeom=(7.5, 3.0, 60.0, -12.0),
+             ohgrid=np.array([nxo, nyo, nzo], np.int32), ldirect=ld, nspec=3, npart=n,
+             lonOH=-180.0 + 45.0 * np.arange(nxo), latOH=-45.0 + 15.0 * np.arange(nyo), altOH=np.array([500.0, 2000.0, 5000.0, 10000.0]),
+             lonjr=-179.5 + np.arange(360.0), latjr=-89.5 + np.arange(180.0),
+             bdate=GV_BDATE + 16.0 + (23.0 * 3600.0 + 600.0) / 86400.0 if ld == 1 else GV_BDATE + 17.0 + 600.0 / 86400.0,
+             ohcconst=np.array([1.0e-13, -9.99, 1.0e-14]), ohdconst=np.array([1200.0, -9.99, -300.0]), ohnconst=np.array([2.0, -9.99, 1.5]))
+    m, k, j, i = np.meshgrid(np.arange(12), np.arange(nzo), np.arange(nyo), np.arange(nxo), indexing="ij")
+    f = 1.0e6 * (1.0 + ((i * 5 + j * 3 + k * 7 + m * 2) % 11).astype(np.float64) / 16.0)
+    f[:, OH_HOT[2], OH_HOT[1], OH_HOT[0]] *= 3.0e4
+    f[:, OH_WARM[2], OH_WARM[1], OH_WARM[0]] *= 300.0 if ld == 1 else 175.0     # ohrate |ltsample| = 2.3 in the first ohreaction
+    c["OH_field"] = f                                               # [12][nzOH][nyOH][nxOH] = Fortran (ix,jy,kz,m)
+    m, j, i = np.meshgrid(np.arange(12), np.arange(180), np.arange(360), indexing="ij")
+    jr = 2.0e-5 * (1.0 + ((i + 2 * j + 5 * m) % 16).astype(np.float64) / 32.0)
+    jr[:, 59, 314] = -1.0                                           # the picks of lonOH = 135 (a tie: the first, 134.5), latOH = -30 (-30.5)
+    jr[:, 74, 359] = 0.0                                            # lonOH = 180 (179.5), latOH = -15 (-15.5)
+    c["jrate_average"] = jr                                         # [12][180][360]
+    m, k, j, i = np.meshgrid(np.arange(2), np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    c["tt"] = 200.0 + 8.0 * ((i * 7 + j * 13 + k * 29 + m * 17) % 12).astype(np.float64)   # [2][nz][ny][nx]
+    s = 7700 + (0 if ld == 1 else 50)
+    u, v, w = _uniform01(n, s + 1), _uniform01(n, s + 2), _uniform01(n, s + 3)
+    xt = 0.03 + 10.94 * u
+    yt = 0.03 + 8.94 * v
+    idx = np.arange(n)
+    inn = idx % 3 == 1                                              # into the nest: x 2 .. 5.5, y 3 .. 5.5
+    inn[-9:] = False
+    xt[inn] = 2.02 + 3.46 * u[inn]
+    yt[inn] = 3.02 + 2.46 * v[inn]
+    zt = 50.0 + 8900.0 * w * w
+    # the special particles: lon 180 = x 10, lat 0 = y 5 (OH_HOT); lon 135 = x 7, lat 15 = y 7.5 (OH_WARM)
+    xt[5], yt[5], zt[5] = 9.9, 5.1, 11000.0
+    xt[6], yt[6], zt[6] = 7.1, 7.4, 11000.0
+    h = _splitmix64(n, s + 4)
+    mass = np.empty((3, n), np.float64)
+    mass[0] = (1.0 + (h % np.uint64(1000)).astype(np.float64)) / 3000.0
+    mass[1] = (1.0 + ((h >> np.uint64(16)) % np.uint64(1000)).astype(np.float64)) / 7000.0
+    mass[2] = (1.0 + ((h >> np.uint64(32)) % np.uint64(1000)).astype(np.float64)) * 1.0e9
+    itra1 = np.zeros(n, np.int32)
+    dead = np.nonzero((idx % 14 == 9) & (idx > 6))[0][:60]
+    itra1[dead] = DEAD
+    c.update(xtra1=xt, ytra1=yt, ztra1=zt, xmass1=mass, itra1=itra1, tiny_particle=6, hot_particle=5)
+    c["calls"] = (("hourly", 0), ("react", 900 * ld, 900 * ld, (0, 10800 * ld), (1, 2)), ("hourly", 3600 * ld), ("hourly", 4500 * ld),
+                  ("react", 6300 * ld, 900 * ld, (0, 10800 * ld), (2, 1)))
+    return c
+
+
+def oh_masses(c, kind):
+    """xmass1 [3][n] of oh_case() in the real kind ('r4' | 'r8'), with the mass of 4 tiny(0.0) of that kind in place."""
+    rt = np.float32 if kind == "r4" else np.float64
+    m = np.asarray(c["xmass1"]).astype(rt)
+    m[0, int(c["tiny_particle"])] = rt(4.0) * np.finfo(rt).tiny
+    return m

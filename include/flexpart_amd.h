@@ -941,6 +941,47 @@ int fpx_wetdepo(fpx_handle h, int32_t itime, int32_t ltsample, int32_t loutnext)
  * mpi_mod.f90:2486-2488).  Never cleared: it accumulates over the run. */
 int fpx_get_wetgrid(fpx_handle h, void *wetgridunc, int32_t allreduce);
 
+/* ---- OH chemistry (ohreaction; species with ohcconst > 0, readreleases.f90:377-380) ---- */
+/* What readOHfield (FLEXPART.f90:348-353, readOHfield.f90:44-75) leaves in oh_mod, handed over once; the host keeps reading the
+ * file.  The arrays are in the host's real kind: lonOH(nxOH), latOH(nyOH), altOH(nzOH), OH_field(nxOH,nyOH,nzOH,12),
+ * jrate_average(360,180,12), lonjr(360), latjr(180) (oh_mod.f90:11-18).  bdate: com_mod.f90:117.  ohcconst, ohdconst, ohnconst:
+ * com_mod.f90:180 of the species 1..nspec as doubles (exact both ways); a species reacts when ohcconst > 0. */
+typedef struct {
+  int32_t struct_bytes;
+  int32_t nxOH, nyOH, nzOH;
+  const void *lonOH, *latOH, *altOH, *OH_field, *jrate_average, *lonjr, *latjr;
+  double bdate;
+  double ohcconst[FPX_MAXSPEC], ohdconst[FPX_MAXSPEC], ohnconst[FPX_MAXSPEC];
+} fpx_oh_config;
+/* Once per handle, after fpx_nests_init if the run has nests.  A handle that never calls it allocates nothing and launches
+ * exactly what it launched before.  FPX_ERR_ARG: wrong struct_bytes, null arrays, nzOH < 2.  FPX_ERR_UNSUPPORTED: lonOH, latOH
+ * or altOHtop (ohreaction.f90:114-117) not strictly increasing, or with a spacing of no more than four units in the last place
+ * of the array's largest value (the nearest-index search of fpx_ohreaction bisects); a nest with nxn > nx or nyn > ny (the
+ * reference reads tt of the mother grid with the nest's indices, ohreaction.f90:133, there beyond the field). */
+int fpx_oh_init(fpx_handle h, const fpx_oh_config *c);
+/* call gethourlyOH(itime), timemanager.f90:212-216 = gethourlyOH.f90:40-142 with zenithangle.f90, photo_O1D.f90, caldate.f90:
+ * on the engine's host side in the host's real kind with libm, OH_hourly and memOHtime bit for bit; the new field is uploaded.
+ * The reference's quirks are kept: the first call sets memOHtime(1) = 0 whatever itime is and forms the second date as
+ * bdate + ldirect*real(1./24., dp) (:104), later calls bdate + memOHtime(2)/86400._dp (:61); a call advances the pair by at
+ * most one hour. */
+int fpx_gethourlyOH(fpx_handle h, int32_t itime);
+/* call ohreaction(itime, lsynctime, loutnext), timemanager.f90:171-172 = ohreaction.f90:47-153, for the storage spaces
+ * 1..numpart: xmass1 of every species with ohcconst > 0 is replaced.  Needs fpx_gethourlyOH (or fpx_set_oh_hourly), height,
+ * the wind-time window and tt of the slot n of ohreaction.f90:85-87 (fpx_upload_diag_fields or a transform) -- n is used as
+ * the slot itself, not through memind, and inside a nest tt of the MOTHER grid is read with the nest's indices (:133): both as
+ * the reference has them.  Deviations: terminated spaces (itra1 = FPX_DEAD), whose mass nobody reads, are skipped; where no
+ * level lies above the particle the level is nz-1 (the reference keeps the previous particle's); a live particle outside the
+ * mother grid is left untouched and counted (fpx_get_info "oh_skipped", of the last call).  loutnext is not used (the
+ * reference computes ldeltat from it and never reads it).  The result is per particle: it depends neither on the number of
+ * ranks nor on the storage order. */
+int fpx_ohreaction(fpx_handle h, int32_t itime, int32_t ltsample, int32_t loutnext);
+/* OH_hourly(nxOH,nyOH,nzOH,2) and memOHtime(2) (oh_mod.f90:13,15) in the host's real kind; either pointer may be NULL.  set:
+ * a host that computes its own hourly fields, or continues from values it kept. */
+int fpx_get_oh_hourly(fpx_handle h, void *OH_hourly_out, void *memOHtime_out);
+int fpx_set_oh_hourly(fpx_handle h, const void *OH_hourly, const void *memOHtime);
+/* device time (ms) of the two kernels of the last fpx_ohreaction, by events of its own */
+int fpx_ohreaction_time(fpx_handle h, double *ms);
+
 /* Precipitation / cloud / temperature fields of one nested grid and time slot: lsprecn, convprecn, tccn
  * (com_mod.f90:518-520), ctwcn (:503, only with readclouds_nest), ttn (:501), cloudsn integer(1) (:505), passed in the
  * members of fpx_wet_fields with strides nxmaxn, nymaxn(, nzmax); each pointer is element (0,0,1,slot,nest).  A particle
@@ -987,7 +1028,8 @@ void *fpx_stream(fpx_handle h);
  * forms with two quadratic Newton steps of m_rcp, m_rsqrt, m_sqrtp, m_sqrt_rsqrt (22 the root, 23 its reciprocal), m_rcbrt,
  * m_pow08, m_cuberoot_parts (26, 27 as 5, 6) and 31 of m_divf(3, x); 28, 29 the two results of m_sqrt_rsqrt and 30 m_divf(3, x)
  * as the kernels call them; 32 and 33 the 256-entry forms of 9 and 14 (m_exp_tab<256, 4>, m_exp_tab_nh<256, 4>: the exponential
- * of the fp64 gas kernels).  No reference counterpart; used by the parity tests to bound
+ * of the fp64 gas kernels); 40 .. 43 the device library's functions that k_ohreaction calls -- 40 exp, 41 expf, 42 pow and
+ * 43 powf of (x[i], x[n + i]), the f32 ones on the values rounded to float.  No reference counterpart; used by the parity tests to bound
  * the helpers against libm.  Returns 0 or a negative fpx_status. */
 int fpx_math_probe(int32_t fn, const double *x, double *y, int64_t n);
 /* Diagnostics: the turbulence profiles of one Langevin pass (hanna.f90) for n points in[5i..5i+4] = h, ol, ust, wst, z: ten values
@@ -1032,7 +1074,9 @@ int fpx_set_option(fpx_handle h, const char *name, const char *value);
  * first step; after "pbl_grid_blocks"), "pbl_blocks_per_cu" (resident blocks of four waves per CU the grid was sized for),
  * "pbl_list_length" (boundary-layer particles in the work list of the last step: one synchronising copy, diagnostics and
  * tests only), "conv_batches" (matrix batches of the last fpx_convmix, 0 when no column got past CONVECT's early exits, -1
- * before the first call).  Unknown names return FPX_ERR_ARG. */
+ * before the first call), "oh_skipped" (live particles the last fpx_ohreaction left untouched because their position was
+ * outside the mother grid; one synchronising copy), "oh_branch" (what the last fpx_gethourlyOH did: 0 nothing, 1 advanced the
+ * pair by an hour, 2 computed both fields; -1 before the first call).  Unknown names return FPX_ERR_ARG. */
 int fpx_get_info(fpx_handle h, const char *name, int64_t *value);
 
 #ifdef __cplusplus
