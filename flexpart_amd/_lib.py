@@ -82,6 +82,12 @@ class FpxCalcparIn(C.Structure):
                [("lsubgrid", C.c_int32), ("device_vdep", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class FpxCalcparGfsIn(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("lsubgrid", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("surfstr", "sshf", "hmix", "excessoro", "vdep")] + \
+               [("device_vdep", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FpxGetvdepTables(C.Structure):
     _fields_ = [("numclass", C.c_int32), ("ni", C.c_int32), ("maxspec", C.c_int32), ("reserved", C.c_int32), ("bdate", C.c_double)] + \
                [(n, C.c_void_p) for n in ("xlanduse", "z0", "ri", "rac", "rcl", "rgs", "rlu", "rm", "reldiff", "henry", "f0",
@@ -227,7 +233,7 @@ SYMBOLS = [
     "fpx_get_grids", "fpx_get_flux", "fpx_fluxoutput", "fpx_calcfluxes_time", "fpx_get_partavg", "fpx_partoutput_average", "fpx_partavg_time", "fpx_initcond_finish", "fpx_get_initcond", "fpx_initial_cond_output", "fpx_initcond_time", "fpx_plumetraj_init", "fpx_plumetraj", "fpx_get_plumetraj", "fpx_plumetraj_time", "fpx_domainfill_init", "fpx_boundcond_domainfill", "fpx_get_domainfill_acc", "fpx_set_domainfill_acc", "fpx_boundcond_output", "fpx_domainfill_time", "fpx_comm_unique_id", "fpx_comm_init", "fpx_comm_init_host", "fpx_count_particles", "fpx_lane_stats", "fpx_set_option", "fpx_get_info", "fpx_wet_init", "fpx_upload_wet_fields",
     "fpx_wetdepo", "fpx_get_wetgrid", "fpx_oh_init", "fpx_ohreaction", "fpx_get_oh_hourly", "fpx_set_oh_hourly", "fpx_ohreaction_time", "fpx_nests_init", "fpx_upload_nest_fields", "fpx_math_probe", "fpx_hanna_probe", "fpx_cbl_probe", "fpx_find_level_probe",
     "fpx_outgrid_nest_init", "fpx_get_grids_nest", "fpx_receptors_init", "fpx_get_receptors", "fpx_upload_wet_nest_fields",
-    "fpx_verttransform_ecmwf", "fpx_verttransform_nest", "fpx_verttransform_gfs", "fpx_verttransform_time", "fpx_calcpar", "fpx_calcpar_time", "fpx_getvdep_init", "fpx_getvdep", "fpx_getvdep_time", "fpx_calcpar_nest", "fpx_getvdep_nest_init", "fpx_getvdep_nest", "fpx_calcpv_init", "fpx_get_pvh", "fpx_calcpv_time", "fpx_upload_diag_fields", "fpx_partoutput", "fpx_partoutput_time", "fpx_readpartpositions", "fpx_concoutput",
+    "fpx_verttransform_ecmwf", "fpx_verttransform_nest", "fpx_verttransform_gfs", "fpx_verttransform_time", "fpx_calcpar", "fpx_calcpar_time", "fpx_getvdep_init", "fpx_getvdep", "fpx_getvdep_time", "fpx_calcpar_nest", "fpx_calcpar_gfs", "fpx_getvdep_nest_init", "fpx_getvdep_nest", "fpx_calcpv_init", "fpx_get_pvh", "fpx_calcpv_time", "fpx_upload_diag_fields", "fpx_partoutput", "fpx_partoutput_time", "fpx_readpartpositions", "fpx_concoutput",
     "fpx_checkpoint_write", "fpx_checkpoint_read",
     "fpx_conv_init", "fpx_upload_conv_fields", "fpx_convmix", "fpx_convmix_time", "fpx_get_cbaseflux", "fpx_set_cbaseflux",
     "fpx_upload_conv_nest_fields", "fpx_get_cbaseflux_nest", "fpx_set_cbaseflux_nest", "fpx_upload_diag_nest_fields",
@@ -279,6 +285,7 @@ def load():
     lib.fpx_getvdep.argtypes = [vp, C.c_int32, C.POINTER(FpxGetvdepIn), vp]
     lib.fpx_getvdep_time.argtypes = [vp, C.POINTER(C.c_double)]
     lib.fpx_calcpar_nest.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(FpxCalcparIn), C.POINTER(FpxCalcparOut)]
+    lib.fpx_calcpar_gfs.argtypes = [vp, C.c_int32, C.POINTER(FpxCalcparGfsIn), C.POINTER(FpxCalcparOut)]
     lib.fpx_getvdep_nest_init.argtypes = [vp, C.c_int32, vp]
     lib.fpx_getvdep_nest.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(FpxGetvdepIn), vp]
     lib.fpx_calcpv_init.argtypes = [vp, C.POINTER(FpxCalcpvCfg)]

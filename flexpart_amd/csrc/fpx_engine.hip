@@ -28,6 +28,7 @@
 #include "fpx_verttransform.hpp"
 #include "fpx_verttransform_gfs.hpp"
 #include "fpx_calcpar.hpp"
+#include "fpx_calcpar_gfs.hpp"
 #include "fpx_getvdep.hpp"
 #include "fpx_calcpv.hpp"
 #include "fpx_calcfluxes.hpp"
@@ -77,6 +78,7 @@ struct EngineBase {
   virtual int verttransform_gfs(int slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out, void *pplev_out) = 0;
   virtual int calcpar(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) = 0;
   virtual int calcpar_nest(int nest, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) = 0;
+  virtual int calcpar_gfs(int slot, const fpx_calcpar_gfs_in *c, const fpx_calcpar_out *out) = 0;
   virtual double cp_ms() = 0;
   virtual int getvdep_init(const fpx_getvdep_tables *t) = 0;
   virtual int getvdep(int slot, const fpx_getvdep_in *g, void *vdep_out) = 0;
@@ -883,15 +885,14 @@ struct Engine : EngineBase {
   // ---- calcpar on the device ----------------------------------------------------------
   // g = 0: the mother grid (calcpar.f90); g = l >= 1: nested grid l (one iteration l of calcpar_nests.f90:63-225): the same
   // kernel on the nest's arrays, extents and latitudes, with buffers and gather packs of the nest's own
+  // The buffers of a grid's calcpar (cp_begin) and what follows the kernel (cp_finish) are shared by calcpar_t and
+  // calcpar_gfs_t: gather packs, hcell, the copies into `out`, the timing and the slot's state.
   template <typename H>
-  int calcpar_t(int g, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) {
-    enum { UUH, VVH, PVH, WWH, TTH, QVH, PS, TT2, TD2, AKZ, BKZ, AKN, BKN, HGT,
-           UU, VV, WW, TT, QV, PV, RHO, DRHO, UPOL, VPOL, UVZ, WZ, RHOH, PINM, KUV, KW, NBUF };
-    void **vt_dev = vt_sets[g];
-    auto D = [&](int i) { return (H *)vt_dev[i]; };
+  struct CpDev { H *str, *shf, *exc, *ust, *wst, *oli, *hmix, *akm, *bkm, *trop; };
+  template <typename H>
+  int cp_begin(int g, int s, CpDev<H> &d) {
     const HostGrid HG = host_grid(g);
-    const WindDst T = wind_dst(g);
-    const int nz = cfg.nz, s = slot - 1;
+    const int nz = cfg.nz;
     const size_t n2 = (size_t)HG.nxmax * HG.nymax;
     int rc;
     if (!cp_buf[g]) {
@@ -901,13 +902,13 @@ struct Engine : EngineBase {
       cp_buf[g] = q;
     }
     H *B = (H *)cp_buf[g];
-    H *d_str = B, *d_shf = B + n2, *d_exc = B + 2 * n2, *d_ust = B + 3 * n2, *d_wst = B + 4 * n2, *d_oli = B + 5 * n2, *d_hmix = B + 6 * n2, *d_akm = B + 8 * n2, *d_bkm = d_akm + nz;
+    d.str = B; d.shf = B + n2; d.exc = B + 2 * n2; d.ust = B + 3 * n2; d.wst = B + 4 * n2; d.oli = B + 5 * n2; d.hmix = B + 6 * n2;
+    d.akm = B + 8 * n2; d.bkm = d.akm + nz;
     // the slot's tropopause in the host's layout (the mother grid's is kept for partoutput): it starts at zero and stale values
     // persist as in the reference -- the kernel writes a column only where the criterion fires (calcpar_nests.f90:201-214)
-    H *d_trop;
     if (g == 0) {
       if ((rc = diag_alloc())) return rc;
-      d_trop = (H *)diag_tropo[s];
+      d.trop = (H *)diag_tropo[s];
     } else {
       if (!nest_tropo[g - 1][s]) {
         H *q = nullptr;
@@ -915,27 +916,17 @@ struct Engine : EngineBase {
         HIPCHK(hipMemsetAsync(q, 0, n2 * sizeof(H), stream));
         nest_tropo[g - 1][s] = q;
       }
-      d_trop = (H *)nest_tropo[g - 1][s];
+      d.trop = (H *)nest_tropo[g - 1][s];
     }
-    HIPCHK(hipMemcpyAsync(d_str, c->surfstr, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_shf, c->sshf, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
-    if (c->lsubgrid == 1) HIPCHK(hipMemcpyAsync(d_exc, c->excessoro, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_akm, c->akm, (size_t)nz * sizeof(H), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_bkm, c->bkm, (size_t)nz * sizeof(H), hipMemcpyHostToDevice, stream));
-    cp::Args<H> A;
-    A.G.nx = HG.nx; A.G.ny = HG.ny; A.G.nz = nz; A.G.nuvz = nz; A.G.nwz = nz; A.G.nxmax = HG.nxmax; A.G.nymax = HG.nymax;
-    A.G.dx = (H)cfg.dx; A.G.dy = (H)cfg.dy; A.G.xlon0 = (H)cfg.xlon0; A.G.ylat0 = (H)cfg.ylat0;
-    if (g) { A.G.dy = (H)nest_dyn[g - 1]; A.G.ylat0 = (H)nest_ylat0n[g - 1]; }   // altmin: ylat0n(l) + jy*dyn(l), calcpar_nests.f90:73
-    A.I = vt::In<H>{D(UUH), D(VVH), D(PVH), D(WWH), D(TTH), D(QVH), D(PS), D(TT2), D(TD2), D(AKZ), D(BKZ), D(AKN), D(BKN), D(HGT)};
-    A.surfstr = d_str; A.sshf = d_shf; A.excessoro = d_exc; A.akm = d_akm; A.bkm = d_bkm; A.lsubgrid = c->lsubgrid;
-    A.zlev = D(RHOH);                          // scratch of the grid's transform, free between calls
-    A.ustar = d_ust; A.wstar = d_wst; A.oli = d_oli; A.hmix = d_hmix; A.tropopause = d_trop;
-    Events<2> ev;
-    HIPCHK(ev.create());
-    HIPCHK(hipEventRecord(ev[0], stream));
-    cp::k_calcpar<H><<<(HG.nx * HG.ny + 255) / 256, 256, 0, stream>>>(A);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev[1], stream));
+    return 0;
+  }
+  template <typename H>
+  int cp_finish(int g, int slot, const CpDev<H> &d, const void *vdep, const fpx_calcpar_out *out, Events<2> &ev) {
+    const HostGrid HG = host_grid(g);
+    const WindDst T = wind_dst(g);
+    const int s = slot - 1;
+    const size_t n2 = (size_t)HG.nxmax * HG.nymax;
+    int rc;
     // into the gather packs, as upload_fields / upload_nest_fields do from the host's arrays
     auto pk2 = [&](const H *in, const R *outp, int stride, int off) -> int {
       const int tot = HG.nx * HG.ny;
@@ -943,19 +934,19 @@ struct Engine : EngineBase {
       HIPCHK(hipGetLastError());
       return 0;
     };
-    if ((rc = pk2(d_ust, T.sfc, 8, s * 4 + 0)) || (rc = pk2(d_wst, T.sfc, 8, s * 4 + 1)) || (rc = pk2(d_oli, T.sfc, 8, s * 4 + 2)) || (rc = pk2(d_hmix, T.sfc, 8, s * 4 + 3))) return rc;
-    if (slot == 1 && (rc = pk2(d_trop, T.tropo, 1, 0))) return rc;        // literal time index 1, advance.f90:253 (tropopausen: :263)
+    if ((rc = pk2(d.ust, T.sfc, 8, s * 4 + 0)) || (rc = pk2(d.wst, T.sfc, 8, s * 4 + 1)) || (rc = pk2(d.oli, T.sfc, 8, s * 4 + 2)) || (rc = pk2(d.hmix, T.sfc, 8, s * 4 + 3))) return rc;
+    if (slot == 1 && (rc = pk2(d.trop, T.tropo, 1, 0))) return rc;        // literal time index 1, advance.f90:253 (tropopausen: :263)
     if (g == 0) diag_have[DG_TROPO + s] = true;
-    if (T.vdep && c->vdep) {
+    if (T.vdep && vdep) {
       const size_t plane = n2 * cfg.host_real_bytes;
       for (int ks = 0; ks < cfg.nspec; ks++)
-        if ((rc = p2(HG, (const char *)c->vdep + plane * ks, T.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
+        if ((rc = p2(HG, (const char *)vdep + plane * ks, T.vdep, 2 * cfg.nspec, s * cfg.nspec + ks))) return rc;
     }
     k_hcell<R><<<(HG.nx * HG.ny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(T.sfc, (R *)T.hcell, HG.nx, HG.ny);
     HIPCHK(hipGetLastError());
     if (out) {
       void *dst[5] = {out->ustar, out->wstar, out->oli, out->hmix, out->tropopause};
-      const H *src[5] = {d_ust, d_wst, d_oli, d_hmix, d_trop};
+      const H *src[5] = {d.ust, d.wst, d.oli, d.hmix, d.trop};
       for (int i = 0; i < 5; i++)
         if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], src[i], n2 * sizeof(H), hipMemcpyDeviceToHost, stream));
     }
@@ -965,10 +956,77 @@ struct Engine : EngineBase {
     cp_last_ms = ms;
     cp_slot_on_device[g] = slot;               // whose ustar, oli the grid's buffer holds (fpx_getvdep, fpx_getvdep_nest)
     // device_vdep with DRYDEP: the slot's vdep is still the previous wind field's until fpx_getvdep has run: not loaded
-    const bool pending = T.vdep && !c->vdep;
+    const bool pending = T.vdep && !vdep;
     if (g == 0) { vdep_pending[s] = pending; slot_loaded[s] = !pending; }
     else { nest_vdep_pending[g - 1][s] = pending; nest_loaded[g - 1][s] = !pending; }
     return 0;
+  }
+  template <typename H>
+  int calcpar_t(int g, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) {
+    enum { UUH, VVH, PVH, WWH, TTH, QVH, PS, TT2, TD2, AKZ, BKZ, AKN, BKN, HGT,
+           UU, VV, WW, TT, QV, PV, RHO, DRHO, UPOL, VPOL, UVZ, WZ, RHOH, PINM, KUV, KW, NBUF };
+    void **vt_dev = vt_sets[g];
+    auto D = [&](int i) { return (H *)vt_dev[i]; };
+    const HostGrid HG = host_grid(g);
+    const int nz = cfg.nz, s = slot - 1;
+    const size_t n2 = (size_t)HG.nxmax * HG.nymax;
+    int rc;
+    CpDev<H> d;
+    if ((rc = cp_begin<H>(g, s, d))) return rc;
+    HIPCHK(hipMemcpyAsync(d.str, c->surfstr, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d.shf, c->sshf, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
+    if (c->lsubgrid == 1) HIPCHK(hipMemcpyAsync(d.exc, c->excessoro, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d.akm, c->akm, (size_t)nz * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d.bkm, c->bkm, (size_t)nz * sizeof(H), hipMemcpyHostToDevice, stream));
+    cp::Args<H> A;
+    A.G.nx = HG.nx; A.G.ny = HG.ny; A.G.nz = nz; A.G.nuvz = nz; A.G.nwz = nz; A.G.nxmax = HG.nxmax; A.G.nymax = HG.nymax;
+    A.G.dx = (H)cfg.dx; A.G.dy = (H)cfg.dy; A.G.xlon0 = (H)cfg.xlon0; A.G.ylat0 = (H)cfg.ylat0;
+    if (g) { A.G.dy = (H)nest_dyn[g - 1]; A.G.ylat0 = (H)nest_ylat0n[g - 1]; }   // altmin: ylat0n(l) + jy*dyn(l), calcpar_nests.f90:73
+    A.I = vt::In<H>{D(UUH), D(VVH), D(PVH), D(WWH), D(TTH), D(QVH), D(PS), D(TT2), D(TD2), D(AKZ), D(BKZ), D(AKN), D(BKN), D(HGT)};
+    A.surfstr = d.str; A.sshf = d.shf; A.excessoro = d.exc; A.akm = d.akm; A.bkm = d.bkm; A.lsubgrid = c->lsubgrid;
+    A.zlev = D(RHOH);                          // scratch of the grid's transform, free between calls
+    A.ustar = d.ust; A.wstar = d.wst; A.oli = d.oli; A.hmix = d.hmix; A.tropopause = d.trop;
+    Events<2> ev;
+    HIPCHK(ev.create());
+    HIPCHK(hipEventRecord(ev[0], stream));
+    cp::k_calcpar<H><<<(HG.nx * HG.ny + 255) / 256, 256, 0, stream>>>(A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], stream));
+    return cp_finish<H>(g, slot, d, c->vdep, out, ev);
+  }
+  // fpx_calcpar_gfs: the NCEP branch (fpx_calcpar_gfs.hpp) on the arrays fpx_verttransform_gfs left; the host's raw hmix goes
+  // into the hmix plane, which the kernel reads and overwrites column by column
+  template <typename H>
+  int calcpar_gfs_t(int slot, const fpx_calcpar_gfs_in *c, const fpx_calcpar_out *out) {
+    enum { UUH, VVH, PVH, WWH, TTH, QVH, PS, TT2, TD2, AKZ, BKZ, AKN, BKN, HGT,
+           UU, VV, WW, TT, QV, PV, RHO, DRHO, UPOL, VPOL, UVZ, WZ, RHOH, PINM, KUV, KW, NBUF };
+    void **vt_dev = vt_sets[0];
+    auto D = [&](int i) { return (H *)vt_dev[i]; };
+    const HostGrid HG = host_grid(0);
+    const int nz = cfg.nz, s = slot - 1;
+    const size_t n2 = (size_t)HG.nxmax * HG.nymax;
+    int rc;
+    CpDev<H> d;
+    if ((rc = cp_begin<H>(0, s, d))) return rc;
+    HIPCHK(hipMemcpyAsync(d.str, c->surfstr, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d.shf, c->sshf, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d.hmix, c->hmix, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
+    if (c->lsubgrid == 1) HIPCHK(hipMemcpyAsync(d.exc, c->excessoro, n2 * sizeof(H), hipMemcpyHostToDevice, stream));
+    cpg::Args<H> A;
+    A.G = vt::Geo<H>{};
+    A.G.nx = HG.nx; A.G.ny = HG.ny; A.G.nz = nz; A.G.nuvz = nz; A.G.nwz = nz; A.G.nxmax = HG.nxmax; A.G.nymax = HG.nymax;
+    A.G.dx = (H)cfg.dx; A.G.dy = (H)cfg.dy; A.G.xlon0 = (H)cfg.xlon0; A.G.ylat0 = (H)cfg.ylat0;
+    A.I = vt::In<H>{D(UUH), D(VVH), D(PVH), D(WWH), D(TTH), D(QVH), D(PS), D(TT2), D(TD2), D(AKZ), D(BKZ), D(AKN), D(BKN), D(HGT)};
+    A.surfstr = d.str; A.sshf = d.shf; A.excessoro = d.exc; A.lsubgrid = c->lsubgrid;
+    A.zlev = D(RHOH);                          // scratch of the transform, free between calls
+    A.ustar = d.ust; A.wstar = d.wst; A.oli = d.oli; A.hmix = d.hmix; A.tropopause = d.trop;
+    Events<2> ev;
+    HIPCHK(ev.create());
+    HIPCHK(hipEventRecord(ev[0], stream));
+    cpg::k_calcpar_gfs<H><<<(HG.nx * HG.ny + 255) / 256, 256, 0, stream>>>(A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], stream));
+    return cp_finish<H>(0, slot, d, c->vdep, out, ev);
   }
   void *cp_buf[1 + kMaxNests] = {};          // one per grid, sized by it: calls for the mother grid and the nests may interleave
   void *nest_tropo[kMaxNests][2] = {};       // tropopausen(:,:,1,n,l) in the host's layout and real kind, allocated on first use
@@ -977,7 +1035,7 @@ struct Engine : EngineBase {
   bool vdep_pending[2] = {false, false};
   bool nest_vdep_pending[kMaxNests][2] = {};
   int calcpar(int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) override {
-    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "calcpar: NCEP GFS fields: the NCEP branch of calcpar.f90:109-121,145-149 (first level above ground, mixing height from the GRIB file) is not computed by this engine");
+    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "calcpar: NCEP GFS fields: the NCEP branch of calcpar.f90:109-121,145-149 (first level above ground, mixing height from the GRIB file) is not computed by this call: fpx_calcpar_gfs computes it");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "calcpar: slot must be 1 or 2");
     if (!c || !c->surfstr || !c->sshf || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "calcpar: surfstr, sshf, akm, bkm are required");
     if (c->lsubgrid == 1 && !c->excessoro) return fail(FPX_ERR_ARG, "calcpar: excessoro required with lsubgrid = 1");
@@ -986,7 +1044,7 @@ struct Engine : EngineBase {
     return cfg.host_real_bytes == 4 ? calcpar_t<float>(0, slot, c, out) : calcpar_t<double>(0, slot, c, out);
   }
   int calcpar_nest(int nest, int slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) override {
-    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "calcpar_nest: NCEP GFS fields: the NCEP branch of calcpar.f90:109-121,145-149 is not computed by this engine, and the reference has no GFS nests");
+    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "calcpar_nest: NCEP GFS fields: the NCEP branch of calcpar.f90:109-121,145-149 is computed by fpx_calcpar_gfs for the mother grid, and the reference has no GFS nests");
     if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "calcpar_nest: nest out of range (fpx_nests_init first)");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "calcpar_nest: slot must be 1 or 2");
     if (!c || !c->surfstr || !c->sshf || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "calcpar_nest: surfstrn, sshfn, akm, bkm are required");
@@ -995,6 +1053,16 @@ struct Engine : EngineBase {
     if (!vt_set_ready[nest] || vt_slot_on_device[nest] != slot)
       return fail(FPX_ERR_STATE, "calcpar_nest: fpx_verttransform_nest of this nest and slot first (its model-level arrays are read on the device)");
     return cfg.host_real_bytes == 4 ? calcpar_t<float>(nest, slot, c, out) : calcpar_t<double>(nest, slot, c, out);
+  }
+  int calcpar_gfs(int slot, const fpx_calcpar_gfs_in *c, const fpx_calcpar_out *out) override {
+    if (met_format != MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "calcpar_gfs: this handle does not take NCEP GFS fields (no fpx_verttransform_gfs has run on it): fpx_calcpar computes the ECMWF branch");
+    if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "calcpar_gfs: slot must be 1 or 2");
+    if (!c || c->struct_bytes != (int32_t)sizeof(fpx_calcpar_gfs_in)) return fail(FPX_ERR_ARG, "calcpar_gfs: null or fpx_calcpar_gfs_in size mismatch (ABI)");
+    if (!c->surfstr || !c->sshf || !c->hmix) return fail(FPX_ERR_ARG, "calcpar_gfs: surfstr, sshf, hmix (the GRIB file's mixing height) are required");
+    if (c->lsubgrid == 1 && !c->excessoro) return fail(FPX_ERR_ARG, "calcpar_gfs: excessoro required with lsubgrid = 1");
+    if (cfg.drydep && !c->vdep && !c->device_vdep) return fail(FPX_ERR_ARG, "calcpar_gfs: vdep (the host's getvdep) required with DRYDEP");
+    if (!vt_set_ready[0] || vt_slot_on_device[0] != slot) return fail(FPX_ERR_STATE, "calcpar_gfs: fpx_verttransform_gfs of this slot first (its pressure-level arrays are read on the device)");
+    return cfg.host_real_bytes == 4 ? calcpar_gfs_t<float>(slot, c, out) : calcpar_gfs_t<double>(slot, c, out);
   }
   // ---- getvdep on the device (calcpar.f90:171-189) ------------------------------------------------------------
   void *gv_tab = nullptr;                      // the resistance and species tables: shared by the mother grid and the nests
@@ -1190,9 +1258,9 @@ struct Engine : EngineBase {
     if (!gv_ready) return fail(FPX_ERR_STATE, "getvdep: fpx_getvdep_init first (the land-use inventory and the resistance tables)");
     if (!g || !g->ssr || !g->lsprec || !g->convprec || !g->sd) return fail(FPX_ERR_ARG, "getvdep: ssr, lsprec, convprec, sd are required");
     if ((!g->ustar || !g->oli) && (!cp_buf[0] || cp_slot_on_device[0] != slot))
-      return fail(FPX_ERR_ARG, "getvdep: ustar / oli = NULL means the ones fpx_calcpar left on the device: fpx_calcpar of this slot first");
+      return fail(FPX_ERR_ARG, "getvdep: ustar / oli = NULL means the ones fpx_calcpar / fpx_calcpar_gfs left on the device: that call for this slot first");
     if ((!g->ps || !g->tt2 || !g->td2) && (!vt_set_ready[0] || vt_slot_on_device[0] != slot))
-      return fail(FPX_ERR_ARG, "getvdep: ps / tt2 / td2 = NULL means the ones of fpx_verttransform_ecmwf: transform this slot first");
+      return fail(FPX_ERR_ARG, "getvdep: ps / tt2 / td2 = NULL means the ones of fpx_verttransform_ecmwf / fpx_verttransform_gfs: transform this slot first");
     return cfg.host_real_bytes == 4 ? getvdep_t<float>(0, slot, g, vdep_out) : getvdep_t<double>(0, slot, g, vdep_out);
   }
   int getvdep_nest(int nest, int slot, const fpx_getvdep_in *g, void *vdep_out) override {
@@ -1336,10 +1404,11 @@ struct Engine : EngineBase {
     if (slot == 1 && T.rhott)
       if ((rc = pk(D(RHO), T.rhott, 2, 0)) || (rc = pk(D(TT), T.rhott, 2, 1))) return rc;
     if (wet_on && Wp.ttw) { if ((rc = pk(D(TT), Wp.ttw, 2, s))) return rc; }
-    if ((rc = upload_wind2(0, slot, sfc))) return rc;
+    const bool have2d = sfc->hmix != nullptr;       // all five or none (checked by the caller); none: fpx_calcpar_gfs follows
+    if (have2d && (rc = upload_wind2(0, slot, sfc))) return rc;
     if ((rc = diag_alloc())) return rc;
     if ((rc = diag3(D(PV), true, 0, s)) || (rc = diag3(D(QV), true, 1, s)) || (rc = diag3(D(TT), true, 2, s))) return rc;
-    k_hcell<R><<<(gnx * gny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(T.sfc, (R *)T.hcell, gnx, gny);
+    if (have2d) k_hcell<R><<<(gnx * gny + kBlock - 1) / kBlock, kBlock, 0, stream>>>(T.sfc, (R *)T.hcell, gnx, gny);
     HIPCHK(hipGetLastError());
     if (out) {
       void *dst[10] = {out->uu, out->vv, out->ww, out->tt, out->qv, out->pv, out->rho, out->drhodz, out->uupol, out->vvpol};
@@ -1359,7 +1428,8 @@ struct Engine : EngineBase {
       pv_last_ms = ms;
     }
     pvh_on_device[0] = true;
-    slot_loaded[s] = true; vdep_pending[s] = false;
+    // without the 2-D fields the slot still holds those of the previous wind field until fpx_calcpar_gfs has run: not loaded
+    slot_loaded[s] = have2d; vdep_pending[s] = false;
     vt_slot_on_device[0] = slot;
     return 0;
   }
@@ -1371,8 +1441,9 @@ struct Engine : EngineBase {
     if (m->nuvz != cfg.nz || m->nwz != cfg.nz) return fail(FPX_ERR_ARG, "verttransform_gfs: nuvz = nwz = nz expected (gridcheck_gfs.f90:439-491 sets them equal)");
     if (cfg.nz < 4 || cfg.nz > 65535 || cfg.ny > 65535) return fail(FPX_ERR_ARG, "verttransform_gfs: 4 <= nz <= 65535, ny <= 65535");
     if (!sfc) return fail(FPX_ERR_UNSUPPORTED, "verttransform_gfs: sfc = NULL: the NCEP branch of calcpar.f90:109-121,145-149 is not computed by this engine; pass the host's hmix, ustar, wstar, oli, tropopause");
-    if (!sfc->hmix || !sfc->ustar || !sfc->wstar || !sfc->oli || !sfc->tropopause) return fail(FPX_ERR_ARG, "verttransform_gfs: the 2-D fields hmix, ustar, wstar, oli, tropopause are required");
-    if (cfg.drydep && !sfc->vdep) return fail(FPX_ERR_ARG, "verttransform_gfs: vdep required with DRYDEP");
+    const int n2d = (sfc->hmix != nullptr) + (sfc->ustar != nullptr) + (sfc->wstar != nullptr) + (sfc->oli != nullptr) + (sfc->tropopause != nullptr);
+    if (n2d != 0 && n2d != 5) return fail(FPX_ERR_ARG, "verttransform_gfs: the 2-D fields hmix, ustar, wstar, oli, tropopause are required (or all five NULL and fpx_calcpar_gfs)");
+    if (n2d == 5 && cfg.drydep && !sfc->vdep) return fail(FPX_ERR_ARG, "verttransform_gfs: vdep required with DRYDEP");
     if (!m->pvh && (cfg.nx < 3 || cfg.ny < 4)) return fail(FPX_ERR_ARG, "verttransform_gfs: calcpv on the device (pvh = NULL) needs nx >= 3, ny >= 4");
     const int rc = cfg.host_real_bytes == 4 ? verttransform_gfs_t<float>(slot, m, sfc, out, pplev_out) : verttransform_gfs_t<double>(slot, m, sfc, out, pplev_out);
     if (!rc) met_format = MET_GFS;
@@ -5181,6 +5252,7 @@ int fpx_calcpar(fpx_handle h, int32_t slot, const fpx_calcpar_in *c, const fpx_c
 int fpx_getvdep_init(fpx_handle h, const fpx_getvdep_tables *t) { FPX_GUARD(h); return h->impl->getvdep_init(t); }
 int fpx_getvdep(fpx_handle h, int32_t slot, const fpx_getvdep_in *g, void *vdep_out) { FPX_GUARD(h); return h->impl->getvdep(slot, g, vdep_out); }
 int fpx_calcpar_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out) { FPX_GUARD(h); return h->impl->calcpar_nest(nest, slot, c, out); }
+int fpx_calcpar_gfs(fpx_handle h, int32_t slot, const fpx_calcpar_gfs_in *c, const fpx_calcpar_out *out) { FPX_GUARD(h); return h->impl->calcpar_gfs(slot, c, out); }
 int fpx_getvdep_nest_init(fpx_handle h, int32_t nest, const void *xlandusen) { FPX_GUARD(h); return h->impl->getvdep_nest_init(nest, xlandusen); }
 int fpx_getvdep_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_getvdep_in *g, void *vdep_out) { FPX_GUARD(h); return h->impl->getvdep_nest(nest, slot, g, vdep_out); }
 int fpx_calcpv_init(fpx_handle h, const fpx_calcpv_cfg *c) { FPX_GUARD(h); return h->impl->calcpv_init(c); }

@@ -261,7 +261,8 @@ class Engine:
                           want=("uu", "vv", "ww", "tt", "qv", "pv", "rho", "drhodz", "uupol", "vvpol", "pplev"), device_pv=False):
         """fpx_verttransform_gfs: m = synthetic.gfs_levels() dict (compact [nz][ny][nx] arrays, akz = the pressures of the
         levels), sfc = dict of compact 2-D fields (hmix, ustar, wstar, oli, tropopause[, vdep]) of this slot; sfc = None is
-        passed through as NULL (the library refuses it).  device_pv: pvh = NULL, calcpv runs on the device.
+        passed through as NULL (the library refuses it); sfc = {} leaves the five 2-D members NULL: calcpar_gfs(slot, ..)
+        follows and the slot stays "not loaded" until it has run.  device_pv: pvh = NULL, calcpv runs on the device.
         Returns the z-level arrays asked for (compact; "pplev" is the GFS extra), height and nmixz."""
         from ._lib import FpxModelLevels, FpxFieldsOut
         rt = self.hreal
@@ -285,6 +286,8 @@ class Engine:
         f = FpxFields()
         if sfc is not None:
             for k in ("hmix", "ustar", "wstar", "oli", "tropopause"):
+                if k not in sfc:            # a member left NULL; sfc = {}: all five NULL, calcpar_gfs(slot, ..) follows
+                    continue
                 a = np.zeros((self.nymax, self.nxmax), rt)
                 a[: self.ny, : self.nx] = sfc[k]
                 keep["s" + k] = a
@@ -373,6 +376,45 @@ class Engine:
         ms = C.c_double(0)
         check(self.lib.fpx_calcpar_time(self.h, C.byref(ms)), "fpx_calcpar_time")
         out["device_ms"] = ms.value
+        return out
+
+    def calcpar_gfs(self, slot, cin, vdep=None, device_vdep=False):
+        """fpx_calcpar_gfs after verttransform_gfs(slot, m, {}): cin = synthetic.calcpar_gfs_inputs(m) (surfstr, sshf, excessoro,
+        the GRIB file's raw hmix, lsubgrid).  Returns the five 2-D fields (compact [ny][nx]) and the device time.
+        device_vdep: with DRYDEP no vdep is handed over; getvdep(slot, ..) follows."""
+        from ._lib import FpxCalcparGfsIn, FpxCalcparOut
+        rt = self.hreal
+        keep = {}
+        c = FpxCalcparGfsIn()
+        c.struct_bytes = C.sizeof(FpxCalcparGfsIn)
+        for k in ("surfstr", "sshf", "excessoro", "hmix"):
+            if cin.get(k) is None:          # left NULL: the library says what is missing
+                continue
+            a = np.zeros((self.nymax, self.nxmax), rt)
+            a[: self.ny, : self.nx] = cin[k]
+            keep[k] = a
+            setattr(c, k, a.ctypes.data)
+        c.lsubgrid = int(cin["lsubgrid"])
+        c.device_vdep = int(bool(device_vdep))
+        if vdep is not None:
+            v = np.zeros((self.nspec, self.nymax, self.nxmax), rt)
+            v[:, : self.ny, : self.nx] = vdep
+            keep["vdep"] = v
+            c.vdep = v.ctypes.data
+        o = FpxCalcparOut()
+        res = {}
+        for k in ("ustar", "wstar", "oli", "hmix", "tropopause"):
+            res[k] = np.zeros((self.nymax, self.nxmax), rt)
+            setattr(o, k, res[k].ctypes.data)
+        import time as _time
+        t0 = _time.perf_counter()
+        check(self.lib.fpx_calcpar_gfs(self.h, int(slot), C.byref(c), C.byref(o)), "fpx_calcpar_gfs")
+        call_s = _time.perf_counter() - t0
+        out = {k: v[: self.ny, : self.nx].astype(np.float64) for k, v in res.items()}
+        ms = C.c_double(0)
+        check(self.lib.fpx_calcpar_time(self.h, C.byref(ms)), "fpx_calcpar_time")
+        out["device_ms"] = ms.value
+        out["call_ms"] = call_s * 1e3
         return out
 
     def getvdep_init(self, tables):

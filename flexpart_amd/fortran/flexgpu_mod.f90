@@ -41,7 +41,7 @@ module flexgpu_mod
             flexgpu_plumetraj_init, flexgpu_plumetraj, &
             flexgpu_domainfill_init, flexgpu_boundcond_domainfill, flexgpu_boundcond_output, &
             flexgpu_concoutput, flexgpu_abi_sizes, flexgpu_comm_init_host, flexgpu_count_particles, flexgpu_set_option, flexgpu_get_info, &
-            flexgpu_release_init, flexgpu_releaseparticles, flexgpu_split_particles, flexgpu_calcpar, &
+            flexgpu_release_init, flexgpu_releaseparticles, flexgpu_split_particles, flexgpu_calcpar, flexgpu_calcpar_gfs, &
             flexgpu_getvdep_init, flexgpu_getvdep, &
             flexgpu_redist_plan, flexgpu_redist_bytes, flexgpu_redist_pack, flexgpu_redist_unpack, &
             flexgpu_checkpoint_write, flexgpu_checkpoint_read, &
@@ -180,6 +180,11 @@ module flexgpu_mod
     integer(c_int32_t) :: device_vdep
     integer(c_int32_t) :: reserved(2)
   end type fpx_calcpar_in
+  type, bind(C) :: fpx_calcpar_gfs_in
+    integer(c_int32_t) :: struct_bytes, lsubgrid
+    type(c_ptr) :: surfstr, sshf, hmix, excessoro, vdep
+    integer(c_int32_t) :: device_vdep, reserved
+  end type fpx_calcpar_gfs_in
   type, bind(C) :: fpx_getvdep_tables
     integer(c_int32_t) :: numclass, ni, maxspec, reserved
     real(c_double) :: bdate
@@ -238,6 +243,13 @@ module flexgpu_mod
       type(c_ptr), value :: h
       integer(c_int32_t), value :: slot
       type(fpx_calcpar_in), intent(in) :: c
+      type(fpx_calcpar_out), intent(in) :: o
+    end function
+    integer(c_int) function fpx_calcpar_gfs(h, slot, c, o) bind(C, name='fpx_calcpar_gfs')
+      import :: c_ptr, c_int, c_int32_t, fpx_calcpar_gfs_in, fpx_calcpar_out
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: slot
+      type(fpx_calcpar_gfs_in), intent(in) :: c
       type(fpx_calcpar_out), intent(in) :: o
     end function
     integer(c_int) function fpx_getvdep_init(h, t) bind(C, name='fpx_getvdep_init')
@@ -344,7 +356,7 @@ module flexgpu_mod
       type(c_ptr), value :: sfc            ! c_loc of a type(fpx_fields), or c_null_ptr: flexgpu_calcpar follows
       type(fpx_fields_out), intent(in) :: o
     end function fpx_verttransform_ecmwf
-    ! NCEP GFS fields on pressure levels (verttransform_gfs.f90): sfc is required, pplev_out = c_loc(pplev(0,0,1,n)) or c_null_ptr
+    ! NCEP GFS fields on pressure levels (verttransform_gfs.f90): sfc is required (its five 2-D members c_null_ptr: flexgpu_calcpar_gfs follows), pplev_out = c_loc(pplev(0,0,1,n)) or c_null_ptr
     integer(c_int) function fpx_verttransform_gfs(h, slot, m, sfc, o, pplev_out) bind(C, name='fpx_verttransform_gfs')
       import :: c_ptr, c_int, c_int32_t, fpx_model_levels, fpx_fields_out
       type(c_ptr), value :: h
@@ -1577,7 +1589,7 @@ contains
   ! host.  vdep: with DRYDEP either the host's vdep(:,:,:,n) must have been computed before this call, or
   ! device_vdep = .true. and flexgpu_getvdep(n, ierr) follows (the slot is not usable by the step until it has run).
   ! writeback (default .true.): the five fields are also copied into com_mod for host routines that read them.
-  ! (No Fortran-host test: calcpar.f90 itself cannot be compiled in the build image -- class_gribfile needs ecCodes.)
+  ! (No Fortran-host test; the routine is pinned through tests/golden/ref_cpg_driver.f90 with a stand-in for class_gribfile.)
   subroutine flexgpu_calcpar(n, ierr, writeback, device_vdep)
     integer, intent(in) :: n
     integer, intent(out) :: ierr
@@ -1605,6 +1617,41 @@ contains
     end if
     ierr = fpx_calcpar(flexgpu_handle, int(n, c_int32_t), c, o)
   end subroutine flexgpu_calcpar
+
+  ! Replaces `call calcpar(n,uuh,vvh,pvh,metdata_format)` for NCEP GFS fields (the GRIBFILE_CENTRE_NCEP branch of
+  ! calcpar.f90:109-121,145-149, obukhov.f90, richardson.f90): call after fpx_verttransform_gfs of slot n with a sfc whose
+  ! hmix, ustar, wstar, oli, tropopause are c_null_ptr.  hmix(:,:,1,n) must hold the mixing height readwind_gfs read from the
+  ! GRIB file: it is the input, and with writeback (default .true.) it receives calcpar's value, as in the reference.
+  ! vdep, device_vdep: as for flexgpu_calcpar; flexgpu_getvdep(n, ierr) works on a GFS handle.
+  subroutine flexgpu_calcpar_gfs(n, ierr, writeback, device_vdep)
+    integer, intent(in) :: n
+    integer, intent(out) :: ierr
+    logical, intent(in), optional :: writeback, device_vdep
+    type(fpx_calcpar_gfs_in) :: c
+    type(fpx_calcpar_out) :: o
+    logical :: wb, dv
+    wb = .true.; if (present(writeback)) wb = writeback
+    dv = .false.; if (present(device_vdep)) dv = device_vdep
+    c%struct_bytes = int(c_sizeof(c), c_int32_t)
+    c%lsubgrid = lsubgrid
+    c%surfstr = loc_r(surfstr(0,0,1,n)); c%sshf = loc_r(sshf(0,0,1,n))
+    c%hmix = loc_r(hmix(0,0,1,n))
+    c%excessoro = loc_r(excessoro)
+    c%vdep = c_null_ptr
+    c%device_vdep = 0
+    if (DRYDEP .and. dv) then
+      c%device_vdep = 1
+    else if (DRYDEP) then
+      c%vdep = loc_r(vdep(0,0,1,n))
+    end if
+    c%reserved = 0
+    o%ustar = c_null_ptr; o%wstar = c_null_ptr; o%oli = c_null_ptr; o%hmix = c_null_ptr; o%tropopause = c_null_ptr
+    if (wb) then
+      o%ustar = loc_r(ustar(0,0,1,n)); o%wstar = loc_r(wstar(0,0,1,n)); o%oli = loc_r(oli(0,0,1,n))
+      o%hmix = loc_r(hmix(0,0,1,n)); o%tropopause = loc_r(tropopause(0,0,1,n))
+    end if
+    ierr = fpx_calcpar_gfs(flexgpu_handle, int(n, c_int32_t), c, o)
+  end subroutine flexgpu_calcpar_gfs
 
   ! ---- getvdep on the device (the DRYDEP block of calcpar, calcpar.f90:171-189) --------------------------------
   ! once, after readlanduse / readdepo / readspecies / assignland have filled com_mod and after flexgpu_init: the land-use

@@ -789,6 +789,20 @@ def calcpar_inputs(m, lsubgrid=1):
     return dict(surfstr=surfstr, sshf=sshf, excessoro=exc, akm=akm, bkm=bkm, lsubgrid=int(lsubgrid))
 
 
+def calcpar_gfs_inputs(m, lsubgrid=1):
+    """What the NCEP branch of calcpar reads besides the pressure levels of a gfs_levels() dict: calcpar_inputs' surfstr, sshf
+    and excessoro, and hmix -- the mixing height as readwind_gfs took it from the GRIB file.  It runs from below hmixmin
+    (100 m) to above hmixmax (4500 m), so that both clamps of calcpar.f90:165-166 fire."""
+    c = calcpar_inputs(m, lsubgrid)
+    nx, ny, nz = (int(v) for v in m["grid"])
+    per = nx - 1
+    i = np.arange(nx, dtype=np.int64)[None, :]
+    j = np.arange(ny, dtype=np.int64)[:, None]
+    hmix = 2400.0 + 2500.0 * _wave(i + 3 * j, per) + 0.0 * j         # about -100 m ... 4900 m
+    hmix[:, nx - 1] = hmix[:, 0]
+    return dict(surfstr=c["surfstr"], sshf=c["sshf"], excessoro=c["excessoro"], hmix=hmix, lsubgrid=int(lsubgrid))
+
+
 # --------------------------------------------------------------------------
 # convective mixing (convmix.f90): soundings with and without CAPE
 # --------------------------------------------------------------------------

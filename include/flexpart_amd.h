@@ -267,15 +267,20 @@ int fpx_verttransform_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_m
  * written (:271-285), so it keeps what the slot held before the call and the slope term (:354) is added to that -- the engine
  * keeps a z-level ww per slot for this, zero at first use like com_mod's array (a checkpoint does not carry it).  Where the slope term reads uvwzlev of a
  * neighbour column below that column's llev (entries of an automatic array the routine never wrote) the device reads 0.
- * sfc is required: the GFS mixing height comes from the GRIB file and the NCEP branch of calcpar.f90:109-121,145-149 stays
- * with the host; sfc = NULL returns FPX_ERR_UNSUPPORTED.  pvh = NULL: calcpv on the device first, as for ECMWF (calcpv.f90 has
+ * sfc is required: the GFS mixing height comes from the GRIB file, so the NCEP branch of calcpar.f90:109-121,145-149 is not
+ * this call's; sfc = NULL returns FPX_ERR_UNSUPPORTED.  Either sfc carries the host's hmix, ustar, wstar, oli, tropopause (and
+ * vdep with DRYDEP), or all five are NULL: then fpx_calcpar_gfs(h, slot, ..) follows and computes them on the device (sfc's
+ * vdep is ignored), and until it has run the slot is "not loaded": fpx_step and fpx_releaseparticles return FPX_ERR_STATE, so
+ * no step runs on new winds with the previous field's boundary layer.  Some of the five NULL and some not: FPX_ERR_ARG.
+ * pvh = NULL: calcpv on the device first, as for ECMWF (calcpv.f90 has
  * no format branch); fpx_get_pvh works afterwards.  pplev_out (may be NULL) receives pplev(0:nxmax-1,0:nymax-1,nzmax) of this
  * slot, which the reference's GFS convection reads (convmix.f90:181-188).  fpx_verttransform_time reports the device time.
  * Not computed: the cloud block :498-596 (both the readclouds branch and the parameterised one) and clwc, as the ECMWF path
  * leaves out its cloud diagnostics.
  * A handle becomes a GFS handle at its first fpx_verttransform_gfs.  On it fpx_calcpar, fpx_calcpar_nest, fpx_conv_init,
  * fpx_convmix, fpx_verttransform_ecmwf and fpx_verttransform_nest return FPX_ERR_UNSUPPORTED (their ECMWF arithmetic would be
- * wrong on GFS data), and fpx_verttransform_gfs is refused on a handle that has run an ECMWF transform. */
+ * wrong on GFS data; fpx_calcpar_gfs is the GFS counterpart of fpx_calcpar), and fpx_verttransform_gfs is refused on a handle
+ * that has run an ECMWF transform.  fpx_getvdep has no format branch (getvdep.f90) and works on either. */
 int fpx_verttransform_gfs(fpx_handle h, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out, void *pplev_out);
 /* device time of the transform kernels of the last call, milliseconds (without the PV kernels of a call with pvh = NULL) */
 int fpx_verttransform_time(fpx_handle h, double *ms);
@@ -333,7 +338,31 @@ int fpx_calcpar(fpx_handle h, int32_t slot, const fpx_calcpar_in *c, const fpx_c
  * the nest's arrays, e.g. c_loc(hmixn(0,0,1,n,l)).  Calls for the mother grid and for the nests may interleave in any
  * order: every grid has buffers of its own. */
 int fpx_calcpar_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_calcpar_in *c, const fpx_calcpar_out *out);
-/* device time of the kernel of the last fpx_calcpar / fpx_calcpar_nest call (whichever grid it was for), milliseconds */
+/* calcpar for NCEP GFS fields: replaces `call calcpar(n,uuh,vvh,pvh,metdata_format)` with metdata_format =
+ * GRIBFILE_CENTRE_NCEP -- calcpar.f90:76-265 with the NCEP branches :109-121 (llev: the first pressure level above ground;
+ * obukhov.f90 with tth(llev) and plev = akz(llev)), :145-149 (the mixing height is the GRIB file's; richardson.f90:73-86,
+ * 107-112 starts its level loop at its own llev and gives only wstar and hmixplus), :156-166 (hmix = the host's raw hmix +
+ * min(excessoro, hmixplus) with lsubgrid = 1, clamped to hmixmin / hmixmax) and :198-257 (zlev and the tropopause search
+ * from llev).  It runs on the pressure-level arrays fpx_verttransform_gfs(h, slot, m, sfc, ..) uploaded for this slot -- call
+ * that first, with the five 2-D members of sfc NULL -- and leaves the handle as fpx_calcpar leaves an ECMWF handle: the gather
+ * packs of the slot (hcell included), the tropopause rule, vdep or the wait for fpx_getvdep (device_vdep = 1), and
+ * fpx_calcpar_time.  A column in which no layer meets the tropopause criterion keeps the previous value of the slot's buffer
+ * (zero at first use).  The reference does not reset kzmin per column (:232-238); a column none of whose levels reaches
+ * altmin searches from llev here.
+ * FPX_ERR_UNSUPPORTED on a handle that is not a GFS handle, FPX_ERR_STATE unless fpx_verttransform_gfs of this slot was the
+ * last transform, FPX_ERR_ARG for missing members. */
+typedef struct {
+  int32_t struct_bytes;          /* sizeof(fpx_calcpar_gfs_in)                                                   */
+  int32_t lsubgrid;              /* com_mod.f90:117                                                             */
+  const void *surfstr, *sshf;    /* as fpx_calcpar_in                                                           */
+  const void *hmix;              /* c_loc(hmix(0,0,1,n)) as readwind_gfs left it: input                         */
+  const void *excessoro;         /* (0:nxmax-1,0:nymax-1), read with lsubgrid = 1 (else NULL)                   */
+  const void *vdep;              /* as fpx_calcpar_in                                                           */
+  int32_t device_vdep;           /* as fpx_calcpar_in: fpx_getvdep of this slot follows                         */
+  int32_t reserved;
+} fpx_calcpar_gfs_in;
+int fpx_calcpar_gfs(fpx_handle h, int32_t slot, const fpx_calcpar_gfs_in *c, const fpx_calcpar_out *out);
+/* device time of the kernel of the last fpx_calcpar / fpx_calcpar_nest / fpx_calcpar_gfs call (whichever grid it was for), milliseconds */
 int fpx_calcpar_time(fpx_handle h, double *ms);
 /* ---- getvdep on the device: the dry-deposition velocities of calcpar (calcpar.f90:171-189) -----------------
  * Replaces the DRYDEP block of calcpar -- z0(7) from ustar, rh = ew(td2)/ew(tt2), `call getvdep(..)` (getvdep.f90 with
