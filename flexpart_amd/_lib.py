@@ -112,6 +112,14 @@ class FpxConvFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ps", "tt2", "td2", "tth", "qvh")] + [("nuvzmax", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FpxConvGfsConfig(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("nuvz", C.c_int32), ("nconvlev", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FpxConvGfsFields(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("ps", "tt2", "td2", "tt", "qv", "pplev")] + [("nzmax", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FpxCalcpvCfg(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("dxn", C.c_double * 4)]
 
@@ -237,7 +245,7 @@ SYMBOLS = [
     "fpx_checkpoint_write", "fpx_checkpoint_read",
     "fpx_conv_init", "fpx_upload_conv_fields", "fpx_convmix", "fpx_convmix_time", "fpx_get_cbaseflux", "fpx_set_cbaseflux",
     "fpx_upload_conv_nest_fields", "fpx_get_cbaseflux_nest", "fpx_set_cbaseflux_nest", "fpx_upload_diag_nest_fields",
-    "fpx_conv_columns",
+    "fpx_conv_columns", "fpx_conv_init_gfs", "fpx_upload_conv_gfs_fields", "fpx_conv_soundings",
 ]
 
 # ... and the one whose name follows the reference routine's spelling (SYMBOLS holds the all-lower-case names)
@@ -301,6 +309,9 @@ def load():
     lib.fpx_convmix.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
     lib.fpx_convmix_time.argtypes = [vp, C.POINTER(C.c_double)]
     lib.fpx_conv_columns.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp]
+    lib.fpx_conv_init_gfs.argtypes = [vp, C.POINTER(FpxConvGfsConfig)]
+    lib.fpx_upload_conv_gfs_fields.argtypes = [vp, C.c_int32, C.POINTER(FpxConvGfsFields)]
+    lib.fpx_conv_soundings.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.fpx_upload_conv_nest_fields.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(FpxConvFields)]
     lib.fpx_upload_diag_nest_fields.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(FpxDiagFields)]
     lib.fpx_get_cbaseflux_nest.argtypes = [vp, C.c_int32, vp]

@@ -38,6 +38,7 @@
 #include "fpx_plumetraj.hpp"
 #include "fpx_domainfill.hpp"
 #include "fpx_convect.hpp"
+#include "fpx_convect_gfs.hpp"
 #include "fpx_step_common.hpp"
 #include "fpx_fields.hpp"
 #include "fpx_sort.hpp"
@@ -172,6 +173,9 @@ struct EngineBase {
   virtual int cbaseflux_nest_io(int nest, void *host, bool set) = 0;
   virtual double conv_ms() = 0;
   virtual int conv_columns(const int32_t *col, int ncol, int32_t *lconv, int32_t *nconvtop, void *fmassfrac, void *uvzlev) = 0;
+  virtual int conv_init_gfs(const fpx_conv_gfs_config *c) = 0;
+  virtual int upload_conv_gfs_fields(int slot, const fpx_conv_gfs_fields *f) = 0;
+  virtual int conv_soundings(const int32_t *col, int ncol, void *psconv, void *pconv, void *phconv, void *dpr, void *tconv, void *qconv) = 0;
   virtual int checkpoint_write(const char *path, int itime, int numparticlecount) = 0;
   virtual int checkpoint_read(const char *path, int32_t *itime, int64_t *numpart_out, int32_t *numparticlecount) = 0;
 };
@@ -1418,6 +1422,7 @@ struct Engine : EngineBase {
       if (out->nmixz) *out->nmixz = V.nmixz;
     }
     if (pplev_out) HIPCHK(hipMemcpyAsync(pplev_out, d_pplev, n3 * sizeof(H), hipMemcpyDeviceToHost, stream));
+    if (conv_gfs && (rc = conv_keep_gfs<H>(slot, D(PS), D(TT2), D(TD2), D(TT), D(QV), d_pplev))) return rc;
     HIPCHK(hipStreamSynchronize(stream));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
@@ -2440,7 +2445,7 @@ struct Engine : EngineBase {
   double conv_ms() override { return conv_last_ms; }
 
   int conv_init(const fpx_conv_config *c) override {
-    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "conv_init: NCEP GFS fields: convmix.f90:100-116,173-189 (pplev-based columns) and the NCEP branch of calcmatrix.f90 are not computed by this engine");
+    if (met_format == MET_GFS || conv_gfs) return fail(FPX_ERR_UNSUPPORTED, "conv_init: NCEP GFS fields: convmix.f90:100-116,173-189 (pplev-based columns) and the NCEP branch of calcmatrix.f90 are not computed by this call: fpx_conv_init_gfs sets them up");
     if (!c || c->struct_bytes != (int32_t)sizeof(fpx_conv_config)) return fail(FPX_ERR_ARG, "conv_init: null or fpx_conv_config size mismatch (ABI)");
     if (c->nuvz < 4 || c->nconvlev < 2 || c->nconvlev > c->nuvz - 2) return fail(FPX_ERR_ARG, "conv_init: need 2 <= nconvlev <= nuvz - 2");
     if (!c->akz || !c->bkz || !c->akm || !c->bkm) return fail(FPX_ERR_ARG, "conv_init: akz, bkz, akm, bkm are required");
@@ -2480,6 +2485,7 @@ struct Engine : EngineBase {
   }
   int upload_conv_fields(int slot, const fpx_conv_fields *f) override {
     if (!conv_on) return fail(FPX_ERR_STATE, "upload_conv_fields: fpx_conv_init first");
+    if (conv_gfs) return fail(FPX_ERR_UNSUPPORTED, "upload_conv_fields: fpx_conv_init_gfs has run on this handle: its slots take ps, tt2, td2, tt, qv, pplev (fpx_upload_conv_gfs_fields), not the model-level tth, qvh");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_conv_fields: slot must be 1 or 2");
     if (!f || !f->ps || !f->tt2 || !f->td2 || !f->tth || !f->qvh) return fail(FPX_ERR_ARG, "upload_conv_fields: ps, tt2, td2, tth, qvh are required");
     if (f->nuvzmax < conv_nuvz) return fail(FPX_ERR_ARG, "upload_conv_fields: nuvzmax < nuvz");
@@ -2487,6 +2493,7 @@ struct Engine : EngineBase {
   }
   int upload_conv_nest_fields(int nest, int slot, const fpx_conv_fields *f) override {
     if (!conv_on) return fail(FPX_ERR_STATE, "upload_conv_nest_fields: fpx_conv_init first");
+    if (conv_gfs) return fail(FPX_ERR_UNSUPPORTED, "upload_conv_nest_fields: fpx_conv_init_gfs has run on this handle: the reference has no GFS nests");
     if (nest < 1 || nest > V.numbnests) return fail(FPX_ERR_ARG, "upload_conv_nest_fields: nest out of range (fpx_nests_init first)");
     if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_conv_nest_fields: slot must be 1 or 2");
     if (!f || !f->ps || !f->tt2 || !f->td2 || !f->tth || !f->qvh) return fail(FPX_ERR_ARG, "upload_conv_nest_fields: ps, tt2, td2, tth, qvh are required");
@@ -2688,7 +2695,8 @@ struct Engine : EngineBase {
     // fpx_set_option "conv_no_walk": the interleaved form
     const bool conv_walk = !conv_one_lane && !opt.conv_no_walk;
     const bool conv_rows_plain = opt.conv_rows_plain != 0;  // k_conv_rows without the LDS staging of its operands
-    conv::k_conv_column_a<H><<<conv::serial_grid(nact), 64, 0, stream>>>(F, vbuf, cst, nv, conv_act, nact, alive);
+    if (conv_gfs) cvg::k_conv_column_a_gfs<H><<<conv::serial_grid(nact), 64, 0, stream>>>(F, (const H *)conv_pplev[F.m1], (const H *)conv_pplev[F.m2], vbuf, cst, nv, conv_act, nact, alive);
+    else conv::k_conv_column_a<H><<<conv::serial_grid(nact), 64, 0, stream>>>(F, vbuf, cst, nv, conv_act, nact, alive);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(conv_lconv, 0, (size_t)nact * sizeof(int), stream));
     HIPCHK(hipMemsetAsync(conv_ntop, 0, (size_t)nact * sizeof(int), stream));
@@ -2803,9 +2811,111 @@ struct Engine : EngineBase {
                                     : conv_columns_t<double>(col, ncol_req, lconv, nconvtop, fmassfrac, uvzlev);
   }
 
+  // ---- the NCEP GFS branch (fpx_convect_gfs.hpp) ------------------------------------------------------------------
+  // conv_fld[0][0..4] hold ps, tt2, td2 and the z-level tt, qv (in the places of tth, qvh); pplev has buffers of its own.
+  bool conv_gfs = false;
+  void *conv_pplev[2] = {nullptr, nullptr};
+  int conv_init_gfs(const fpx_conv_gfs_config *c) override {
+    if (!c || c->struct_bytes != (int32_t)sizeof(fpx_conv_gfs_config)) return fail(FPX_ERR_ARG, "conv_init_gfs: null or fpx_conv_gfs_config size mismatch (ABI)");
+    if (met_format == MET_ECMWF) return fail(FPX_ERR_UNSUPPORTED, "conv_init_gfs: this handle has run an ECMWF transform: fpx_conv_init is its convection set-up");
+    if (V.numbnests) return fail(FPX_ERR_UNSUPPORTED, "conv_init_gfs: fpx_nests_init has run: the reference has no GFS nests (the eps-free nest test of convmix.f90:108-116 is never reached)");
+    if (conv_on) return fail(FPX_ERR_STATE, "conv_init_gfs: convection is already initialised");
+    if (cfg.device_flux) return fail(FPX_ERR_UNSUPPORTED, "conv_init_gfs: device_flux = 1: the calcfluxes calls of the convective displacement (convmix.f90:208-220,284-296) are not computed by this engine");
+    if (c->nuvz != cfg.nz) return fail(FPX_ERR_ARG, "conv_init_gfs: nuvz = nz expected (gridcheck_gfs.f90:439-491 sets them equal)");
+    if (c->nuvz < 4 || c->nconvlev < 2 || c->nconvlev > c->nuvz - 2) return fail(FPX_ERR_ARG, "conv_init_gfs: need 2 <= nconvlev <= nuvz - 2");
+    const size_t hb = (size_t)cfg.host_real_bytes;
+    int rc;
+    conv_nuvz = c->nuvz; conv_nconvlev = c->nconvlev;
+    if ((rc = conv_alloc(0))) return rc;
+    for (int sl = 0; sl < 2; sl++) {
+      unsigned char *q = nullptr;
+      if ((rc = dalloc(&q, conv_cb_bytes(0) * conv_nuvz))) return rc;
+      conv_pplev[sl] = q;
+    }
+    if ((rc = dalloc(&conv_pcol, (size_t)P.cap)) || (rc = dalloc(&conv_draws, (size_t)P.cap))) return rc;
+    if ((rc = dalloc(&conv_nmoved, (size_t)1))) return rc;
+    {
+      unsigned char *q = nullptr;
+      if ((rc = dalloc(&q, (size_t)P.cap * hb))) return rc;
+      conv_rn = q;
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    conv_on = true; conv_gfs = true;
+    met_format = MET_GFS;
+    return 0;
+  }
+  int upload_conv_gfs_fields(int slot, const fpx_conv_gfs_fields *f) override {
+    if (!conv_gfs) return fail(FPX_ERR_STATE, "upload_conv_gfs_fields: fpx_conv_init_gfs first");
+    if (slot != 1 && slot != 2) return fail(FPX_ERR_ARG, "upload_conv_gfs_fields: slot must be 1 or 2");
+    if (!f || !f->ps || !f->tt2 || !f->td2 || !f->tt || !f->qv || !f->pplev) return fail(FPX_ERR_ARG, "upload_conv_gfs_fields: ps, tt2, td2, tt, qv, pplev are required");
+    if (f->nzmax < conv_nuvz) return fail(FPX_ERR_ARG, "upload_conv_gfs_fields: nzmax < nuvz");
+    int rc;
+    const void *src[6] = {f->ps, f->tt2, f->td2, f->tt, f->qv, f->pplev};
+    for (int i = 0; i < 6; i++)
+      if ((rc = compact(host_grid(0), src[i], i < 5 ? conv_fld[0][i][slot - 1] : conv_pplev[slot - 1], i < 3 ? 1 : conv_nuvz, i < 3 ? 1 : f->nzmax))) return rc;
+    conv_slot[0][slot - 1] = true;
+    return 0;
+  }
+  // fpx_verttransform_gfs after fpx_conv_init_gfs: the slot's ps, tt2, td2, tt, qv, pplev stay on the device for the convection
+  // (device to device; the transform's buffers are in the host's kind and layout)
+  template <typename H>
+  int conv_keep_gfs(int slot, const H *ps, const H *tt2, const H *td2, const H *tt, const H *qv, const H *pplev) {
+    const HostGrid g = host_grid(0);
+    const H *src[6] = {ps, tt2, td2, tt, qv, pplev};
+    for (int i = 0; i < 6; i++) {
+      const int nlev = i < 3 ? 1 : conv_nuvz;
+      const dim3 grid((g.nx + 31) / 32, (nlev + 7) / 8, g.ny), block(32, 8);
+      cvg::k_cvg_compact<H><<<grid, block, 0, stream>>>(src[i], (H *)(i < 5 ? conv_fld[0][i][slot - 1] : conv_pplev[slot - 1]), g.nx, g.ny, nlev, g.nxmax, g.nymax);
+    }
+    HIPCHK(hipGetLastError());
+    conv_slot[0][slot - 1] = true;
+    return 0;
+  }
+  // fpx_conv_soundings: one gather kernel over the vectors of the last call's scratch; nothing of fpx_convmix runs
+  template <typename H>
+  int conv_soundings_t(const int32_t *col, int nreq, void *psconv, void *pconv, void *phconv, void *dpr, void *tconv, void *qconv) {
+    const int nuvz = conv_nuvz, nv = conv_nuvz + 2;
+    const ConvLast &L = conv_last;
+    const size_t n1 = (size_t)nreq * (nuvz - 1), nh = (size_t)nreq * nuvz;
+    Scratch ibuf, rbuf;
+    hipError_t e = ibuf.reserve((size_t)nreq * sizeof(int), stream);
+    if (e == hipSuccess) e = rbuf.reserve(((size_t)nreq + 4 * n1 + nh) * sizeof(H), stream);
+    if (e != hipSuccess) return fail(FPX_ERR_NOMEM, std::string("conv_soundings: ") + hipGetErrorString(e));
+    int *d_col = ibuf.as<int>();
+    H *d_ps = rbuf.as<H>(), *d_pc = d_ps + nreq, *d_ph = d_pc + n1, *d_dpr = d_ph + nh, *d_tc = d_dpr + n1, *d_qc = d_tc + n1;
+    HIPCHK(hipMemcpyAsync(d_col, col, (size_t)nreq * sizeof(int), hipMemcpyHostToDevice, stream));
+    H *vbuf = nullptr, *cst = nullptr;
+    if (L.nact > 0) {                                      // the layout of convmix_t's scratch
+      vbuf = conv_scr.as<H>();
+      cst = vbuf + conv::vec_elems_per_column<H>(nv) * conv::group_round((size_t)L.nact);
+    }
+    cvg::k_conv_soundings<H><<<nreq, 64, 0, stream>>>(d_col, L.ncol, conv_flag, conv_rank, vbuf, cst, nv, L.nact, nuvz, d_ps, d_pc, d_ph, d_dpr, d_tc, d_qc);
+    HIPCHK(hipGetLastError());
+    if (psconv) HIPCHK(hipMemcpyAsync(psconv, d_ps, (size_t)nreq * sizeof(H), hipMemcpyDeviceToHost, stream));
+    if (pconv) HIPCHK(hipMemcpyAsync(pconv, d_pc, n1 * sizeof(H), hipMemcpyDeviceToHost, stream));
+    if (phconv) HIPCHK(hipMemcpyAsync(phconv, d_ph, nh * sizeof(H), hipMemcpyDeviceToHost, stream));
+    if (dpr) HIPCHK(hipMemcpyAsync(dpr, d_dpr, n1 * sizeof(H), hipMemcpyDeviceToHost, stream));
+    if (tconv) HIPCHK(hipMemcpyAsync(tconv, d_tc, n1 * sizeof(H), hipMemcpyDeviceToHost, stream));
+    if (qconv) HIPCHK(hipMemcpyAsync(qconv, d_qc, n1 * sizeof(H), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  int conv_soundings(const int32_t *col, int nreq, void *psconv, void *pconv, void *phconv, void *dpr, void *tconv, void *qconv) override {
+    if (!conv_on) return fail(FPX_ERR_STATE, "conv_soundings: fpx_conv_init or fpx_conv_init_gfs first");
+    if (!conv_last.valid) return fail(FPX_ERR_STATE, "conv_soundings: no completed call of fpx_convmix to report");
+    if (nreq < 0 || (nreq > 0 && !col)) return fail(FPX_ERR_ARG, "conv_soundings: ncol < 0 or col is null");
+    for (int i = 0; i < nreq; i++)
+      if (col[i] < 0 || col[i] >= conv_last.ncol) return fail(FPX_ERR_ARG, "conv_soundings: column out of range (mother grid first, then the nests)");
+    if (nreq == 0) return 0;
+    return cfg.host_real_bytes == 4 ? conv_soundings_t<float>(col, nreq, psconv, pconv, phconv, dpr, tconv, qconv)
+                                    : conv_soundings_t<double>(col, nreq, psconv, pconv, phconv, dpr, tconv, qconv);
+  }
+
   int convmix(int itime, int64_t *nmoved) override {
-    if (met_format == MET_GFS) return fail(FPX_ERR_UNSUPPORTED, "convmix: NCEP GFS fields: convmix.f90:100-116,173-189 (pplev-based columns) and the NCEP branch of calcmatrix.f90 are not computed by this engine");
+    if (met_format == MET_GFS && !conv_gfs) return fail(FPX_ERR_UNSUPPORTED, "convmix: NCEP GFS fields: convmix.f90:100-116,173-189 (pplev-based columns) and the NCEP branch of calcmatrix.f90 need fpx_conv_init_gfs on this handle");
     if (!conv_on) return fail(FPX_ERR_STATE, "convmix: fpx_conv_init first");
+    if (conv_gfs && V.numbnests) return fail(FPX_ERR_UNSUPPORTED, "convmix: NCEP GFS fields with nested wind fields: the reference has no GFS nests");
+    if (conv_gfs && (!conv_slot[0][0] || !conv_slot[0][1])) return fail(FPX_ERR_STATE, "convmix: fpx_upload_conv_gfs_fields or fpx_verttransform_gfs of both slots first");
     if (!conv_slot[0][0] || !conv_slot[0][1]) return fail(FPX_ERR_STATE, "convmix: fpx_upload_conv_fields of both slots first");
     for (int l = 1; l <= V.numbnests; l++)
       if (!conv_slot[l][0] || !conv_slot[l][1]) return fail(FPX_ERR_STATE, "convmix: fpx_upload_conv_nest_fields of both slots of every nest first");
@@ -4816,6 +4926,7 @@ struct Engine : EngineBase {
     if (!n || n->struct_bytes != (int32_t)sizeof(fpx_nests)) return fail(FPX_ERR_ARG, "nests_init: null or fpx_nests size mismatch (ABI)");
     if (n->numbnests < 1 || n->numbnests > kMaxNests) return fail(FPX_ERR_ARG, "nests_init: numbnests out of range");
     if (V.numbnests) return fail(FPX_ERR_STATE, "nests_init: already initialised");
+    if (conv_gfs) return fail(FPX_ERR_UNSUPPORTED, "nests_init: fpx_conv_init_gfs has run on this handle: the reference has no GFS nests");
     if (cfg.interpolhmix) return fail(FPX_ERR_UNSUPPORTED, "nests_init: interpolhmix with nested wind fields -- the reference reads the unset h1 for a particle inside a nest (advance.f90:254-266)");
     int rc;
     for (int l = 0; l < n->numbnests; l++) {
@@ -5338,6 +5449,12 @@ int fpx_convmix_time(fpx_handle h, double *ms) { FPX_GUARD(h); if (!ms) return F
 int fpx_conv_columns(fpx_handle h, const int32_t *col, int32_t ncol, int32_t *lconv, int32_t *nconvtop, void *fmassfrac, void *uvzlev) {
   FPX_GUARD(h);
   return h->impl->conv_columns(col, ncol, lconv, nconvtop, fmassfrac, uvzlev);
+}
+int fpx_conv_init_gfs(fpx_handle h, const fpx_conv_gfs_config *c) { FPX_GUARD(h); return h->impl->conv_init_gfs(c); }
+int fpx_upload_conv_gfs_fields(fpx_handle h, int32_t slot, const fpx_conv_gfs_fields *f) { FPX_GUARD(h); return h->impl->upload_conv_gfs_fields(slot, f); }
+int fpx_conv_soundings(fpx_handle h, const int32_t *col, int32_t ncol, void *psconv, void *pconv, void *phconv, void *dpr, void *tconv, void *qconv) {
+  FPX_GUARD(h);
+  return h->impl->conv_soundings(col, ncol, psconv, pconv, phconv, dpr, tconv, qconv);
 }
 int fpx_upload_diag_nest_fields(fpx_handle h, int32_t nest, int32_t slot, const fpx_diag_fields *f) { FPX_GUARD(h); return h->impl->upload_diag_nest_fields(nest, slot, f); }
 int fpx_upload_conv_nest_fields(fpx_handle h, int32_t nest, int32_t slot, const fpx_conv_fields *f) { FPX_GUARD(h); return h->impl->upload_conv_nest_fields(nest, slot, f); }

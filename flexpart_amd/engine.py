@@ -692,6 +692,52 @@ class Engine:
               "fpx_conv_columns")
         return lconv, ntop, fm.astype(np.float64), uvz.astype(np.float64)
 
+    # ---- the NCEP GFS branch (fpx_conv_init_gfs / fpx_upload_conv_gfs_fields / fpx_conv_soundings) ----
+    def conv_init_gfs(self, cs):
+        """Level structure of a synthetic.convection_case_gfs()-like dict: grid[2] = nuvz (= nz of the engine), nconvlev."""
+        from ._lib import FpxConvGfsConfig
+        c = FpxConvGfsConfig()
+        c.struct_bytes = C.sizeof(FpxConvGfsConfig)
+        c.nuvz, c.nconvlev = int(cs["grid"][2]), int(cs["nconvlev"])
+        check(self.lib.fpx_conv_init_gfs(self.h, C.byref(c)), "fpx_conv_init_gfs")
+        self.conv_nuvz, self.conv_nconvlev = c.nuvz, c.nconvlev
+        self.has_conv = True
+
+    def upload_conv_gfs_fields(self, slot, ps, tt2, td2, tt, qv, pplev, nzmax=None):
+        """One wind-field slot of ps, tt2, td2 [ny][nx] and the z-level tt, qv, pplev [nz][ny][nx] (compact), padded to the
+        host layout (nxmax, nymax, nzmax)."""
+        from ._lib import FpxConvGfsFields
+        rt = self.hreal
+        nz = int(np.asarray(tt).shape[0])
+        nzmax = self.nzmax if nzmax is None else int(nzmax)
+        f = FpxConvGfsFields()
+        keep = {}
+        for k, a in (("ps", ps), ("tt2", tt2), ("td2", td2)):
+            b = np.zeros((self.nymax, self.nxmax), rt)
+            b[: self.ny, : self.nx] = a
+            keep[k] = b
+            setattr(f, k, b.ctypes.data)
+        for k, a in (("tt", tt), ("qv", qv), ("pplev", pplev)):
+            b = np.zeros((max(nzmax, 1), self.nymax, self.nxmax), rt)
+            b[: min(nz, nzmax), : self.ny, : self.nx] = np.asarray(a)[: min(nz, nzmax)]
+            keep[k] = b
+            setattr(f, k, b.ctypes.data)
+        f.nzmax = nzmax
+        check(self.lib.fpx_upload_conv_gfs_fields(self.h, int(slot), C.byref(f)), "fpx_upload_conv_gfs_fields")
+
+    def conv_soundings(self, cols):
+        """fpx_conv_soundings: the soundings the last convmix() left for the columns `cols` -> dict of psconv [n], pconv, dpr,
+        tconv, qconv [n][nuvz-1], phconv [n][nuvz] in the host's real kind (bit for bit what the device holds); zeros for a
+        column the call did not visit."""
+        col = np.ascontiguousarray(cols, np.int32).ravel()
+        n, nuvz = int(col.size), self.conv_nuvz
+        out = {"psconv": np.zeros(n, self.hreal), "phconv": np.zeros((n, nuvz), self.hreal)}
+        for k in ("pconv", "dpr", "tconv", "qconv"):
+            out[k] = np.zeros((n, nuvz - 1), self.hreal)
+        check(self.lib.fpx_conv_soundings(self.h, col.ctypes.data, n, *(out[k].ctypes.data for k in ("psconv", "pconv", "phconv", "dpr", "tconv", "qconv"))),
+              "fpx_conv_soundings")
+        return out
+
     def cbaseflux(self, new=None):
         a = np.zeros((self.ny, self.nx), self.hreal)
         if new is not None:

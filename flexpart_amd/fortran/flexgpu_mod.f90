@@ -45,7 +45,8 @@ module flexgpu_mod
             flexgpu_getvdep_init, flexgpu_getvdep, &
             flexgpu_redist_plan, flexgpu_redist_bytes, flexgpu_redist_pack, flexgpu_redist_unpack, &
             flexgpu_checkpoint_write, flexgpu_checkpoint_read, &
-            flexgpu_conv_init, flexgpu_upload_conv_fields, flexgpu_convmix, flexgpu_cbaseflux, flexgpu_fluxoutput
+            flexgpu_conv_init, flexgpu_upload_conv_fields, flexgpu_convmix, flexgpu_cbaseflux, flexgpu_fluxoutput, &
+            flexgpu_conv_init_gfs, flexgpu_upload_conv_gfs_fields, flexgpu_convmix_gfs
 #ifdef FLEXGPU_FLUX
   public :: flexgpu_get_flux
 #endif
@@ -211,6 +212,13 @@ module flexgpu_mod
     type(c_ptr) :: ps, tt2, td2, tth, qvh
     integer(c_int32_t) :: nuvzmax, reserved
   end type fpx_conv_fields
+  type, bind(C) :: fpx_conv_gfs_config
+    integer(c_int32_t) :: struct_bytes, nuvz, nconvlev, reserved
+  end type fpx_conv_gfs_config
+  type, bind(C) :: fpx_conv_gfs_fields
+    type(c_ptr) :: ps, tt2, td2, tt, qv, pplev
+    integer(c_int32_t) :: nzmax, reserved
+  end type fpx_conv_gfs_fields
 
   type, bind(C) :: fpx_release
     integer(c_int32_t) :: struct_bytes, numpoint
@@ -465,6 +473,23 @@ module flexgpu_mod
       integer(c_int32_t), value :: slot
       type(fpx_conv_fields), intent(in) :: f
     end function fpx_upload_conv_fields
+    integer(c_int) function fpx_conv_init_gfs(h, c) bind(C, name='fpx_conv_init_gfs')
+      import :: c_ptr, c_int, fpx_conv_gfs_config
+      type(c_ptr), value :: h
+      type(fpx_conv_gfs_config), intent(in) :: c
+    end function fpx_conv_init_gfs
+    integer(c_int) function fpx_upload_conv_gfs_fields(h, slot, f) bind(C, name='fpx_upload_conv_gfs_fields')
+      import :: c_ptr, c_int, c_int32_t, fpx_conv_gfs_fields
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: slot
+      type(fpx_conv_gfs_fields), intent(in) :: f
+    end function fpx_upload_conv_gfs_fields
+    integer(c_int) function fpx_conv_soundings(h, col, ncol, psconv, pconv, phconv, dpr, tconv, qconv) bind(C, name='fpx_conv_soundings')
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: h, col
+      integer(c_int32_t), value :: ncol
+      type(c_ptr), value :: psconv, pconv, phconv, dpr, tconv, qconv
+    end function fpx_conv_soundings
     integer(c_int) function fpx_convmix(h, itime, nmoved) bind(C, name='fpx_convmix')
       import :: c_ptr, c_int, c_int32_t
       type(c_ptr), value :: h
@@ -1107,6 +1132,35 @@ contains
     integer, intent(out) :: ierr
     ierr = fpx_convmix(flexgpu_handle, int(itime, c_int32_t), c_null_ptr)
   end subroutine flexgpu_convmix
+
+  ! ---- the same with NCEP GFS fields (the GRIBFILE_CENTRE_NCEP branches of convmix.f90, calcmatrix.f90) ----------------------
+  ! after gridcheck_gfs (nuvz, nconvlev of gridcheck_gfs.f90:513-522); no akz .. bkm: the sounding comes from pplev
+  subroutine flexgpu_conv_init_gfs(ierr)
+    integer, intent(out) :: ierr
+    type(fpx_conv_gfs_config) :: c
+    c%struct_bytes = int(c_sizeof(c), c_int32_t)
+    c%nuvz = nuvz; c%nconvlev = nconvlev; c%reserved = 0
+    ierr = fpx_conv_init_gfs(flexgpu_handle, c)
+  end subroutine flexgpu_conv_init_gfs
+
+  ! after verttransform_gfs filled slot n on the host: ps, tt2, td2 and the z-level tt, qv, pplev of that slot.  Not needed when
+  ! the slot went through fpx_verttransform_gfs after flexgpu_conv_init_gfs: the engine kept the six fields on the device.
+  subroutine flexgpu_upload_conv_gfs_fields(n, ierr)
+    integer, intent(in) :: n
+    integer, intent(out) :: ierr
+    type(fpx_conv_gfs_fields) :: f
+    f%ps = loc_r(ps(0,0,1,n)); f%tt2 = loc_r(tt2(0,0,1,n)); f%td2 = loc_r(td2(0,0,1,n))
+    f%tt = loc_r(tt(0,0,1,n)); f%qv = loc_r(qv(0,0,1,n)); f%pplev = loc_r(pplev(0,0,1,n))
+    f%nzmax = min(nzmax, nuvzmax); f%reserved = 0      ! tt, qv: nzmax levels, pplev: nuvzmax (com_mod.f90:377)
+    ierr = fpx_upload_conv_gfs_fields(flexgpu_handle, int(n, c_int32_t), f)
+  end subroutine flexgpu_upload_conv_gfs_fields
+
+  ! replaces `call convmix(itime,metdata_format)` of a run with metdata_format = GRIBFILE_CENTRE_NCEP: the same entry point
+  subroutine flexgpu_convmix_gfs(itime, ierr)
+    integer, intent(in) :: itime
+    integer, intent(out) :: ierr
+    ierr = fpx_convmix(flexgpu_handle, int(itime, c_int32_t), c_null_ptr)
+  end subroutine flexgpu_convmix_gfs
 
   ! conv_mod cbaseflux(0:nxmax-1,0:nymax-1) <-> the engine's field (set = .true.: host -> device, e.g. from a restart file)
   subroutine flexgpu_cbaseflux(set, ierr)

@@ -876,6 +876,74 @@ def convection_case(nx=24, ny=16, nuvz=46, n=4000, ncalls=3, ldirect=1, lsynctim
     return out
 
 
+def nconvlev_gfs(akz):
+    """gridcheck_gfs.f90:513-517: the first level i <= nuvz-2 whose pressure akz(i) (bkz = 0) lies below 50 hPa; a loop that runs
+    out leaves i = nuvz - 1.  The clamp to nconvlevmax - 1 (:518-522) is the host's compile-time size and is not applied here."""
+    nuvz = len(akz)
+    for i in range(1, nuvz - 1):
+        if float(akz[i - 1]) < 5000.0:
+            return i
+    return nuvz - 1
+
+
+def convection_case_gfs(nx=24, ny=16, nz=26, n=4000, ncalls=3, ldirect=1, lsynctime=900, seed=11, terrain=False, deep=False):
+    """NCEP-GFS-shaped input of the convection scheme (convmix.f90:180-188): two time slots of ps, tt2, td2 and of the z-level
+    fields tt, qv, pplev [2][nz][ny][nx], as verttransform_gfs leaves them.  The columns have the shape of the GFS pressure
+    levels: pplev(.,.,k) = ps * GFS_PLEV_HPA[k] / 1000 hPa with a wave of a few tenths of a per cent on it, pplev(.,.,1) up to
+    30 Pa below ps.  nuvz = nz, akz = the pressures of the levels, nconvlev as gridcheck_gfs.f90:513-517 computes it.  The
+    soundings are those of convection_case() on these pressures -- deep convection over shallow and marginal cases -- with
+    patches of cold columns (CONVECT's exit on tconv(nk) < 250), of columns without moisture (the same exit, qconv(nk) <= 0)
+    and of very dry ones heated at the ground (its exit on the lifting condensation level); stable columns without a mass flux from before take the
+    exit on the buoyancy at cloud base.  terrain: ps down to about 700 hPa.  The stratosphere warms with height, which keeps
+    the deepest convection at nconvtop <= nconvlev; deep: an isothermal one instead, so that CONVECT's inb reaches nconvlev and
+    nconvtop = nconvlev + 1 -- with nz = 26 that is nuvz - 1, and redist reads level nuvz, which no GFS run writes.  Particles, due flags, times and cbaseflux as in
+    convection_case()."""
+    if not 6 <= nz <= len(GFS_PLEV_HPA):
+        raise ValueError("convection_case_gfs: 6 <= nz <= %d" % len(GFS_PLEV_HPA))
+    per = nx
+    i = np.arange(nx, dtype=np.int64)[None, None, :]
+    j = np.arange(ny, dtype=np.int64)[None, :, None]
+    kk = np.arange(nz, dtype=np.int64)[:, None, None]
+    akz = 100.0 * np.array(GFS_PLEV_HPA[:nz], np.float64)
+    ratio = (akz / akz[0])[:, None, None]
+    res = {}
+    for slot in range(2):
+        ii = i + 3 * slot
+        warm = 0.5 + 0.5 * _wave(ii[0] + 2 * j[0], per)                  # 0 ... 1: cold/dry ... warm/moist
+        ps = 101300.0 + 600.0 * _wave(2 * ii[0] + j[0], per) - (31000.0 if terrain else 14000.0) * np.maximum(0.0, _wave(3 * ii[0] + 5 * j[0], 2 * per)) ** 3
+        p = ps[None] * ratio * (1.0 + 0.003 * _wave(ii + j + 2 * kk, per))
+        p[0] = ps - 15.0 * (1.0 + _wave(ii[0] + 3 * j[0], per))
+        z = -7600.0 * np.log(p / ps[None])
+        tsfc = 271.0 + 31.0 * warm
+        lapse = 0.0055 + 0.0015 * warm
+        # a stratosphere that warms with height keeps the deepest convection below nconvlev (nconvtop <= nconvlev)
+        tt = np.maximum(tsfc[None] - lapse[None] * z, 198.0 + 8.0 * warm[None] + (0.0 if deep else 0.0025) * np.maximum(z - 12000.0, 0.0)) + 0.4 * _wave(ii + j + 3 * kk, per)
+        rh = (0.25 + 0.65 * warm[None]) * np.exp(-z / (5000.0 + 4000.0 * warm[None])) + 0.05
+        cold = ((2 * ii[0] + j[0]) % 13 == 0)
+        nomoist = ((ii[0] + 4 * j[0]) % 17 == 3)
+        dry = ((ii[0] + 3 * j[0]) % 11 == 5) & ~nomoist
+        tt = tt - 50.0 * cold[None]
+        tt[0] += 3.0 * dry            # superadiabatic at the ground: hm has its minimum at level 2, the parcel starts at level 1
+        tc = tt - 273.15
+        es = 611.2 * np.exp(17.67 * tc / (tc + 243.5))
+        qs = 0.622 * es / np.maximum(p - 0.378 * es, 1.0)
+        qv = np.minimum(rh, 0.98) * qs * np.where(dry, 1.0e-5, 1.0)[None] * np.where(nomoist, 0.0, 1.0)[None]
+        tt2 = tt[0] + 0.6
+        td2 = tt2 - (2.0 + 14.0 * (1.0 - warm))
+        res[slot] = (ps, tt2, td2, tt, qv, p)
+    out = {key: np.stack([res[0][idx], res[1][idx]]) for idx, key in enumerate(("ps", "tt2", "td2", "tt", "qv", "pplev"))}
+    warm0 = 0.5 + 0.5 * _wave(i[0] + 2 * j[0], per)
+    cb0 = np.where(warm0 > 0.55, 0.12 * warm0 ** 2, 0.0)
+    u = [_splitmix64(n, seed + q).astype(np.float64) / 2.0 ** 64 for q in range(4)]
+    height = make_height(nz, top=80000.0 if nz >= 60 else 30000.0, lin=0.05 if nz >= 60 else 0.15)     # base_scenario's z levels
+    out.update(akz=akz, grid=np.array([nx, ny, nz], np.int32), nconvlev=nconvlev_gfs(akz), ldirect=int(ldirect), lsynctime=int(lsynctime) * int(ldirect),
+               memtime=np.array([0, 10800 * int(ldirect)], np.int32), itimes=np.arange(ncalls, dtype=np.int32) * int(lsynctime) * int(ldirect),
+               height_nz=float(height[-1]), cbaseflux=cb0,
+               xtra1=0.3 + u[0] * (nx - 1.6), ytra1=0.3 + u[1] * (ny - 1.6), ztra1=16000.0 * u[2] ** 1.5,
+               due=(u[3][:, None] + 0.013 * np.arange(ncalls)[None, :]) % 1.0 > 0.1, npart=n)
+    return out
+
+
 # --------------------------------------------------------------------------
 # getvdep (calcpar.f90:171-189): land use, resistance tables, the surface fields it reads
 # --------------------------------------------------------------------------

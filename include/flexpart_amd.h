@@ -279,7 +279,8 @@ int fpx_verttransform_nest(fpx_handle h, int32_t nest, int32_t slot, const fpx_m
  * leaves out its cloud diagnostics.
  * A handle becomes a GFS handle at its first fpx_verttransform_gfs.  On it fpx_calcpar, fpx_calcpar_nest, fpx_conv_init,
  * fpx_convmix, fpx_verttransform_ecmwf and fpx_verttransform_nest return FPX_ERR_UNSUPPORTED (their ECMWF arithmetic would be
- * wrong on GFS data; fpx_calcpar_gfs is the GFS counterpart of fpx_calcpar), and fpx_verttransform_gfs is refused on a handle
+ * wrong on GFS data; fpx_calcpar_gfs is the GFS counterpart of fpx_calcpar, fpx_conv_init_gfs that of fpx_conv_init, after
+ * which fpx_convmix works on the handle), and fpx_verttransform_gfs is refused on a handle
  * that has run an ECMWF transform.  fpx_getvdep has no format branch (getvdep.f90) and works on either. */
 int fpx_verttransform_gfs(fpx_handle h, int32_t slot, const fpx_model_levels *m, const fpx_fields *sfc, const fpx_fields_out *out, void *pplev_out);
 /* device time of the transform kernels of the last call, milliseconds (without the PV kernels of a call with pvh = NULL) */
@@ -1107,6 +1108,48 @@ int fpx_set_option(fpx_handle h, const char *name, const char *value);
  * outside the mother grid; one synchronising copy), "oh_branch" (what the last fpx_gethourlyOH did: 0 nothing, 1 advanced the
  * pair by an hour, 2 computed both fields; -1 before the first call).  Unknown names return FPX_ERR_ARG. */
 int fpx_get_info(fpx_handle h, const char *name, int64_t *value);
+
+/* ---- convective mixing with NCEP GFS fields (the GRIBFILE_CENTRE_NCEP branches of convmix.f90 and calcmatrix.f90) ---------
+ * fpx_conv_init_gfs is the NCEP counterpart of fpx_conv_init, as fpx_calcpar_gfs is of fpx_calcpar.  The GFS path differs from
+ * the ECMWF one in the sounding of a column -- pconv, tconv, qconv(kz), kz = 1 .. nuvz-1, are the time interpolation of the
+ * z-level pplev, tt, qv at level kz (convmix.f90:180-188), phconv(kuvz) = 0.5*(pconv(kuvz) + pconv(kuvz-1)) (calcmatrix.f90:72-77)
+ * -- so no akz .. bkm are needed; in nconvlev (gridcheck_gfs.f90:513-522: nuvz - 2 for the standard GFS levels); and in the nest
+ * test without eps (convmix.f90:108-116), which is never reached: the reference has no GFS nests, and this call is refused once
+ * fpx_nests_init has run (fpx_nests_init is refused after it).
+ * Requires nuvz == fpx_config.nz and 2 <= nconvlev <= nuvz - 2 (FPX_ERR_ARG).  Allowed on a handle that has run no transform;
+ * it makes the handle a GFS handle.  FPX_ERR_STATE if convection is already initialised; FPX_ERR_UNSUPPORTED on a handle that
+ * has run an ECMWF transform, after fpx_nests_init, and with device_flux = 1 (for the reason fpx_conv_init gives).
+ * Allocates cbaseflux at zero, the per-particle arrays of fpx_conv_init and, per slot, device buffers for ps, tt2, td2, tt, qv,
+ * pplev in the host's real kind, compact [level][jy][ix] (nuvz levels: (3 + 3*nuvz) * nx * ny reals per slot).
+ * A slot is filled in one of two ways, equal bit for bit:
+ *   fpx_upload_conv_gfs_fields takes com_mod's arrays of slot n;
+ *   every fpx_verttransform_gfs(h, slot, ..) after fpx_conv_init_gfs keeps the slot's six fields by a device-to-device copy
+ *   (nothing crosses to the host) and marks the slot filled.
+ * fpx_convmix then behaves as on an ECMWF handle (FPX_ERR_STATE until both slots are filled, fpx_set_windtime has been called
+ * and the height is set); fpx_get/set_cbaseflux, fpx_convmix_time, fpx_conv_columns, the "conv_*" options and the checkpoint's
+ * cbaseflux work unchanged.  On a GFS handle fpx_conv_init stays refused, and fpx_convmix is refused until fpx_conv_init_gfs
+ * has run.
+ * Reproduced quirk: phconv(nuvz) reads pconv(nuvz), which no GFS run writes (convmix.f90:181 stops at nuvz - 1, for tconv and
+ * qconv too; conv_mod's arrays are static and hold zeros there).  The engine uses 0 for it and stores 0 to pconv, tconv and
+ * qconv at level nuvz of every visited column, which redist.f90:74-85 reads when nconvtop = nconvlev + 1 = nuvz - 1 (possible on
+ * the standard GFS levels): the top half-level height then comes out as in the reference.  No result depends on any of it
+ * while nconvtop <= nconvlev.  fpx_upload_conv_fields and fpx_upload_conv_nest_fields are refused (FPX_ERR_UNSUPPORTED) after
+ * fpx_conv_init_gfs.
+ * fpx_conv_soundings: a diagnostic beside fpx_conv_columns, with its column numbering; works on ECMWF handles too.  Returns, in
+ * the host's real kind, what the last fpx_convmix left in its scratch for each column: psconv[ncol], pconv[ncol][nuvz-1],
+ * phconv[ncol][nuvz], dpr[ncol][nuvz-1], tconv[ncol][nuvz-1], qconv[ncol][nuvz-1]; zeros for a column the call did not visit.
+ * Every output may be NULL.  Runs no kernel of fpx_convmix.  FPX_ERR_STATE before the first completed fpx_convmix (the vectors
+ * exist for every visited column, so several matrix batches do not matter here); FPX_ERR_ARG for a column out of range. */
+typedef struct { int32_t struct_bytes, nuvz, nconvlev, reserved; } fpx_conv_gfs_config;
+typedef struct {
+  const void *ps, *tt2, *td2;      /* (0:nxmax-1,0:nymax-1)        c_loc(ps(0,0,1,n)) ...          */
+  const void *tt, *qv, *pplev;     /* (0:nxmax-1,0:nymax-1,nzmax)  z-level fields of slot n        */
+  int32_t nzmax, reserved;
+} fpx_conv_gfs_fields;
+int fpx_conv_init_gfs(fpx_handle h, const fpx_conv_gfs_config *c);
+int fpx_upload_conv_gfs_fields(fpx_handle h, int32_t slot, const fpx_conv_gfs_fields *f);
+int fpx_conv_soundings(fpx_handle h, const int32_t *col, int32_t ncol, void *psconv, void *pconv, void *phconv,
+                       void *dpr, void *tconv, void *qconv);
 
 #ifdef __cplusplus
 }
